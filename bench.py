@@ -2,7 +2,7 @@
 # -*- coding: utf-8 -*-
 """Benchmark of the link-prediction hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one full ``LinkPredictionEvaluator.evaluate`` over the test split of
 the workload (default: BASELINE.json configs[1] = TransE dim=200 L2 on an
@@ -24,8 +24,8 @@ N > 1 (launched by torch.distributed.run, one rank per GPU over RCCL):
                    dataset-sized test split against its replica of the tables (no collective).
   --scaling strong --shard queries   the test facts split across ranks, tables replicated.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra
-objects: "roofline" (dominant kernel timed live with HIP events on the launch
+Rank 0 prints ONE JSON line; a plain run times the headline only, and with --full
+the line carries two extra objects: "roofline" (dominant kernel timed live with HIP events on the launch
 stream) and "cpu_baseline" (the oracle = reference CPU algorithm, timed on the
 host cores of this box on a bounded sample; N=1 only), plus "parity_full_split":
 every rank of the WHOLE test split against the reference algorithm run on ATen
@@ -34,7 +34,8 @@ GPU ops (oracle.lp_evaluate(device=cuda)).
 Workload realism: the synthetic KG is Zipf-skewed with planted hub
 keys (filter lists of thousands of entities, --kg uniform gives the r01 graph), and
 the model is "trained-like" by default (--weights trained: a few hundred steps of the
-engine's own training step -- Bernoulli negatives, margin loss, Adam -- on the full
+reference training step -- Bernoulli negatives, margin loss, Adam, scores and gradients
+on deterministic ATen ops, so the tables are the same on every run -- on the full
 synthetic graph before the timed region, so true ranks are small and near-ties
 dense; --weights xavier = the constructor's initialisation).
 """
@@ -121,7 +122,7 @@ def parse():
                          'includes the hub keys -- filter lists of 10^5 entities)')
     ap.add_argument('--train-steps', type=int, default=None)
     ap.add_argument('--only-timed', action='store_true',
-                    help='profiling aid: nothing but the warm-up and the timed loop (no roofline / f32 / cpu / parity legs)')
+                    help='profiling aid: nothing but the warm-up and the timed loop, even with --full (what a plain run does)')
     ap.add_argument('--no-traffic', action='store_true',
                     help='skip the two rocprofv3 --pmc child passes that measure the dominant kernel\'s HBM-side bytes')
     ap.add_argument('--no-full-parity', action='store_true',
@@ -129,6 +130,14 @@ def parse():
     ap.add_argument('--launch-check', action='store_true',
                     help='only prove the N-rank launch: rendezvous on 127.0.0.1, one all-reduce over the ranks, rank 0 prints '
                          'a JSON line -- no GPU is touched (CPU test of the self-launch path, --backend gloo)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline: first-call parts, cold steps, the fp32-only '
+                         'leg, roofline and counters, CPU baseline, parity against the reference algorithm, secondary '
+                         'timings, fresh-evaluator loop, and at N > 1 the other exchange / partition / weak mode / cfg4 '
+                         '(default: set-up, warm-up, the timed steps and the result line only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed evaluate() computed (its four rank vectors and '
+                         'the metrics derived from them) as DIR/<name>.npy in float64')
     return ap.parse_args()
 
 
@@ -168,13 +177,30 @@ TRAIN_DEFAULTS = {'steps': 500, 'batch': 32768, 'lr': 1e-2, 'margin': 0.5}
 TRAIN_DEFAULTS_BIG = {'steps': 300, 'batch': 1 << 21, 'lr': 1e-2, 'margin': 0.5}
 
 
+TRAIN_CHUNK = 1 << 18      # triples per forward / backward pass of one training step (bounds the ATen temporaries)
+
+
+def _kind_and_p(model):
+    import torchkge_amd as tk
+    for cls, kind in ((tk.TransEModel, 'transe'), (tk.TransHModel, 'transh'), (tk.TransDModel, 'transd'),
+                      (tk.DistMultModel, 'distmult'), (tk.ComplExModel, 'complex')):
+        if isinstance(model, cls):
+            return kind, 1 if getattr(model, 'dissimilarity_type', 'L2') == 'L1' else 2
+    raise ValueError(type(model).__name__)
+
+
 def train_like(model, kg, steps=None, batch=None, lr=None, margin=None, seed=0):
-    """"Trained-like" weights: `steps` steps of the engine's own training path on the FULL graph
-    `kg` (corrupt_batch -> Model.forward -> MarginLoss -> backward -> Adam), entity tables
+    """"Trained-like" weights: `steps` steps of the reference training loop on the FULL graph
+    `kg` (corrupt_batch -> forward -> MarginLoss -> backward -> Adam), entity tables
     re-normalised every epoch and at the end as utils/training.py:186-188 does.  The synthetic graph has
     no held-out structure, so the test facts are trained on too: what is wanted is the score
-    DISTRIBUTION of a fitted model (small true ranks, clustered embeddings, dense near-ties)."""
+    DISTRIBUTION of a fitted model (small true ranks, clustered embeddings, dense near-ties).
+    The scores and their gradients are the reference formulas on ATen ops (oracle.model_forward) with
+    deterministic algorithms: the engine's backward sums gradient rows with float atomics, so tables trained
+    through it differ from run to run; these are the same on every run and every build of the engine."""
     import torchkge_amd as tk
+    from oracle import kge_oracle as orc
+    kind, p = _kind_and_p(model)
     cfg = dict(TRAIN_DEFAULTS_BIG if model.n_ent > 2000000 else TRAIN_DEFAULTS)
     for k, v in (('steps', steps), ('batch', batch), ('lr', lr), ('margin', margin)):
         if v is not None:
@@ -189,17 +215,27 @@ def train_like(model, kg, steps=None, batch=None, lr=None, margin=None, seed=0):
     crit = tk.MarginLoss(cfg['margin'])
     opt = torch.optim.Adam(model.parameters(), lr=cfg['lr'])
     per_epoch = max(1, n // B)
-    for s in range(cfg['steps']):
-        idx = torch.randint(0, n, (B,), device=dev)
-        hh, tt, rr = h[idx], t[idx], r[idx]
-        nh, nt = samp.corrupt_batch(hh, tt, rr)
-        pos, neg = model(hh, tt, rr, nh, nt)
-        loss = crit(pos, neg)
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        opt.step()
-        if (s + 1) % per_epoch == 0:
-            model.normalize_parameters()
+    det, det_warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    import torch.utils.deterministic as tud
+    fill = tud.fill_uninitialized_memory
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    tud.fill_uninitialized_memory = False
+    try:
+        for s in range(cfg['steps']):
+            idx = torch.randint(0, n, (B,), device=dev)
+            hh, tt, rr = h[idx], t[idx], r[idx]
+            nh, nt = samp.corrupt_batch(hh, tt, rr)
+            opt.zero_grad(set_to_none=True)
+            for c in range(0, B, TRAIN_CHUNK):
+                sl = slice(c, c + TRAIN_CHUNK)
+                pos, neg = orc.model_forward(kind, model._tables(), hh[sl], tt[sl], rr[sl], nh[sl], nt[sl], p=p)
+                crit(pos, neg).backward()
+            opt.step()
+            if (s + 1) % per_epoch == 0:
+                model.normalize_parameters()
+    finally:
+        torch.use_deterministic_algorithms(det, warn_only=det_warn)
+        tud.fill_uninitialized_memory = fill
     model.normalize_parameters()
     for prm in model.parameters():
         prm.grad = None
@@ -458,6 +494,30 @@ def reference_evaluator(ref, kind, p, tables, n_ent, n_rel, heads, tails, rels, 
     return ref.evaluation.LinkPredictionEvaluator(m, kg_ref)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+RANK_VECTORS = ('rank_true_heads', 'rank_true_tails', 'filt_rank_true_heads', 'filt_rank_true_tails')
+
+
+def dump_outputs(out_dir, ev):
+    """--dump-outputs: what evaluate() hands its caller, as float64 .npy files in `out_dir` -- the raw and filtered ranks
+    of the true heads / tails (one entry per test fact, in the test split's order) and metrics.npy = [MRR, filtered MRR,
+    Hits@10, filtered Hits@10, mean rank, filtered mean rank] of the whole split.  Rank vectors beyond the size budget
+    are cut to one fixed sample of positions (seed 0, sorted), written beside them as sample_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ranks = {nm: getattr(ev, nm).detach().cpu().to(torch.float64).numpy() for nm in RANK_VECTORS}
+    n = ranks[RANK_VECTORS[0]].shape[0]
+    cap = DUMP_LIMIT_BYTES // (8 * (len(RANK_VECTORS) + 1)) - 16
+    if n > cap:
+        keep = np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+        ranks = {nm: v[keep] for nm, v in ranks.items()}
+        np.save(os.path.join(out_dir, 'sample_index.npy'), keep.astype(np.float64))
+    for nm, v in ranks.items():
+        np.save(os.path.join(out_dir, nm + '.npy'), v)
+    metrics = list(ev.mrr()) + list(ev.hit_at_k(10)) + list(ev.mean_rank())
+    np.save(os.path.join(out_dir, 'metrics.npy'), np.array(metrics, dtype=np.float64))
+
+
 def _flush_c_stdio():
     """RCCL writes a banner through C stdio; on a piped stdout it would otherwise surface after the JSON line."""
     try:
@@ -598,6 +658,8 @@ def _self_launch(n):
 
 def main():
     args = parse()
+    if not args.full:
+        args.only_timed = True      # a plain run: set-up, warm-up, the timed steps, the outputs, the result line
     if args.only_timed:
         args.no_cpu_baseline = args.no_secondary = args.no_full_parity = args.no_traffic = True
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -695,7 +757,7 @@ def main():
     kg_test.relations = kg_test.relations.to(device)
 
     flt_stats = None
-    if rank == 0 and n_ent <= 2000000:
+    if rank == 0 and n_ent <= 2000000 and not args.only_timed:
         flt_stats = orc.filter_list_stats(heads, tails, rels, kg_test.head_idx.cpu(), kg_test.tail_idx.cpu(),
                                           kg_test.relations.cpu(), n_ent, n_rel)
     shard = None
@@ -707,7 +769,7 @@ def main():
         # ROW-SHARDED entity tables: this rank keeps rows [lo, hi) of every entity-indexed table;
         # relation tables stay replicated; query rows are built by the owner rank and summed over the ranks
         from torchkge_amd import distributed as kd
-        if table_bytes_full <= (1 << 30) and not args.materialize:
+        if table_bytes_full <= (1 << 30) and not args.materialize and not args.only_timed:
             import copy as _copy0
             model_rep = _copy0.deepcopy(model)      # (a replica: the query partition of the same job, measured beside the headline)
         kd.shard_model_(model)
@@ -735,7 +797,7 @@ def main():
     sync()
     first_parts = {'rocm_wakeup_ms_first_gpu_op_of_the_process': round(rocm_wakeup_ms, 2)}
     t0 = time.perf_counter()
-    if not multi:
+    if not multi and not args.only_timed:
         # the library's own first-use work, in parts: its first launch (code object load), the device-side filter index of the
         # full graph, then the evaluation itself (FilterPlans, MFMA self-test, capture or eager launches, ranks to the host)
         from torchkge_amd import _hip as _hipb
@@ -756,13 +818,15 @@ def main():
     ev.evaluate(args.batch, verbose=False)      # (second call: captures the hipGraph)
     sync()
     # ... and the per-step time of a few evaluations after an idle gap, clocks NOT settled (what r01 / early r02 reported)
-    time.sleep(0.5)
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(5):
-        ev.evaluate(args.batch, verbose=False)
-    sync()
-    cold_ms = (time.perf_counter() - t0) / 5 * 1e3
+    cold_ms = None
+    if not args.only_timed:
+        time.sleep(0.5)
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(5):
+            ev.evaluate(args.batch, verbose=False)
+        sync()
+        cold_ms = (time.perf_counter() - t0) / 5 * 1e3
     settle_steps = 0
     if args.settle_ms > 0:
         sync()
@@ -788,6 +852,8 @@ def main():
     elapsed = time.perf_counter() - t0
     # (read HERE: the legs that follow -- the other exchange, the weak mode -- run evaluations of their own on this model)
     level_timed, rescored_timed = int(getattr(model, '_split_level', 0)), getattr(ev, 'last_rescored_per_query', None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ev)
     if multi:
         tt = torch.tensor([elapsed], device=device if args.backend == 'nccl' else 'cpu', dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -839,13 +905,13 @@ def main():
         return out
 
     headline_coll = None
-    if multi and shard == 'entities' and not args.materialize and device.type == 'cuda':
+    if multi and shard == 'entities' and not args.materialize and device.type == 'cuda' and not args.only_timed:
         headline_coll = collective_ms(ev, args.batch, exchange=args.exchange)
 
     # entity shards: the OTHER exchange measured beside the headline one, at the SAME b_size -- the all-gather of the
     # partial score tiles (B, N/P) -> (B, N) that north_star names, vs the all-reduce of rank counts (bit-identical ranks)
     other_x = None
-    if multi and shard == 'entities' and not args.materialize:
+    if multi and shard == 'entities' and not args.materialize and not args.only_timed:
         ox = 'scores' if args.exchange == 'counts' else 'counts'
         ob = args.batch
         ev_o = tk.LinkPredictionEvaluator(model, kg_test, shard=shard, exchange=ox, graph=graph_arg,
@@ -888,7 +954,7 @@ def main():
     # weights), every rank scoring its own shard for all test facts, counts exchange -- per-GPU work fixed as N grows
     weak_mode = None
     if multi and shard == 'entities' and args.scaling == 'strong' and not args.no_weak and not args.materialize \
-            and args.tables == 'sharded':
+            and args.tables == 'sharded' and not args.only_timed:
         from torchkge_amd import distributed as kd
         m_w, _, kg_w, kg_test_w, info_w = build_workload(args.workload, device, kg_kind=args.kg, weights='xavier',
                                                          n_ent_mult=world)
@@ -916,7 +982,7 @@ def main():
     # next to the default cfg2 job (strong scaling, counts exchange, trained-like weights from rank 0)
     cfg4_mode = None
     if multi and shard == 'entities' and args.workload == 'transe_fb15k237' and not args.no_weak and not args.materialize \
-            and args.tables == 'sharded':
+            and args.tables == 'sharded' and not args.only_timed:
         from torchkge_amd import distributed as kd
         m_4, _, kg_4, kg_test_4, info_4 = build_workload('distmult_fb15k', device, kg_kind=args.kg,
                                                          weights=('trained' if rank == 0 else 'xavier'),
@@ -981,28 +1047,56 @@ def main():
         lo_r, hi_r = 0, n_ent
     n_ent = hi_r - lo_r
 
-    # ---- roofline of the dominant kernel (the all-candidates count kernel) ----
-    roof = None
-    if rank == 0 and not args.only_timed:
+    def dominant_problem():
+        """The problem one launch of the dominant kernel solves, built as evaluate() builds its first batch (call inside
+        model.lp_session()): (prob, both, h, t, r, cols); both: prob holds the two sides of the batch as 2B queries."""
         B = min(args.batch, n_test)
         h, t, r = kg_test.head_idx[:B], kg_test.tail_idx[:B], kg_test.relations[:B]
         if getattr(ev, '_perm', None) is not None and B == n_test:    # the order evaluate() processes the facts in
             h, t, r = h[ev._perm], t[ev._perm], r[ev._perm]
+        prob = None
+        both = (shard is None and not args.materialize and ev.both_sides and not args.overlap
+                and hasattr(model, 'lp_problem_both'))
+        cols = None
+        if both:    # as evaluate() builds it: both sides of the batch as one problem of 2B queries -- over the
+            # batch's COLUMNS (distinct query rows) where the evaluator's plan carries a ColumnPlan
+            pl = (getattr(ev, '_plans', None) or {}).get((0, int(h.shape[0])))
+            cols = getattr(pl, 'cols', None)
+            if model._use_level1() and (not (tk.evaluation.DEDUPE_LEVEL1 and getattr(model, 'lp_dedupe_level1', True))
+                                        or model._level1_stream()):
+                cols = None     # (as evaluate() does on the one-product level: Model.lp_dedupe_level1 / the free-running kernel)
+            prob = model.lp_problem(h, t, r, 'both', cols=cols) if cols is not None else model.lp_problem_both(h, t, r)
+        if prob is not None:
+            return prob, True, h, t, r, cols
+        # (row-sharded tables: only rank 0 builds this problem, so the query exchange is skipped --
+        # rows of entities other ranks own stay zero, which does not change the kernel's work)
+        xk = {'exchange': (lambda ts: None)} if getattr(model, '_row_shard', None) is not None else {}
+        return model.lp_problem(h, t, r, 'tail', ent_lo=lo_r, ent_hi=hi_r, **xk), False, h, t, r, cols
+
+    def dtype_of(prob):
+        """The result line's dtype: which prefilter, if any, the dominant kernel runs in front of the exact fp32 recheck."""
+        if prob.split is not None and not args.materialize:
+            return 'f32 (f16 hi/lo-split MFMA prefilter + exact f32 recheck; ranks bit-identical to f32)'
+        if (prob.desc.mode not in (_hip.LP_DOT, _hip.LP_L2_EXPAND, _hip.LP_L2_PROJH, _hip.LP_L2_PROJD)
+                and getattr(prob, 'sad', None) is not None and not args.materialize):
+            return 'f32 (u16 fixed-point SAD prefilter + exact f32 recheck; ranks bit-identical to f32)'
+        return 'f32'
+
+    # ---- roofline of the dominant kernel (the all-candidates count kernel) ----
+    roof, dtype = None, 'f32'
+    if rank == 0 and args.only_timed:       # (a plain run: the dtype from the problem alone, nothing timed)
         guard_on = hasattr(model, 'lp_guard_begin') and model.lp_guard_begin(device) is not None
         with model.lp_session():
-            prob = None
-            both = (shard is None and not args.materialize and ev.both_sides and not args.overlap
-                    and hasattr(model, 'lp_problem_both'))
-            cols = None
-            if both:    # as evaluate() builds it: both sides of the batch as one problem of 2B queries -- over the
-                # batch's COLUMNS (distinct query rows) where the evaluator's plan carries a ColumnPlan
-                pl = (getattr(ev, '_plans', None) or {}).get((0, int(h.shape[0])))
-                cols = getattr(pl, 'cols', None)
-                if model._use_level1() and (not (tk.evaluation.DEDUPE_LEVEL1 and getattr(model, 'lp_dedupe_level1', True))
-                                            or model._level1_stream()):
-                    cols = None     # (as evaluate() does on the one-product level: Model.lp_dedupe_level1 / the free-running kernel)
-                prob = model.lp_problem(h, t, r, 'both', cols=cols) if cols is not None else model.lp_problem_both(h, t, r)
-            if prob is not None:
+            dtype = dtype_of(dominant_problem()[0])
+        if guard_on:
+            model.lp_guard_end()
+    if rank == 0 and not args.only_timed:
+        guard_on = hasattr(model, 'lp_guard_begin') and model.lp_guard_begin(device) is not None
+        with model.lp_session():
+            prob, both, h, t, r, cols = dominant_problem()
+            dtype = dtype_of(prob)
+            B = h.shape[0]
+            if both:
                 true = torch.cat([t, h])
                 if prob.pre is not None:
                     prob.pre['true_idx'] = true
@@ -1010,10 +1104,6 @@ def main():
                 prob.split_true = (s_true, true)    # (as the evaluator: the sweep does not list the pairs whose score IS the threshold)
                 B = 2 * B
             else:
-                # (row-sharded tables: only rank 0 runs this timing leg, so the query exchange is skipped --
-                # rows of entities other ranks own stay zero, which does not change the kernel's work)
-                xk = {'exchange': (lambda ts: None)} if getattr(model, '_row_shard', None) is not None else {}
-                prob = model.lp_problem(h, t, r, 'tail', ent_lo=lo_r, ent_hi=hi_r, **xk)
                 s_true = prob.pair_scores(t)
             raw = torch.zeros(B, dtype=torch.int32, device=device)
             scores_buf = torch.empty(B, n_ent, device=device) if args.materialize else None
@@ -1449,16 +1539,13 @@ def main():
                 else 'all-to-all of the partial (2B, N/P) score tiles: each rank receives and ranks the rows of its 2B/P queries')
         else:
             par = 'query-shards-%d' % world
-        used_split = bool(roof and 'executed_frac' in roof)
-        dtype = 'f32 (f16 hi/lo-split MFMA prefilter + exact f32 recheck; ranks bit-identical to f32)' \
-            if used_split else ('f32 (u16 fixed-point SAD prefilter + exact f32 recheck; ranks bit-identical to f32)'
-                                if roof and 'lp_l1_sad' in roof.get('kernel', '') else 'f32')
         line = {
             'metric': 'link-prediction triples scored/sec (filtered LP eval, both sides)',
             'value': round(value, 1), 'unit': 'triples_scored/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
             'clock_settle': {'untimed_steps_before_warmup': settle_steps, 'target_ms': args.settle_ms},
-            'first_evaluate_ms': round(first_ms, 2), 'first_evaluate_parts': first_parts, 'cold_ms_per_step': round(cold_ms, 4),
+            'first_evaluate_ms': round(first_ms, 2), 'first_evaluate_parts': first_parts if not args.only_timed else None,
+            'cold_ms_per_step': None if cold_ms is None else round(cold_ms, 4),
             'first_evaluate_what': 'wall time of the first evaluate() of a fresh evaluator: device-side filter index, FilterPlans, '
                                    'MFMA self-test, eager launches, ranks to the host; cold_ms_per_step: 5 graph replays after a '
                                    '0.5 s idle gap, before the clock-settle phase',

@@ -6,7 +6,7 @@
 A=$1; B=$2; ROUNDS=${3:-2}
 shift 3 2>/dev/null
 [ "$1" == "--" ] && shift
-CMD=${*:-python bench.py --no-cpu-baseline --no-secondary --steps 30}
+CMD=${*:-python bench.py --full --no-cpu-baseline --no-secondary --steps 30}
 LIB=torchkge_amd/csrc/libkge_hip.so
 for r in $(seq 1 $ROUNDS); do
   for v in "$A" "$B"; do

@@ -22,12 +22,12 @@ m=d.get('strong_scaling_model') or {}; print('   strong_scaling_model: entity sh
 print('   collectives_fallback:', (d.get('collectives_fallback') or '')[:80])
 "; }
 echo "== python bench.py --gpus 2 --backend gloo   (default: strong scaling of the cfg2 job over entity shards, counts all-reduce; score all-to-all, query partition, weak mode and cfg4 beside it)"
-timeout 900 python bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
+timeout 900 python bench.py --gpus 2 --backend gloo --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
 echo "== python bench.py --gpus 2 --backend gloo --shard queries"
-timeout 600 python bench.py --gpus 2 --backend gloo --shard queries --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
+timeout 600 python bench.py --gpus 2 --backend gloo --shard queries --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
 echo "== KGE_EAGER_COLLECTIVES=1 python bench.py --gpus 2 --backend gloo --no-weak"
-KGE_EAGER_COLLECTIVES=1 timeout 600 python bench.py --gpus 2 --backend gloo --no-weak --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
+KGE_EAGER_COLLECTIVES=1 timeout 600 python bench.py --gpus 2 --backend gloo --no-weak --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
 echo "== one RCCL rank, collectives forced (KGE_FORCE_COLLECTIVES=1, torch.distributed.run --nproc-per-node 1)"
-HSA_ENABLE_IPC_MODE_LEGACY=0 KGE_FORCE_COLLECTIVES=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 2 --no-weak --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
+HSA_ENABLE_IPC_MODE_LEGACY=0 KGE_FORCE_COLLECTIVES=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --full --steps 5 --warmup 2 --no-weak --no-cpu-baseline --no-secondary 2>/tmp/dry.err | tail -1 | show
 echo "== BASELINE cfg5 sharded: two gloo ranks on one GPU, each HOLDING half of the 4.59 M entity rows, trained-like tables"
 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 tools/sharded_shapes.py --workload complex_wikidata5m --weights trained --evals 3 --score-facts 64 --batch 8192 --out gpurun_out/r06/sharded_complex_wikidata5m.json 2>/tmp/dry.err | tail -1 | cut -c1-1800

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kprof
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kprof -o k -- python $R/bench.py --no-cpu-baseline "$@" > /tmp/kprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kprof -o k -- python $R/bench.py --full --no-cpu-baseline "$@" > /tmp/kprof.log 2>&1
 tail -1 /tmp/kprof.log | cut -c1-200
 f=$(find /tmp/kprof -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY'

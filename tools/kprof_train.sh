@@ -2,7 +2,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kprof
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kprof -o k -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-full-parity --weights xavier > /tmp/kprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kprof -o k -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-full-parity --weights xavier > /tmp/kprof.log 2>&1
 f=$(find /tmp/kprof -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

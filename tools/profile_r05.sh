@@ -7,19 +7,19 @@ OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 T="--no-cpu-baseline"
-b() { name=$1; shift; timeout 600 python $R/bench.py "$@" 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; [ -s $OUT/bench_$name.json ] && rm -f $OUT/$name.err; }
+b() { name=$1; shift; timeout 600 python $R/bench.py --full "$@" 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; [ -s $OUT/bench_$name.json ] && rm -f $OUT/$name.err; }
 tl() { name=$1; shift; cd $R; timeout 400 bash tools/eval_timeline.sh gpurun_out/profiles_$TAG/timeline_$name.txt "$@" > /dev/null 2>&1; cd /tmp; }
 tr() { name=$1; shift; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$name -o bench -- python $R/bench.py --only-timed "$@" > $OUT/trace_$name.log 2>&1; }
 # the headline line exactly as the driver runs it, then the other BASELINE workloads and the A/B variants on the same box
 b transe_fb15k237 --steps 20 --warmup 3
-KGE_HI_STREAM=0 timeout 400 python $R/bench.py --steps 20 --warmup 3 $T --no-secondary --no-full-parity 2>/dev/null | tail -1 > $OUT/bench_transe_fb15k237_r04_level1_kernel.json
+KGE_HI_STREAM=0 timeout 400 python $R/bench.py --full --steps 20 --warmup 3 $T --no-secondary --no-full-parity 2>/dev/null | tail -1 > $OUT/bench_transe_fb15k237_r04_level1_kernel.json
 b transe_fb15k237_three_products --steps 20 --warmup 3 --split-level 0 $T --no-secondary
 b complex_wn18rr --steps 10 --warmup 3 --workload complex_wn18rr $T
 b distmult_fb15k --steps 5 --warmup 2 --workload distmult_fb15k $T
 b transh_fb15k237 --steps 5 --warmup 2 --workload transh_fb15k237 $T
 b transd_fb15k237 --steps 5 --warmup 2 --workload transd_fb15k237 $T
 for w in complex_wn18rr distmult_fb15k transh_fb15k237; do
-  KGE_HI_STREAM=0 timeout 400 python $R/bench.py --steps 5 --warmup 2 --workload $w $T --no-secondary --no-full-parity --no-traffic 2>/dev/null | tail -1 | python3 -c "
+  KGE_HI_STREAM=0 timeout 400 python $R/bench.py --full --steps 5 --warmup 2 --workload $w $T --no-secondary --no-full-parity --no-traffic 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$w r04 level-1 kernel (KGE_HI_STREAM=0), same box:', d['ms_per_step'], 'ms per evaluate; count kernel', d['roofline']['kernel_ms'], 'ms')" >> $OUT/level1_kernel_ab.txt
 done

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export KGE_BENCH_TABLE_CACHE=/tmp/kge_cache
 T="--no-cpu-baseline"
-b() { name=$1; shift; timeout 1500 python $R/bench.py "$@" 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; [ -s $OUT/bench_$name.json ] && rm -f $OUT/$name.err; }
+b() { name=$1; shift; timeout 1500 python $R/bench.py --full "$@" 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; [ -s $OUT/bench_$name.json ] && rm -f $OUT/$name.err; }
 tl() { name=$1; shift; cd $R; timeout 600 bash tools/eval_timeline.sh gpurun_out/profiles_$TAG/timeline_$name.txt "$@" > /dev/null 2>&1; cd /tmp; }
 ks() {  # evaluate-only kernel statistics: the bench's timed loop under rocprofv3 --kernel-trace --stats, tables from the cache
   name=$1; shift; rm -rf /tmp/ks_$name

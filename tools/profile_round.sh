@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 Q="--no-cpu-baseline --no-full-parity --no-traffic"
 P="--no-cpu-baseline --no-traffic"          # (full-split parity ON: every workload's parity_full_split is recorded)
 T="--no-cpu-baseline"                       # (... and the run's own PMC passes: traffic, SQ_INSTS_MFMA, MFMA busy)
-b() { name=$1; shift; timeout 600 python $R/bench.py "$@" 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; [ -s $OUT/bench_$name.json ] && rm -f $OUT/$name.err; }
+b() { name=$1; shift; timeout 600 python $R/bench.py --full "$@" 2>$OUT/$name.err | tail -1 > $OUT/bench_$name.json; [ -s $OUT/bench_$name.json ] && rm -f $OUT/$name.err; }
 tr() { name=$1; shift; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$name -o bench -- python $R/bench.py --only-timed "$@" > $OUT/trace_$name.log 2>&1; }
 finish() {
   cd $R
@@ -42,14 +42,14 @@ b transd_fb15k237 --steps 5 --warmup 2 --workload transd_fb15k237 $T
 b transe_l1_fb15k237 --steps 5 --warmup 2 --workload transe_l1_fb15k237 $P
 b transe_fb15k237_l2direct --steps 10 --warmup 3 --l2-mode direct $Q
 b transe_fb15k237_materialized --steps 10 --warmup 3 --materialize $Q
-KGE_DEDUPE_QUERIES=0 timeout 400 python $R/bench.py --steps 20 --warmup 5 $Q --no-secondary 2>/dev/null | tail -1 > $OUT/bench_transe_fb15k237_no_query_columns.json
+KGE_DEDUPE_QUERIES=0 timeout 400 python $R/bench.py --full --steps 20 --warmup 5 $Q --no-secondary 2>/dev/null | tail -1 > $OUT/bench_transe_fb15k237_no_query_columns.json
 # cfg5 (ComplEx d=512, Wikidata5M shape, 18.8 GB of tables on one GPU): subsample parity + CPU sample + traffic inside
-timeout 1500 python $R/bench.py --workload complex_wikidata5m --no-secondary --batch 8192 --kg uniform --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_complex_wikidata5m.json
+timeout 1500 python $R/bench.py --full --workload complex_wikidata5m --no-secondary --batch 8192 --kg uniform --steps 3 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_complex_wikidata5m.json
 # tiled top-k inference at cfg2 and cfg5 shapes; the first evaluate() of a process
 timeout 600 python $R/tools/topk_time.py --cfg5 2>/dev/null | grep "^{" > $OUT/topk_inference.jsonl
 timeout 300 python $R/tools/first_call.py 2>/dev/null | tail -1 > $OUT/first_call.json
 # per-kernel time of the bench command (the trained-weights set-up shows up as the score_fwd/bwd, key_* and optimiser rows)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $R/bench.py --steps 20 --warmup 5 $Q > $OUT/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $R/bench.py --full --steps 20 --warmup 5 $Q > $OUT/trace.log 2>&1
 # ... and of the timed loops alone (no roofline / f32 legs): what one evaluate() consists of, per workload
 tr eval --steps 20 --warmup 5
 tr eval_three_products --steps 20 --warmup 5 --split-level 0
