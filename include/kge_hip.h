@@ -49,6 +49,10 @@
  *                                  sampling.py:313-325 and :206-221 (the integer scatter)
  *   kge_gather_rows              nn.Embedding lookups of the above
  *   kge_normalize_rows           Model.normalize_parameters (translation.py:83-90 etc.)
+ *   kge_bilinear_query           RESCAL / HolE inference_scoring_function on entity candidates: the query row h.M_r /
+ *                                  M_r.t (bilinear.py:98-114, :365-381) that a KGE_LP_DOT problem then scores
+ *   kge_bilinear_relation_rows   RESCAL / HolE relation candidates (bilinear.py:115-121, :382-389)
+ *   kge_rescal_rel_grad          autograd of RESCAL's scoring_function wrt rel_mat (bilinear.py:60-71)
  */
 #ifndef KGE_HIP_H
 #define KGE_HIP_H
@@ -72,7 +76,9 @@ enum {
     KGE_TRANSH = 2,
     KGE_TRANSD = 3,
     KGE_DISTMULT = 4,
-    KGE_COMPLEX = 5
+    KGE_COMPLEX = 5,
+    KGE_RESCAL = 6,     /* ABI 33: tables {E, rel_mat}, d_ent = d, d_rel = d * d (M_r = rel_mat[r] viewed (d, d)) */
+    KGE_HOLE = 7        /* ABI 33: tables {E, R}, d_ent = d_rel = d (B_r = the rolling matrix of R[r]) */
 };
 
 /* which entity is replaced by the candidates */
@@ -153,9 +159,13 @@ typedef struct kge_lp_desc {
 } kge_lp_desc;
 
 /* ---- K1: fused gather + normalise + score (scoring_function) ------------- */
-/* tables: TransE/DistMult {E,R}; TransH {E,R,W}; TransD {E,R,Ep,Rp}; ComplEx {Ere,Eim,Rre,Rim}.
+/* tables: TransE/DistMult {E,R}; TransH {E,R,W}; TransD {E,R,Ep,Rp}; ComplEx {Ere,Eim,Rre,Rim};
+ * RESCAL {E,rel_mat}; HolE {E,R}.
  * d_ent = row length of entity tables, d_rel = row length of relation tables
- * (equal except TransD, which needs d_ent >= d_rel).  Tables are contiguous. */
+ * (equal except TransD, which needs d_ent >= d_rel, and RESCAL, d_rel = d_ent^2).  Tables are contiguous.
+ * RESCAL / HolE (ABI 33, bilinear.py:60-71, :311-323): score = h^ . B_r . t^ with B_r = M_r = rel_mat[r] viewed (d, d)
+ * (M[i][j] = row[i*d + j]) or the rolling matrix B_r[i][j] = R[r][(j - i) mod d]; u_j = chain_k h^_k B_r[k][j],
+ * score = chain_j u_j t^_j (lanes over j, summed by a wavefront reduction); 1 <= d_ent <= 512. */
 int kge_score_triples(int kind, const float *t0, const float *t1, const float *t2, const float *t3,
                       int d_ent, int d_rel, const int64_t *h, const int64_t *t, const int64_t *r,
                       int64_t B, float *out, kge_stream_t stream);
@@ -168,7 +178,11 @@ int kge_score_triples(int kind, const float *t0, const float *t1, const float *t
  *     TransE / DistMult: 0 (g0,h) 1 (g0,t) 2 (g1,r)        TransH: 0 (g0,h) 1 (g0,t) 2 (g1,r) 3 (g2,r)
  *     ComplEx: 0 (g0,h) 1 (g0,t) 2 (g1,h) 3 (g1,t) 4 (g2,r) 5 (g3,r)
  *     TransD:  0 (g0,h) 1 (g0,t) 2 (g2,h) 3 (g2,t) 4 (g1,r) 5 (g3,r)
- *   and the caller reduces them per target table with kge_segment_sum_rows. */
+ *     HolE:    0 (g0,h) 1 (g0,t) 2 (g1,r)
+ *     RESCAL:  0 (g0,h) 1 (g0,t), and the operands of kge_rescal_rel_grad: 2 U_i = go_i h^_i, 3 V_i = t^_i
+ *   and the caller reduces them per target table with kge_segment_sum_rows.
+ * RESCAL needs the row mode (rows != NULL, g0..g3 unused): its rel_mat gradient is d^2 wide per triple and is never
+ * scattered per triple; kge_rescal_rel_grad reduces it per relation. */
 int kge_score_triples_bwd(int kind, const float *t0, const float *t1, const float *t2,
                           const float *t3, int d_ent, int d_rel, const int64_t *h,
                           const int64_t *t, const int64_t *r, int64_t B, const float *go,
@@ -236,6 +250,38 @@ int kge_lp_prep_hi(int kind, int side, const float *t0, const float *t1, const f
 int kge_relation_scores_proj(int kind, const float *E, const float *R, const float *Wt, const float *Ep,
                              int d_ent, int d_rel, const int64_t *h, const int64_t *t, int64_t B,
                              int64_t n_rel, float *out, int64_t ldo, kge_stream_t stream);
+
+/* ---- RESCAL / HolE (ABI 33, bilinear_xform.hip) ---------------------------- */
+/* Query rows of the bilinear models with a d x d relation operator B_r (RESCAL: M_r = Rt[r] viewed (d, d); HolE: the
+ * rolling matrix B_r[i][j] = Rt[r][(j - i) mod d], generated in LDS from the d floats of Rt[r]):
+ *   tail side  Q[i][j] = chain_k X[h_i][k] * B_r[k][j]       (q = h . M_r; HolE q_j = sum_k h_k r[(j - k) mod d])
+ *   head side  Q[i][j] = chain_k X[t_i][k] * B_r[j][k]       (q = M_r . t; HolE q_j = sum_k r[(k - j) mod d] t_k)
+ * with r = r_i, k ascending (one fmaf chain per output): a row depends on (entity, relation, side) only.  The all-
+ * candidates score is then KGE_LP_DOT of Q against the entity table (replaces bilinear.py:98-114, :365-381).
+ * side KGE_SIDE_TAIL / _HEAD: B rows; KGE_SIDE_BOTH: 2B rows, [0, B) tail side, [B, 2B) head side.
+ * perm (optional, NULL: natural order): the output rows in relation order -- kge_key_sort of [r] (or [r | r] for
+ * KGE_SIDE_BOTH); every 64 consecutive rows of that order share each staged tile of B_r, which is then read once per
+ * group instead of once per row.  The values do not depend on perm.
+ * ent_n >= 0: X holds only the entity rows [ent_lo, ent_lo + ent_n) (row-sharded, as kge_lp_prep_sharded): rows of
+ * entities outside it are written as zeros.  ent_n < 0: whole table, ent_lo ignored (pass 0).
+ * ldr >= d*d (RESCAL) / d (HolE); 1 <= d <= 512; Q is (rows, ldq >= d). */
+int kge_bilinear_query(int kind, int side, const float *X, int64_t ldx, const float *Rt, int64_t ldr, int d,
+                       const int64_t *h, const int64_t *t, const int64_t *r, int64_t B, int64_t ent_lo,
+                       int64_t ent_n, const int64_t *perm, float *Q, int64_t ldq, kge_stream_t stream);
+/* Relation candidates (relation prediction, `entities=False`; bilinear.py:115-121, :382-389): the row that a KGE_LP_DOT
+ * against the relation table turns into the score of every relation rho,
+ *   RESCAL  out[i][a*d + b] = H[i][a] * T[i][b]                 (vec(h t^T) . rel_mat[rho] = h . M_rho . t)
+ *   HolE    out[i][k] = chain_j H[i][j] * T[i][(j + k) mod d]   (c_i . R[rho] = h . Roll(R[rho]) . t)
+ * No (b, n_rel, d) or (b, n_rel, d, d) tensor exists.  ldo >= d*d (RESCAL) / d (HolE). */
+int kge_bilinear_relation_rows(int kind, const float *H, int64_t ldh, const float *T, int64_t ldt, int64_t B, int d,
+                               float *out, int64_t ldo, kge_stream_t stream);
+/* Gradient of RESCAL's scoring_function wrt rel_mat (bilinear.py:60-71 through autograd), reduced per relation:
+ *   gM[rho*ldg + a*d + b] = chain over the triples i of rho, in the order of perm, of U[i][a] * V[i][b]
+ * with U / V the row streams 2 / 3 of kge_score_triples_bwd (U_i = go_i h^_i, V_i = t^_i) and perm = kge_key_sort of r
+ * (B entries, ascending relation).  Every (relation, 64 x 64 tile) is one block that WRITES its outputs (relations
+ * without triples get zeros): no atomics, no B x d^2 scratch, the same bits on every run. */
+int kge_rescal_rel_grad(const float *U, const float *V, int64_t ld, int d, const int64_t *r, const int64_t *perm,
+                        int64_t B, int64_t n_rel, float *gM, int64_t ldg, kge_stream_t stream);
 
 /* Per-query scalars of the projection modes (KGE_LP_L2_PROJH / _PROJD) in ONE launch: qn[i] = ||Q[i]||^2 and
  * pz[i] = (scale * (Q[i] . W[r_idx[i]]), ||W[r_idx[i]]||^2 + z_add) -- kge_lp_desc.Wq of those modes (TransH: scale 2,

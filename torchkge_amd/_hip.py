@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libkge_hip.so')
 
 # enums of include/kge_hip.h
-TRANSE_L1, TRANSE_L2, TRANSH, TRANSD, DISTMULT, COMPLEX = range(6)
+TRANSE_L1, TRANSE_L2, TRANSH, TRANSD, DISTMULT, COMPLEX, RESCAL, HOLE = range(8)
 SIDE_TAIL, SIDE_HEAD, SIDE_PROJ_H, SIDE_PROJ_T, SIDE_BOTH = range(5)
 EW_ADD, EW_SUB, EW_MUL, EW_MULSUB, EW_MULADD = range(5)
 LP_DOT, LP_L2_EXPAND, LP_L1_DIRECT, LP_L2_DIRECT, LP_L2_PROJH, LP_L2_PROJD = range(6)
@@ -141,6 +141,9 @@ _SIGNATURES = {
     'kge_column_plan_build': [_vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _i64, _vp],
     'kge_column_plan_emit': [_i64, _i64, _i64, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     'kge_topk': [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp],
+    'kge_bilinear_query': [_int, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
+    'kge_bilinear_relation_rows': [_int, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp],
+    'kge_rescal_rel_grad': [_vp, _vp, _i64, _int, _vp, _vp, _i64, _i64, _vp, _i64, _vp],
 }
 # every symbol include/kge_hip.h declares
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['kge_corrupt_ws_elems', 'kge_abi_version', 'kge_lp_split_rows_padded',
@@ -150,7 +153,7 @@ EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['kge_corrupt_ws_elems', 'kge_abi_
                                                'kge_column_plan_ws_bytes'])
 
 _lib = None
-ABI_VERSION = 32        # kge_abi_version() of the library this binding was written against
+ABI_VERSION = 33        # kge_abi_version() of the library this binding was written against
 
 
 def load_library():
@@ -276,6 +279,9 @@ _BWD_STREAMS = {
     TRANSH: [(0, 0, 2, 'ht'), (1, 2, 1, 'r'), (2, 3, 1, 'r')],
     COMPLEX: [(0, 0, 2, 'ht'), (1, 2, 2, 'ht'), (2, 4, 1, 'r'), (3, 5, 1, 'r')],
     TRANSD: [(0, 0, 2, 'ht'), (2, 2, 2, 'ht'), (1, 4, 1, 'r'), (3, 5, 1, 'r')],
+    HOLE: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
+    # rel_mat's gradient (d^2 per triple) is reduced per relation from streams 2 / 3 (kge_rescal_rel_grad)
+    RESCAL: [(0, 0, 2, 'ht')],
 }
 BWD_SORTED_MIN_BATCH = 2048     # below this the plain atomic scatter is as fast
 
@@ -313,6 +319,8 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
     go = f32c(grad_out)
     B = h.shape[0]
     dev = h.device
+    if kind == RESCAL:
+        return _rescal_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
     if B < BWD_SORTED_MIN_BATCH:
         with _on(dev):
             _check(lib.kge_score_triples_bwd(kind, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
@@ -360,6 +368,81 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
     return [g if n else None for g, n in zip(grads[:len(tables)], needs)]
 
 
+def _key_perm(k0, k1, n_keys):
+    """kge_key_sort of [k0 | k1] (k1 may be None): stable ascending order of the ids < n_keys.  Workspace sizes are
+    cached per shape (the size query walks rocPRIM's host-side configuration); nothing here synchronises the host, so it
+    runs inside a graph capture."""
+    lib = load_library()
+    n0, n1 = k0.shape[0], (0 if k1 is None else k1.shape[0])
+    bits = max(1, int(n_keys - 1).bit_length())
+    nb = _KEY_SORT_WS.get((n0 + n1, bits))
+    if nb is None:
+        nb = _KEY_SORT_WS[(n0 + n1, bits)] = int(lib.kge_key_sort_ws_bytes(n0 + n1, bits))
+    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=k0.device)
+    perm = torch.empty(n0 + n1, dtype=torch.int64, device=k0.device)
+    if n0 + n1 > 0:
+        _check(lib.kge_key_sort(_p(k0), n0, _p(k1), n1, bits, _p(perm), _p(ws), nb, _stream()), 'kge_key_sort')
+    return perm
+
+
+def _rescal_bwd(tabs, d, d_rel, h, t, r, go, grads, needs):
+    """RESCAL's backward: entity gradients through the row mode + kge_segment_sum_rows, rel_mat's by the relation-grouped
+    reduction kge_rescal_rel_grad (sorted by relation: no atomics on rel_mat, the same bits on every run)."""
+    lib = load_library()
+    B, dev = h.shape[0], h.device
+    rows = torch.empty(4 * B * d, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _check(lib.kge_score_triples_bwd(RESCAL, _p(tabs[0]), _p(tabs[1]), None, None, d, d_rel, _p(h), _p(t), _p(r), B,
+                                         _p(go), None, None, None, None, _p(rows), d, _stream()), 'kge_score_triples_bwd')
+        if needs[0]:
+            g = grads[0]
+            perm = _key_perm(h, t, g.shape[0])
+            _check(lib.kge_segment_sum_rows(_p(rows), d, d, _p(h), B, _p(t), B, _p(perm), _p(g), g.stride(0), _stream()),
+                   'kge_segment_sum_rows')
+        if needs[1]:
+            g = grads[1]
+            perm = _key_perm(r, None, g.shape[0])
+            _check(lib.kge_rescal_rel_grad(rows.data_ptr() + 2 * B * d * 4, rows.data_ptr() + 3 * B * d * 4, d, d, _p(r),
+                                           _p(perm), B, g.shape[0], _p(g), g.stride(0), _stream()), 'kge_rescal_rel_grad')
+    return [g if n else None for g, n in zip(grads[:2], needs)]
+
+
+def bilinear_query(kind, side, X, Rt, h, t, r, ent_lo=0, ent_n=-1, sort=True):
+    """kge_bilinear_query: the (B, d) -- side 'both': (2B, d) -- query rows of RESCAL / HolE, x . B_r (tail side) or
+    x . B_r^T (head side), rows taken from X by h / t.  sort: order the rows by relation first (kge_key_sort of [r] or
+    [r | r]) so that every staged tile of B_r serves a group of rows; the values do not depend on it."""
+    lib = load_library()
+    require_cuda(X, Rt, h, t, r)
+    X, Rt = f32c(X), f32c(Rt)
+    h, t, r = i64c(h), i64c(t), i64c(r)
+    d = X.shape[1]
+    B = r.shape[0]
+    rows = 2 * B if side == SIDE_BOTH else B
+    Q = torch.empty(rows, d, dtype=torch.float32, device=X.device)
+    if rows == 0:
+        return Q
+    with _on(X.device):
+        perm = _key_perm(r, r if side == SIDE_BOTH else None, max(Rt.shape[0], 1)) if sort else None
+        _check(lib.kge_bilinear_query(kind, side, _p(X), X.stride(0), _p(Rt), Rt.stride(0), d, _p(h), _p(t), _p(r), B,
+                                      ent_lo, ent_n, _p(perm), _p(Q), Q.stride(0), _stream()), 'kge_bilinear_query')
+    return Q
+
+
+def bilinear_relation_rows(kind, H, T):
+    """kge_bilinear_relation_rows: the (B, d*d) rows vec(h t^T) (RESCAL) or (B, d) rows c_k = sum_j h_j t_(j+k) mod d
+    (HolE) whose KGE_LP_DOT against the relation table scores every relation."""
+    lib = load_library()
+    require_cuda(H, T)
+    H, T = f32c(H), f32c(T)
+    B, d = H.shape
+    out = torch.empty(B, d * d if kind == RESCAL else d, dtype=torch.float32, device=H.device)
+    if B:
+        with _on(H.device):
+            _check(lib.kge_bilinear_relation_rows(kind, _p(H), H.stride(0), _p(T), T.stride(0), B, d, _p(out),
+                                                  out.stride(0), _stream()), 'kge_bilinear_relation_rows')
+    return out
+
+
 def side_code(side):
     """'tail' / 'head' / 'both' (both sides of a batch as one 2B-query problem, tail side first)."""
     return {'tail': SIDE_TAIL, 'head': SIDE_HEAD, 'both': SIDE_BOTH}[side]
@@ -371,6 +454,10 @@ def lp_prep(kind, side, tables, d_ent, d_rel, h, t, r, want_qn=False, want_w=Fal
     rows of entities this shard does not own come back as zeros, to be summed over the shards).
     want_hi (TransH / TransD, unsharded or replica tables): the same launch also writes the planar f16 hi operand of the
     query rows and their residuals (kge_lp_prep_hi); returns (Q0, Q1, qn, Wq, Qh, q_dn2)."""
+    if kind in (RESCAL, HOLE):      # query rows only (the DOT modes need no qn / Wq); rows by relation group
+        assert not (want_qn or want_w or want_q1 or want_hi)
+        return bilinear_query(kind, side, tables[0], tables[1], h, t, r, ent_lo=ent_lo if ent_n >= 0 else 0,
+                              ent_n=ent_n), None, None, None
     lib = load_library()
     require_cuda(h, t, r, *tables)
     tabs = [f32c(x) for x in tables] + [None] * (4 - len(tables))

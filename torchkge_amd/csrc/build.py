@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfma.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip',
-           'lp_l1_sad.hip', 'rank_filter.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip']
+           'lp_l1_sad.hip', 'rank_filter.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip']
 HEADERS = ['kge_common.h', os.path.join('..', '..', 'include', 'kge_hip.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
@@ -41,8 +41,10 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=o
 # (tests/test_host_logic.py::test_mfma_kernels_hold_no_lane_crossing_packed_f32_operand checks the built ISA).  The sources
 # refuse to compile without the flag (KGE_BUILD_NO_SLP).
 _NO_SLP = ['-fno-slp-vectorize', '-DKGE_BUILD_NO_SLP=1']
+# bilinear_xform.hip (RESCAL / HolE query transform, fmaf chains): no packed f32 either -- the same lane-crossing
+# op_sel form would be the vectoriser's to emit there (tests/test_rescal_hole_host.py checks its ISA)
 EXTRA_FLAGS = {'lp_direct.hip': ['-fno-slp-vectorize'], 'lp_hi_stream.hip': _NO_SLP, 'lp_hi_chunk.hip': _NO_SLP,
-               'lp_split_mfma.hip': _NO_SLP}
+               'lp_split_mfma.hip': _NO_SLP, 'bilinear_xform.hip': ['-fno-slp-vectorize']}
 
 
 def _hipcc():

@@ -18,6 +18,13 @@
 
 static inline hipStream_t kge_s(kge_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// KGE_RESCAL / KGE_HOLE behind kge_score_triples / kge_score_triples_bwd (bilinear_xform.hip)
+int kge_bilinear_score_fwd(int kind, const float *t0, const float *t1, int d_ent, int d_rel, const int64_t *h,
+                           const int64_t *t, const int64_t *r, int64_t B, float *out, hipStream_t s);
+int kge_bilinear_score_bwd(int kind, const float *t0, const float *t1, int d_ent, int d_rel, const int64_t *h,
+                           const int64_t *t, const int64_t *r, int64_t B, const float *go, float *g0, float *g1,
+                           float *rows, int64_t rows_ld, hipStream_t s);
+
 static inline bool kge_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Running maximum in a device scalar (non-negative floats compared as bit patterns).  Same-address atomics

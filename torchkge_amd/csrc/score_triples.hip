@@ -629,6 +629,8 @@ extern "C" int kge_score_triples(int kind, const float *t0, const float *t1, con
                                  const int64_t *t, const int64_t *r, int64_t B, float *out,
                                  kge_stream_t stream)
 {
+    if (kind == KGE_RESCAL || kind == KGE_HOLE)
+        return kge_bilinear_score_fwd(kind, t0, t1, d_ent, d_rel, h, t, r, B, out, kge_s(stream));
     int rc = check_common(kind, t0, t1, t2, t3, d_ent, d_rel, h, t, r, B);
     if (rc) return rc;
     if (B == 0) return 0;
@@ -666,6 +668,8 @@ extern "C" int kge_score_triples_bwd(int kind, const float *t0, const float *t1,
                                      float *g0, float *g1, float *g2, float *g3, float *rows, int64_t rows_ld,
                                      kge_stream_t stream)
 {
+    if (kind == KGE_RESCAL || kind == KGE_HOLE)
+        return kge_bilinear_score_bwd(kind, t0, t1, d_ent, d_rel, h, t, r, B, go, g0, g1, rows, rows_ld, kge_s(stream));
     int rc = check_common(kind, t0, t1, t2, t3, d_ent, d_rel, h, t, r, B);
     if (rc) return rc;
     if (B == 0) return 0;

@@ -1,8 +1,9 @@
 # -*- coding: utf-8 -*-
-"""DistMult / ComplEx with the reference's constructors, attributes and
-state_dict keys (torchkge/models/bilinear.py:146-267, :414-556) on the HIP
-engine: the all-candidates score matrix is one fp32 MFMA GEMM
-S = Q . E^T (ComplEx: K = 2d over the [Re | Im] tables, no concatenation)."""
+"""DistMult / ComplEx / RESCAL / HolE with the reference's constructors, attributes
+and state_dict keys (torchkge/models/bilinear.py:14-143, :146-267, :270-411,
+:414-556) on the HIP engine: the all-candidates score matrix is one fp32 MFMA
+GEMM S = Q . E^T (ComplEx: K = 2d over the [Re | Im] tables, no concatenation;
+RESCAL / HolE: Q = the relation-transformed query rows, kge_bilinear_query)."""
 import torch
 
 from .. import _hip
@@ -178,3 +179,186 @@ class ComplExModel(BilinearModel):
                                       c_base=ent_lo)
         prob.cols = cols if (sd == _hip.SIDE_BOTH and prob.split is not None) else None
         return prob
+
+
+class RelationOperators(object):
+    """Light handle standing for the reference's (b, d, d) ``r_mat`` of RESCAL / HolE
+    ``inference_prepare_candidates`` (bilinear.py:135, :398): the relation operator of each query, named by
+    index instead of gathering b * d * d floats; ``materialize()`` gives the tensor itself."""
+
+    def __init__(self, model, r_idx):
+        self.model, self.r_idx = model, r_idx
+        d = model.emb_dim
+        self.shape = (r_idx.shape[0], d, d)
+
+    def dim(self):
+        return 3
+
+    def materialize(self):
+        return self.model._operators(self.r_idx)
+
+
+class RelationOperatorTable(object):
+    """Light handle standing for the reference's (b, n_rel, d, d) relation candidates of RESCAL / HolE
+    (bilinear.py:137-140, :403-407: the operator of every relation, expanded over the batch);
+    ``materialize()`` gives that stride-0 view."""
+
+    def __init__(self, model, b_size):
+        self.model = model
+        d = model.emb_dim
+        self.shape = (b_size, model.n_rel, d, d)
+
+    def dim(self):
+        return 4
+
+    def materialize(self):
+        m = self.model
+        ops = m._operators(torch.arange(m.n_rel, device=m._tables()[1].device))
+        return ops.view(1, *self.shape[1:]).expand(*self.shape)
+
+
+def _ndim(x):
+    return x.dim()
+
+
+class _OperatorModel(BilinearModel):
+    """Bilinear models whose relation is a d x d operator B_r: score = h . B_r . t (RESCAL: B_r = M_r, HolE: the
+    rolling matrix of r).  The query rows h . B_r / B_r . t come from the relation-grouped transform
+    (kge_bilinear_query); from there on every path is DistMult's KGE_LP_DOT against the entity table."""
+
+    _ENT_TABLES = ('ent_emb',)
+
+    def _tables(self):
+        return [self.ent_emb.weight, self._rel_param().weight]
+
+    def _lp_width(self):
+        return self.emb_dim
+
+    def normalize_parameters(self):
+        """L2-normalise entity embeddings (bilinear.py:73-80, :342-349)."""
+        self._normalize_weight_(self.ent_emb)
+
+    def _queries(self, x, r, side):
+        """(b, d) query rows x . B_r (side tail) or x . B_r^T (side head) for the rows ``x``; ``r`` is a
+        RelationOperators handle or a real (b, d, d) tensor of operators."""
+        b = x.shape[0]
+        idx = torch.arange(b, device=x.device)
+        sd = _hip.side_code(side)
+        if isinstance(r, RelationOperators):
+            return _hip.bilinear_query(self._kind, sd, x, _hip.f32c(self._rel_param().weight.data), idx, idx, r.r_idx)
+        d = self.emb_dim
+        one = r.shape[0] == 1 or r.stride(0) == 0        # one operator broadcast over the batch
+        ops = r[:1].reshape(1, d * d) if one else r.reshape(b, d * d)
+        return _hip.bilinear_query(_hip.RESCAL, sd, x, _hip.f32c(ops), idx, idx, torch.zeros_like(idx) if one else idx)
+
+    def _relation_scores(self, h, t, cand):
+        """(b, n_rel) scores of every relation: RESCAL vec(h t^T) . vec(M_rho), HolE c . R[rho] (c_k = sum_j h_j
+        t_(j+k) mod d), both as KGE_LP_DOT against the relation table; a real (b, n_rel, d, d) candidate tensor is
+        scored as matrices (vec(h t^T) . vec(cand[i, rho]))."""
+        if isinstance(cand, RelationOperatorTable):
+            rows = _hip.bilinear_relation_rows(self._kind, h, t)
+            return _hip.LpProblem(_hip.LP_DOT, rows, _hip.f32c(self._rel_param().weight.data)).scores()
+        b, n_rel, d = cand.shape[0], cand.shape[1], self.emb_dim
+        rows = _hip.bilinear_relation_rows(_hip.RESCAL, h, t)
+        if cand.stride(0) == 0 or b == 1:
+            return _hip.LpProblem(_hip.LP_DOT, rows, _hip.f32c(cand[0].reshape(n_rel, d * d))).scores()
+        return _hip.lp_scores_batched(_hip.LP_DOT, rows, _hip.f32c(cand.reshape(b, n_rel, d * d)))
+
+    def inference_scoring_function(self, h, t, r):
+        """Rank dispatch of bilinear.py:98-121 / :365-389: the 3-D entity argument is the candidate set (with the
+        (b, d, d) operators in ``r``); a 4-D ``r`` means relation candidates."""
+        if _ndim(r) == 4:
+            assert _ndim(h) == 2 and _ndim(t) == 2
+            return self._relation_scores(h, t, r)
+        assert _ndim(r) == 3
+        if _ndim(t) == 3:
+            assert _ndim(h) == 2                     # tail completion: (h . B_r) . cand
+            q, cand = self._queries(h, r, 'tail'), t
+        else:
+            assert _ndim(h) == 3 and _ndim(t) == 2  # head completion: (B_r . t) . cand
+            q, cand = self._queries(t, r, 'head'), h
+        table = _table_of(cand)
+        if table is not None:
+            return _hip.LpProblem(_hip.LP_DOT, q, _hip.f32c(table)).scores()
+        return _hip.lp_scores_batched(_hip.LP_DOT, q, _hip.f32c(cand))
+
+    def inference_prepare_candidates(self, h_idx, t_idx, r_idx, entities=True):
+        """(h, t, r_mat, candidates) (bilinear.py:123-143, :391-411): r_mat is a RelationOperators handle for the
+        (b, d, d) operators, candidates a stride-0 (b, n_ent, d) view of the entity table or a RelationOperatorTable
+        handle for the (b, n_rel, d, d) relation operators."""
+        self._check_unsharded('inference_prepare_candidates')
+        b_size = max(h_idx.shape[0], t_idx.shape[0], r_idx.shape[0])   # inference passes one empty index
+        E = self.ent_emb.weight.data
+        h, t = _hip.gather_rows(E, h_idx), _hip.gather_rows(E, t_idx)
+        r = RelationOperators(self, r_idx)
+        if entities:
+            candidates = E.view(1, self.n_ent, self.emb_dim).expand(b_size, self.n_ent, self.emb_dim)
+        else:
+            candidates = RelationOperatorTable(self, b_size)
+        return h, t, r, candidates
+
+    def lp_problem(self, h_idx, t_idx, r_idx, side, ent_lo=0, ent_hi=None, exchange=None, qtabs=None, cols=None):
+        ent_lo, ent_hi = _ent_range(self, ent_lo, ent_hi)
+        sd = _hip.side_code(side)
+        Q0 = self._lp_prep(sd, h_idx, t_idx, r_idx, exchange, qtabs=qtabs)[0]
+        T0 = self._cand_rows(_hip.f32c(self.ent_emb.weight.data), ent_lo, ent_hi)
+        prob = self._attach_dot_split(_hip.LpProblem(_hip.LP_DOT, Q0, T0, c_base=ent_lo), T0, c_base=ent_lo)
+        prob.cols = cols if (sd == _hip.SIDE_BOTH and prob.split is not None) else None
+        return prob
+
+
+class RESCALModel(_OperatorModel):
+    """RESCAL (bilinear.py:14-143): ``RESCALModel(emb_dim, n_entities, n_relations)``; parameters ``ent_emb``
+    (L2-normalised rows) and ``rel_mat`` (n_rel, emb_dim * emb_dim), M_r = rel_mat[r].view(d, d)."""
+
+    _kind = _hip.RESCAL
+
+    def __init__(self, emb_dim, n_entities, n_relations):
+        super().__init__(emb_dim, n_entities, n_relations)
+        self.ent_emb = init_embedding(self.n_ent, self.emb_dim)
+        self.rel_mat = init_embedding(self.n_rel, self.emb_dim * self.emb_dim)
+        self.ent_emb.weight.data = torch.nn.functional.normalize(self.ent_emb.weight.data, p=2, dim=1)
+
+    def _rel_param(self):
+        return self.rel_mat
+
+    def _operators(self, r_idx):
+        d = self.emb_dim
+        return _hip.gather_rows(self.rel_mat.weight.data, r_idx).view(-1, d, d)
+
+    def get_embeddings(self):
+        """(ent_emb, rel_mat viewed (n_rel, d, d)) (bilinear.py:82-96)."""
+        self.normalize_parameters()
+        return self.ent_emb.weight.data, self.rel_mat.weight.data.view(-1, self.emb_dim, self.emb_dim)
+
+
+class HolEModel(_OperatorModel):
+    """HolE (bilinear.py:270-411): ``HolEModel(emb_dim, n_entities, n_relations)``; parameters ``ent_emb``
+    (L2-normalised rows) and ``rel_emb``; B_r = get_rolling_matrix(rel_emb[r])."""
+
+    _kind = _hip.HOLE
+
+    def __init__(self, emb_dim, n_entities, n_relations):
+        super().__init__(emb_dim, n_entities, n_relations)
+        self.ent_emb = init_embedding(self.n_ent, self.emb_dim)
+        self.rel_emb = init_embedding(self.n_rel, self.emb_dim)
+        self.ent_emb.weight.data = torch.nn.functional.normalize(self.ent_emb.weight.data, p=2, dim=1)
+
+    def _rel_param(self):
+        return self.rel_emb
+
+    @staticmethod
+    def get_rolling_matrix(x):
+        """(b, d) -> (b, d, d) with mat[i, j, k] = x[i, (k - j) mod d] (bilinear.py:326-340); any device."""
+        b_size, dim = x.shape
+        ar = torch.arange(dim, device=x.device)
+        idx = (ar.view(1, dim) - ar.view(dim, 1)) % dim
+        return x[:, idx.view(-1)].view(b_size, dim, dim)
+
+    def _operators(self, r_idx):
+        return self.get_rolling_matrix(_hip.gather_rows(self.rel_emb.weight.data, r_idx))
+
+    def get_embeddings(self):
+        """(ent_emb, rel_emb) (bilinear.py:351-363)."""
+        self.normalize_parameters()
+        return self.ent_emb.weight.data, self.rel_emb.weight.data
