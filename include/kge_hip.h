@@ -49,6 +49,7 @@
  *                                  sampling.py:313-325 and :206-221 (the integer scatter)
  *   kge_gather_rows              nn.Embedding lookups of the above
  *   kge_normalize_rows           Model.normalize_parameters (translation.py:83-90 etc.)
+ *   kge_frac_rows                TorusEModel.normalize_parameters (translation.py:723-728)
  *   kge_bilinear_query           RESCAL / HolE inference_scoring_function on entity candidates: the query row h.M_r /
  *                                  M_r.t (bilinear.py:98-114, :365-381) that a KGE_LP_DOT problem then scores
  *   kge_bilinear_relation_rows   RESCAL / HolE relation candidates (bilinear.py:115-121, :382-389)
@@ -78,7 +79,14 @@ enum {
     KGE_DISTMULT = 4,
     KGE_COMPLEX = 5,
     KGE_RESCAL = 6,     /* ABI 33: tables {E, rel_mat}, d_ent = d, d_rel = d * d (M_r = rel_mat[r] viewed (d, d)) */
-    KGE_HOLE = 7        /* ABI 33: tables {E, R}, d_ent = d_rel = d (B_r = the rolling matrix of R[r]) */
+    KGE_HOLE = 7,       /* ABI 33: tables {E, R}, d_ent = d_rel = d (B_r = the rolling matrix of R[r]) */
+    /* TorusE (translation.py:655-767), tables {E, R}, d_ent = d_rel = d, kge_score_triples / _bwd only: h, r, t are the
+     * gathered rows with frac(x) = x - truncf(x) applied (the tables are not changed), x = (h + r) - t per element and
+     * score = -diss(x) with the dissimilarity of the type (utils/dissimilarities.py:11-54): */
+    KGE_TORUSE_L1 = 8,          /* 'L1':        sum |x|                                                      */
+    KGE_TORUSE_TORUS_L1 = 9,    /* 'torus_L1':  2 sum min(|x|, 1 - |x|)                                      */
+    KGE_TORUSE_TORUS_L2 = 10,   /* 'torus_L2':  4 sum min(x*x, 1 - x*x)                                      */
+    KGE_TORUSE_TORUS_EL2 = 11   /* 'torus_eL2': sum (1 - cos(2 pi min(x, 1 - x))) / 2                        */
 };
 
 /* which entity is replaced by the candidates */
@@ -107,10 +115,14 @@ enum {
     KGE_LP_L1_DIRECT = 2,  /* s = -sum_k |A0 - T0 (+a*Wq)|     broadcast-subtract, fp32 VALU   */
     KGE_LP_L2_DIRECT = 3,  /* s = -sum_k (A0 - T0 (+a*Wq))^2   broadcast-subtract, fp32 VALU   */
     KGE_LP_L2_PROJH = 4,   /* TransH: ||u - e + x w||^2 expanded around u.e, x = X[r_i,c]   fp32 MFMA + gather */
-    KGE_LP_L2_PROJD = 5    /* TransD: ||u - e' - y_c w||^2 expanded around u.e', g = X[r_i,c] fp32 MFMA + gather */
+    KGE_LP_L2_PROJD = 5,   /* TransD: ||u - e' - y_c w||^2 expanded around u.e', g = X[r_i,c] fp32 MFMA + gather */
+    KGE_LP_TORUS_L1 = 6,   /* s = -2 sum_k min(|x|, 1 - |x|),     x = A0 - T0   broadcast-subtract, fp32 VALU  */
+    KGE_LP_TORUS_L2 = 7,   /* s = -4 sum_k min(x*x, 1 - x*x)                     broadcast-subtract, fp32 VALU  */
+    KGE_LP_TORUS_EL2 = 8   /* s = -sum_k (1 - cos(2 pi min(x, 1 - x))) / 2       broadcast-subtract, fp32 VALU  */
 };
-/* the MFMA (GEMM-shaped) modes: everything but the two DIRECT ones */
-#define KGE_LP_IS_MFMA(mode) ((mode) <= KGE_LP_L2_EXPAND || (mode) >= KGE_LP_L2_PROJH)
+/* the MFMA (GEMM-shaped) modes: DOT, L2_EXPAND, L2_PROJH, L2_PROJD; the DIRECT and TORUS ones run on the VALU */
+#define KGE_LP_IS_MFMA(mode) ((mode) == KGE_LP_DOT || (mode) == KGE_LP_L2_EXPAND || (mode) == KGE_LP_L2_PROJH || \
+                              (mode) == KGE_LP_L2_PROJD)
 
 /*
  * Descriptor of one all-candidates scoring problem: B queries against the N
@@ -130,6 +142,14 @@ enum {
  *                   L2: acc = fmaf(diff_k, diff_k, acc), k ascending;
  *                   L1: acc += (|diff_k| + |diff_k+1|) + (|diff_k+2| + |diff_k+3|) per aligned group of four k
  *                       (absent k >= K0 count as 0);  s = -acc
+ *     TORUS_*    : x_k = A0[i,k] - T0[c,k] (no Wq, K1 = 0); one accumulator, acc += (m_k + m_k+1) + (m_k+2 + m_k+3)
+ *                  per aligned group of four k as L1 (absent k count as 0: every m below is 0 at x = 0), with
+ *                    TORUS_L1 : a = |x|;  m = fminf(a, 1 - a);                      s = -(2 * acc)
+ *                    TORUS_L2 : v = x * x (no fma);  m = fminf(v, 1 - v);           s = -(4 * acc)
+ *                    TORUS_EL2: u = fminf(x, 1 - x);  m = 1 - cosf(6.2831855f * u);  s = -(0.5 * acc)
+ *                  (cosf = ocml's fp32 cosine of the fp32 product, the reference's `cos(2 * pi * tmp)` in fp32).
+ *                  The terms are applied literally to x: |x| > 1 makes a term negative and a score may be POSITIVE
+ *                  (TorusE's tables lie in (-1, 1), h + r in (-2, 2)); nothing assumes s <= 0.
  *   chain(x, y, K): ONE accumulator, acc = fmaf(x[k], y[k], acc), k visiting
  *   the 8-blocks of [0,K) in ascending order and, inside each 8-block, the
  *   offsets 0,4,1,5,2,6,3,7 (absent k >= K skipped) -- exactly the sequence in
@@ -160,7 +180,7 @@ typedef struct kge_lp_desc {
 
 /* ---- K1: fused gather + normalise + score (scoring_function) ------------- */
 /* tables: TransE/DistMult {E,R}; TransH {E,R,W}; TransD {E,R,Ep,Rp}; ComplEx {Ere,Eim,Rre,Rim};
- * RESCAL {E,rel_mat}; HolE {E,R}.
+ * RESCAL {E,rel_mat}; HolE {E,R}; TorusE (KGE_TORUSE_*) {E,R}.
  * d_ent = row length of entity tables, d_rel = row length of relation tables
  * (equal except TransD, which needs d_ent >= d_rel, and RESCAL, d_rel = d_ent^2).  Tables are contiguous.
  * RESCAL / HolE (ABI 33, bilinear.py:60-71, :311-323): score = h^ . B_r . t^ with B_r = M_r = rel_mat[r] viewed (d, d)
@@ -179,6 +199,7 @@ int kge_score_triples(int kind, const float *t0, const float *t1, const float *t
  *     ComplEx: 0 (g0,h) 1 (g0,t) 2 (g1,h) 3 (g1,t) 4 (g2,r) 5 (g3,r)
  *     TransD:  0 (g0,h) 1 (g0,t) 2 (g2,h) 3 (g2,t) 4 (g1,r) 5 (g3,r)
  *     HolE:    0 (g0,h) 1 (g0,t) 2 (g1,r)
+ *     TorusE:  0 (g0,h) 1 (g0,t) 2 (g1,r)   (closed form: d|x| = sign(x), the taken branch of each min, 0 at an exact tie)
  *     RESCAL:  0 (g0,h) 1 (g0,t), and the operands of kge_rescal_rel_grad: 2 U_i = go_i h^_i, 3 V_i = t^_i
  *   and the caller reduces them per target table with kge_segment_sum_rows.
  * RESCAL needs the row mode (rows != NULL, g0..g3 unused): its rel_mat gradient is d^2 wide per triple and is never
@@ -313,6 +334,8 @@ int kge_gather_rows(const float *X, int64_t ld, const int64_t *idx, int64_t rows
                     float *out, kge_stream_t stream);
 /* X[i,:] /= max(||X[i,:]||_2, 1e-12)   (torch.nn.functional.normalize, p=2, dim=1) */
 int kge_normalize_rows(float *X, int64_t ld, int64_t rows, int K, kge_stream_t stream);
+/* X[i,k] = X[i,k] - truncf(X[i,k]) in place (torch.frac_, TorusEModel.normalize_parameters, translation.py:723-728) */
+int kge_frac_rows(float *X, int64_t ld, int64_t rows, int K, kge_stream_t stream);
 
 /* ---- all-candidates scoring ----------------------------------------------- */
 /* out[i*ldo + c] = score(i,c), i<B, c<N (local candidates). */
@@ -401,7 +424,8 @@ int kge_copy_i64_indirect(const int64_t *src, int64_t n, int64_t *const *dst_ind
 
 /* generic: every query has its own candidate matrix cand[i] (N,K) at
  * cand + i*stride_b (stride_b = 0: shared), rows at stride_n.
- * mode DOT / L1_DIRECT / L2_DIRECT; score = f(q[i], cand[i,c]). */
+ * mode DOT / L1_DIRECT / L2_DIRECT / TORUS_*; score = f(q[i], cand[i,c]) (lanes over k, a wavefront sum: NOT the
+ * chains of kge_lp_scores). */
 int kge_lp_scores_batched(int mode, const float *q, int64_t ldq, const float *cand,
                           int64_t stride_b, int64_t stride_n, int64_t B, int64_t N, int K,
                           float *out, int64_t ldo, kge_stream_t stream);

@@ -16,9 +16,13 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libkge_hip.so')
 
 # enums of include/kge_hip.h
 TRANSE_L1, TRANSE_L2, TRANSH, TRANSD, DISTMULT, COMPLEX, RESCAL, HOLE = range(8)
+TORUSE_L1, TORUSE_TORUS_L1, TORUSE_TORUS_L2, TORUSE_TORUS_EL2 = range(8, 12)
 SIDE_TAIL, SIDE_HEAD, SIDE_PROJ_H, SIDE_PROJ_T, SIDE_BOTH = range(5)
 EW_ADD, EW_SUB, EW_MUL, EW_MULSUB, EW_MULADD = range(5)
 LP_DOT, LP_L2_EXPAND, LP_L1_DIRECT, LP_L2_DIRECT, LP_L2_PROJH, LP_L2_PROJD = range(6)
+LP_TORUS_L1, LP_TORUS_L2, LP_TORUS_EL2 = range(6, 9)
+# the modes whose all-candidates scores are a GEMM (KGE_LP_IS_MFMA of include/kge_hip.h); the rest run on the VALU
+LP_MFMA_MODES = (LP_DOT, LP_L2_EXPAND, LP_L2_PROJH, LP_L2_PROJD)
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -85,6 +89,7 @@ _SIGNATURES = {
     'kge_row_dot': [_vp, _vp, _i64, _i64, _int, ctypes.c_float, _vp, _vp],
     'kge_gather_rows': [_vp, _i64, _vp, _i64, _int, _vp, _vp],
     'kge_normalize_rows': [_vp, _i64, _i64, _int, _vp],
+    'kge_frac_rows': [_vp, _i64, _i64, _int, _vp],
     'kge_lp_scores': [ctypes.POINTER(LpDesc), _vp, _i64, _vp],
     'kge_lp_pair_scores': [ctypes.POINTER(LpDesc), _vp, _vp, _i64, _vp, _vp],
     'kge_lp_count_ge': [ctypes.POINTER(LpDesc), _vp, _vp, _vp],
@@ -280,6 +285,8 @@ _BWD_STREAMS = {
     COMPLEX: [(0, 0, 2, 'ht'), (1, 2, 2, 'ht'), (2, 4, 1, 'r'), (3, 5, 1, 'r')],
     TRANSD: [(0, 0, 2, 'ht'), (2, 2, 2, 'ht'), (1, 4, 1, 'r'), (3, 5, 1, 'r')],
     HOLE: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
+    TORUSE_L1: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')], TORUSE_TORUS_L1: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
+    TORUSE_TORUS_L2: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')], TORUSE_TORUS_EL2: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
     # rel_mat's gradient (d^2 per triple) is reduced per relation from streams 2 / 3 (kge_rescal_rel_grad)
     RESCAL: [(0, 0, 2, 'ht')],
 }
@@ -321,7 +328,9 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
     dev = h.device
     if kind == RESCAL:
         return _rescal_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
-    if B < BWD_SORTED_MIN_BATCH:
+    # (TorusE: always the row mode -- no per-element float atomics; a batch whose rows fit one 32-entry chunk per stream
+    # of kge_segment_sum_rows gets the same bits on every run)
+    if B < BWD_SORTED_MIN_BATCH and kind < TORUSE_L1:
         with _on(dev):
             _check(lib.kge_score_triples_bwd(kind, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
                                              d_ent, d_rel, _p(h), _p(t), _p(r), B, _p(go),
@@ -942,6 +951,19 @@ def normalize_rows_(X):
     with _on(X.device):
         _check(lib.kge_normalize_rows(_p(X), X.stride(0), X.shape[0], X.shape[1], _stream()),
                'kge_normalize_rows')
+    return X
+
+
+def frac_rows_(X):
+    """In-place X.frac_() (x - trunc(x)) of a contiguous float32 matrix (kge_frac_rows)."""
+    lib = load_library()
+    require_cuda(X)
+    if not X.is_contiguous() or X.dtype != torch.float32 or X.dim() != 2:
+        raise RuntimeError('frac_rows_: need a contiguous float32 matrix')
+    if X.numel() == 0:
+        return X
+    with _on(X.device):
+        _check(lib.kge_frac_rows(_p(X), X.stride(0), X.shape[0], X.shape[1], _stream()), 'kge_frac_rows')
     return X
 
 

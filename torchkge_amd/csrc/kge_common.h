@@ -104,6 +104,48 @@ __device__ __forceinline__ float lp_epilogue_any(const kge_lp_desc &d, float dot
     return lp_epilogue_proj(d.mode, v0, x, y, d.Wq[i * d.ldw], d.Wq[i * d.ldw + 1]);
 }
 
+// ---- per-element terms of the group-of-four direct chains: L1 and the torus modes (include/kge_hip.h) --------------
+// x = q - t; every term is 0 at x = 0 (zero-filled padding k counts as nothing).  The compiler must not contract x * x
+// into the following subtraction (-ffp-contract=off): 1 - v rounds the ROUNDED square, as torch's `1 - (a - b) ** 2`.
+constexpr float KGE_TWO_PI_F = 6.2831855f;      // fp32(2 pi): the reference's `2 * pi * tmp` on an fp32 tensor
+template <int MODE>
+__device__ __forceinline__ float lp_direct_term(float x)
+{
+    if (MODE == KGE_LP_TORUS_L1) {
+        const float a = fabsf(x);
+        return fminf(a, 1.0f - a);
+    } else if (MODE == KGE_LP_TORUS_L2) {
+        const float v = x * x;
+        return fminf(v, 1.0f - v);
+    } else if (MODE == KGE_LP_TORUS_EL2) {
+        const float u = fminf(x, 1.0f - x);
+        return 1.0f - cosf(KGE_TWO_PI_F * u);
+    }
+    return fabsf(x);    // KGE_LP_L1_DIRECT
+}
+// score from the accumulated terms (power-of-two scalings: exact, the same bits as scaling every term)
+template <int MODE>
+__device__ __forceinline__ float lp_direct_finish(float acc)
+{
+    if (MODE == KGE_LP_TORUS_L1) return -(2.0f * acc);
+    if (MODE == KGE_LP_TORUS_L2) return -(4.0f * acc);
+    if (MODE == KGE_LP_TORUS_EL2) return -(0.5f * acc);
+    return -acc;
+}
+// one accumulator, one add per aligned group of four k, the group's terms summed as (m0 + m1) + (m2 + m3), absent k = 0
+template <int MODE>
+__device__ __forceinline__ float lp_group_chain(const float *q, const float *t, int K)
+{
+    float acc = 0.0f;
+    for (int k = 0; k < K; k += 4) {
+        float m[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[e] = lp_direct_term<MODE>(k + e < K ? q[k + e] - t[k + e] : 0.0f);
+        acc = acc + ((m[0] + m[1]) + (m[2] + m[3]));
+    }
+    return acc;
+}
+
 // score of query i against LOCAL candidate c, any mode (scalar reference path
 // used by the pair / filter kernels; bit-identical to the tile kernels).
 __device__ __forceinline__ float lp_pair_score(const kge_lp_desc &d, int64_t i, int64_t c)
@@ -115,6 +157,12 @@ __device__ __forceinline__ float lp_pair_score(const kge_lp_desc &d, int64_t i, 
     }
     const float *q = d.A0 + i * d.lda0;
     const float *t = d.T0 + c * d.ldt0;
+    switch (d.mode) {   // the torus modes: no rank-1 term (kge_lp_desc_check)
+    case KGE_LP_TORUS_L1: return lp_direct_finish<KGE_LP_TORUS_L1>(lp_group_chain<KGE_LP_TORUS_L1>(q, t, d.K0));
+    case KGE_LP_TORUS_L2: return lp_direct_finish<KGE_LP_TORUS_L2>(lp_group_chain<KGE_LP_TORUS_L2>(q, t, d.K0));
+    case KGE_LP_TORUS_EL2: return lp_direct_finish<KGE_LP_TORUS_EL2>(lp_group_chain<KGE_LP_TORUS_EL2>(q, t, d.K0));
+    default: break;
+    }
     float acc = 0.0f;
     const bool l1 = d.mode == KGE_LP_L1_DIRECT;
     const float a = d.Wq ? d.scal[c * d.scal_ld + (d.scal_ld > 1 ? d.r_idx[i] : 0)] : 0.0f;
@@ -168,15 +216,18 @@ static inline bool kge_lp_vec4(const kge_lp_desc &d)
 }
 
 // the direct modes' chains (lp_pair_score without the rank-1 term), one accumulator: L2 one fmaf per k in
-// ascending order; L1 one add per aligned 4-group of k, the group as (|d0|+|d1|)+(|d2|+|d3|).  `a` / `t` must be
-// readable (zero-filled) up to the next multiple of 4 -- the staged chunks below are.
-template <bool L1>
+// ascending order; L1 and the torus modes one add per aligned 4-group of k, the group as (m0+m1)+(m2+m3).  `a` / `t`
+// must be readable (zero-filled) up to the next multiple of 4 -- the staged chunks below are.
+// CH: 1 = L1 direct, 2 = L2 direct, or a KGE_LP_TORUS_* mode
+template <int CH>
 __device__ __forceinline__ float lp_chain_direct(const float *__restrict__ a, const float *__restrict__ t, int K, float acc)
 {
-    if (L1) {
+    if (CH != 2) {
+        constexpr int OP = CH == 1 ? (int)KGE_LP_L1_DIRECT : CH;
         for (int k = 0; k < K; k += 4) {
             const float4 av = *reinterpret_cast<const float4 *>(a + k), tv = *reinterpret_cast<const float4 *>(t + k);
-            acc = acc + ((fabsf(av.x - tv.x) + fabsf(av.y - tv.y)) + (fabsf(av.z - tv.z) + fabsf(av.w - tv.w)));
+            acc = acc + ((lp_direct_term<OP>(av.x - tv.x) + lp_direct_term<OP>(av.y - tv.y)) +
+                         (lp_direct_term<OP>(av.z - tv.z) + lp_direct_term<OP>(av.w - tv.w)));
         }
     } else {
         for (int k = 0; k < K; ++k) {
@@ -187,7 +238,7 @@ __device__ __forceinline__ float lp_chain_direct(const float *__restrict__ a, co
     return acc;
 }
 
-// CH: 0 = the MFMA modes' dot chain (lp_chain_dot), 1 = L1 direct, 2 = L2 direct
+// CH: 0 = the MFMA modes' dot chain (lp_chain_dot), 1 = L1 direct, 2 = L2 direct, KGE_LP_TORUS_*: that torus mode
 template <bool VEC4, int CH = 0>
 __device__ __forceinline__ float lp_staged_segment(const float *__restrict__ A, int64_t lda,
                                                    const float *__restrict__ T, int64_t ldt, int K, int qi, int ci,
@@ -224,7 +275,7 @@ __device__ __forceinline__ float lp_staged_segment(const float *__restrict__ A, 
             if (k0 + 2 * KGE_PS_KC <= K) { KGE_PS_ALL(KGE_PS_FETCH, k0 + KGE_PS_KC) }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // same wave: LDS executes in order
             if (CH == 0) acc = lp_chain_dot(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, KGE_PS_KC, acc);
-            else acc = lp_chain_direct<CH == 1>(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, KGE_PS_KC, acc);
+            else acc = lp_chain_direct<CH>(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, KGE_PS_KC, acc);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         }
 #undef KGE_PS_ALL
@@ -252,7 +303,7 @@ __device__ __forceinline__ float lp_staged_segment(const float *__restrict__ A, 
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         if (CH == 0) acc = lp_chain_dot(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, kc, acc);
-        else acc = lp_chain_direct<CH == 1>(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, kc, acc);
+        else acc = lp_chain_direct<CH>(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, kc, acc);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
     return acc;
@@ -263,6 +314,15 @@ template <bool VEC4, bool L1>
 __device__ __forceinline__ float lp_pair_score_staged_direct(const kge_lp_desc &d, int qi, int ci, float *qs, float *es)
 {
     return -lp_staged_segment<VEC4, L1 ? 1 : 2>(d.A0, d.lda0, d.T0, d.ldt0, d.K0, qi, ci, qs, es, 0.0f);
+}
+
+// plain direct or torus modes by chain code (CH of lp_staged_segment: 1 L1, 2 L2, KGE_LP_TORUS_*), bit-identical to
+// lp_pair_score
+template <bool VEC4, int CH>
+__device__ __forceinline__ float lp_pair_score_staged_ch(const kge_lp_desc &d, int qi, int ci, float *qs, float *es)
+{
+    static_assert(CH == 1 || CH == 2 || CH == KGE_LP_TORUS_L1 || CH == KGE_LP_TORUS_L2 || CH == KGE_LP_TORUS_EL2, "chain code");
+    return lp_direct_finish<CH>(lp_staged_segment<VEC4, CH>(d.A0, d.lda0, d.T0, d.ldt0, d.K0, qi, ci, qs, es, 0.0f));
 }
 
 // MFMA modes only (KGE_LP_IS_MFMA); (qi, ci) must be valid rows on every lane
@@ -284,14 +344,15 @@ static inline int kge_env_int(const char *name, int dflt)
 static inline int kge_lp_desc_check(const kge_lp_desc *d)
 {
     if (!d) return KGE_EINVAL;
-    if (d->mode < KGE_LP_DOT || d->mode > KGE_LP_L2_PROJD) return KGE_EINVAL;
+    if (d->mode < KGE_LP_DOT || d->mode > KGE_LP_TORUS_EL2) return KGE_EINVAL;
     if (d->B < 0 || d->N < 0 || d->K0 <= 0 || d->K1 < 0) return KGE_EINVAL;
     if (d->B == 0 || d->N == 0) return 0; // empty problem: nothing is dereferenced
     if (!d->A0 || !d->T0) return KGE_EINVAL;
     if (d->K1 > 0 && (!d->A1 || !d->T1)) return KGE_EINVAL;
     if (d->K1 > 0 && d->mode != KGE_LP_DOT) return KGE_EINVAL;
     if (d->mode == KGE_LP_L2_EXPAND && (!d->qn || !d->en)) return KGE_EINVAL;
-    if (d->mode >= KGE_LP_L2_PROJH) {
+    if (d->mode >= KGE_LP_TORUS_L1) return d->Wq ? KGE_EINVAL : 0;     // plain per-element chains, no rank-1 term
+    if (d->mode == KGE_LP_L2_PROJH || d->mode == KGE_LP_L2_PROJD) {
         if (!d->qn || !d->en || !d->Wq || d->ldw < 2 || !d->scal || d->scal_ld < d->N || !d->r_idx) return KGE_EINVAL;
         if (d->mode == KGE_LP_L2_PROJD && !d->yc) return KGE_EINVAL;
         return 0;

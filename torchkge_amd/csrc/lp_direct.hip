@@ -16,6 +16,13 @@
 // absent k count as 0 -- the same instruction count as a plain chain, a quarter
 // of its roundings at full magnitude), q / e / w tiles staged through
 // double-buffered LDS in BK = 32 slices (row stride 36: conflict-free b128).
+//
+// The same kernel, with the per-element operation as its template parameter,
+// scores TorusE (translation.py:655-767; KGE_LP_TORUS_L1 / _L2 / _EL2): the
+// torus dissimilarities (utils/dissimilarities.py:28-54) of x = q - e have no
+// GEMM form; each term (kge_common.h: lp_direct_term) goes through the L1
+// group-of-four accumulation, and the reference's (b, N, d) broadcast is never
+// built.
 #include "kge_common.h"
 
 namespace {
@@ -61,16 +68,13 @@ __device__ __forceinline__ void lds_store8(float *dst, const float (&v)[8])
     *reinterpret_cast<float4 *>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
 
-template <bool L1>
-__device__ __forceinline__ float acc_step(float acc, float diff)
-{
-    return L1 ? acc + fabsf(diff) : fmaf(diff, diff, acc);
-}
-
-// TM = 8 (plain) or 4 (AXPY: the per-pair scalar a(i,c) also lives in registers)
-template <bool VEC4, bool L1, bool AXPY, bool COUNT, int TM>
+// TM = 8 (plain) or 4 (AXPY: the per-pair scalar a(i,c) also lives in registers).
+// OP: the per-element operation -- KGE_LP_L2_DIRECT (one fmaf per k), or KGE_LP_L1_DIRECT / a KGE_LP_TORUS_* mode (one
+// add per aligned 4-group of lp_direct_term, kge_common.h); the torus modes have no rank-1 term (AXPY = false).
+template <bool VEC4, int OP, bool AXPY, bool COUNT, int TM>
 __global__ __launch_bounds__(NTHREADS, 2) void lp_direct_kernel(const DirectParams p)
 {
+    static_assert(!AXPY || OP == KGE_LP_L1_DIRECT || OP == KGE_LP_L2_DIRECT, "rank-1 term: L1 / L2 only");
     constexpr int BM = 16 * TM;
     constexpr int QCH = BM * 4 / NTHREADS; // 8-float chunks of the q tile per thread (2 or 1)
     constexpr int Q_FLOATS = BM * LDS_LD, T_FLOATS = BN * LDS_LD;
@@ -227,11 +231,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void lp_direct_kernel(const DirectPara
                         dz = fmaf(a, wv.z, dz); dw = fmaf(a, wv.w, dw);
                     }
                     float v = acc[i][j];
-                    if (L1) {   // the L1 contract: one add per aligned 4-group, the group summed as a tree
-                        v = v + ((fabsf(dx) + fabsf(dy)) + (fabsf(dz) + fabsf(dw)));
+                    if (OP != KGE_LP_L2_DIRECT) {   // the L1 / torus contract: one add per aligned 4-group, the group summed as a tree
+                        v = v + ((lp_direct_term<OP>(dx) + lp_direct_term<OP>(dy)) +
+                                 (lp_direct_term<OP>(dz) + lp_direct_term<OP>(dw)));
                     } else {
-                        v = acc_step<L1>(v, dx); v = acc_step<L1>(v, dy);
-                        v = acc_step<L1>(v, dz); v = acc_step<L1>(v, dw);
+                        v = fmaf(dx, dx, v); v = fmaf(dy, dy, v);
+                        v = fmaf(dz, dz, v); v = fmaf(dw, dw, v);
                     }
                     acc[i][j] = v;
                 }
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void lp_direct_kernel(const DirectPara
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const int64_t col = col0 + tx + 16 * j;
-                    const float sc = -acc[i][j];
+                    const float sc = lp_direct_finish<OP == KGE_LP_L2_DIRECT ? (int)KGE_LP_L1_DIRECT : OP>(acc[i][j]);   // (L1 / L2: -acc)
                     if (COUNT) cnt[i] += (sc >= stv) ? (col < d.N ? 1 : 0) : 0;
                     else if (col < d.N && row < d.B) p.out[row * p.ldo + col] = sc;
                     acc[i][j] = 0.f;
@@ -571,7 +576,7 @@ int launch_pk(DirectParams &p, hipStream_t s)
     return 0;
 }
 
-template <bool VEC4, bool L1, bool AXPY, bool COUNT>
+template <bool VEC4, int OP, bool AXPY, bool COUNT>
 int launch(DirectParams &p, hipStream_t s)
 {
     constexpr int TM = AXPY ? 4 : 8;
@@ -589,7 +594,7 @@ int launch(DirectParams &p, hipStream_t s)
     p.col_chunks = (p.col_tiles + p.tiles_per_block - 1) / p.tiles_per_block;
     const int grid = p.row_panels * p.col_chunks;
 
-    auto k = lp_direct_kernel<VEC4, L1, AXPY, COUNT, TM>;
+    auto k = lp_direct_kernel<VEC4, OP, AXPY, COUNT, TM>;
     static int attr_dev[16];    // per instantiation, per device
     if (int e = kge_ensure_dyn_smem(reinterpret_cast<const void *>(k), SMEM_BYTES, attr_dev)) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), SMEM_BYTES, s, p);
@@ -597,11 +602,27 @@ int launch(DirectParams &p, hipStream_t s)
     return 0;
 }
 
-template <bool VEC4, bool L1>
+template <bool VEC4, int OP>
 int dispatch2(DirectParams &p, bool axpy, bool count, hipStream_t s)
 {
-    if (axpy) return count ? launch<VEC4, L1, true, true>(p, s) : launch<VEC4, L1, true, false>(p, s);
-    return count ? launch<VEC4, L1, false, true>(p, s) : launch<VEC4, L1, false, false>(p, s);
+    if (axpy) return count ? launch<VEC4, OP, true, true>(p, s) : launch<VEC4, OP, true, false>(p, s);
+    return count ? launch<VEC4, OP, false, true>(p, s) : launch<VEC4, OP, false, false>(p, s);
+}
+// the torus modes (no rank-1 term)
+template <bool VEC4, int OP>
+int dispatch_torus(DirectParams &p, bool count, hipStream_t s)
+{
+    return count ? launch<VEC4, OP, false, true>(p, s) : launch<VEC4, OP, false, false>(p, s);
+}
+template <bool VEC4>
+int dispatch_torus_mode(DirectParams &p, bool count, hipStream_t s)
+{
+    switch (p.d.mode) {
+    case KGE_LP_TORUS_L1: return dispatch_torus<VEC4, KGE_LP_TORUS_L1>(p, count, s);
+    case KGE_LP_TORUS_L2: return dispatch_torus<VEC4, KGE_LP_TORUS_L2>(p, count, s);
+    case KGE_LP_TORUS_EL2: return dispatch_torus<VEC4, KGE_LP_TORUS_EL2>(p, count, s);
+    default: return KGE_EINVAL;
+    }
 }
 
 } // namespace
@@ -652,10 +673,14 @@ int kge_lp_direct_run(const kge_lp_desc *d, float *out, int64_t ldo, const float
     if (axpy) vec4 = vec4 && (d->ldw % 4 == 0) && kge_aligned16(d->Wq);
     const bool l1 = d->mode == KGE_LP_L1_DIRECT;
     const bool count = raw_count != nullptr;
+    if (d->mode >= KGE_LP_TORUS_L1) {       // (kge_lp_desc_check: no rank-1 term)
+        if (axpy) return KGE_EINVAL;
+        return vec4 ? dispatch_torus_mode<true>(p, count, s) : dispatch_torus_mode<false>(p, count, s);
+    }
     if (vec4 && !l1 && !kge_env_int("KGE_DIRECT_SCALAR", 0)) {      // L2 on aligned operands: the packed-FMA kernel
         if (axpy) return count ? launch_pk<true, true>(p, s) : launch_pk<true, false>(p, s);
         return count ? launch_pk<false, true>(p, s) : launch_pk<false, false>(p, s);
     }
-    if (vec4) return l1 ? dispatch2<true, true>(p, axpy, count, s) : dispatch2<true, false>(p, axpy, count, s);
-    return l1 ? dispatch2<false, true>(p, axpy, count, s) : dispatch2<false, false>(p, axpy, count, s);
+    if (vec4) return l1 ? dispatch2<true, KGE_LP_L1_DIRECT>(p, axpy, count, s) : dispatch2<true, KGE_LP_L2_DIRECT>(p, axpy, count, s);
+    return l1 ? dispatch2<false, KGE_LP_L1_DIRECT>(p, axpy, count, s) : dispatch2<false, KGE_LP_L2_DIRECT>(p, axpy, count, s);
 }

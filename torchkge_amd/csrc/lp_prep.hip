@@ -615,6 +615,17 @@ __global__ __launch_bounds__(WPB * 64) void normalize_rows_kernel(float *X, int6
     }
 }
 
+// torch.frac_ (x - trunc(x), exact in fp32, keeps the sign): TorusEModel.normalize_parameters
+__global__ __launch_bounds__(WPB * 64) void frac_rows_kernel(float *X, int64_t ld, int64_t rows, int K)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+    for (int64_t i = wave; i < rows; i += (int64_t)gridDim.x * WPB) {
+        float *x = X + i * ld;
+        for (int k = lane; k < K; k += 64) x[k] = x[k] - truncf(x[k]);
+    }
+}
+
 } // namespace
 
 // rows up to which the staged chain kernels run 16 rows per wavefront (131,072 rows = 8,192 wavefronts: 32 per CU)
@@ -728,6 +739,16 @@ extern "C" int kge_normalize_rows(float *X, int64_t ld, int64_t rows, int K, kge
     if (rows == 0) return 0;
     if (!X) return KGE_EINVAL;
     hipLaunchKernelGGL(normalize_rows_kernel, dim3(grid_rows(rows)), dim3(WPB * 64), 0, kge_s(stream), X, ld, rows, K);
+    KGE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int kge_frac_rows(float *X, int64_t ld, int64_t rows, int K, kge_stream_t stream)
+{
+    if (rows < 0 || K <= 0 || ld < K) return KGE_EINVAL;
+    if (rows == 0) return 0;
+    if (!X) return KGE_EINVAL;
+    hipLaunchKernelGGL(frac_rows_kernel, dim3(grid_rows(rows)), dim3(WPB * 64), 0, kge_s(stream), X, ld, rows, K);
     KGE_CHECK_LAUNCH();
     return 0;
 }

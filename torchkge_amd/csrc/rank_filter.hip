@@ -235,7 +235,7 @@ __global__ __launch_bounds__(64, 2) void pair_scores_staged_kernel(const kge_lp_
         if (p < P) { i = qi ? qi[p] : p; c = ci[p] - d.c_base; }
         const bool ok = p < P && c >= 0 && c < d.N;
         float sc;
-        if (DIRECT) sc = lp_pair_score_staged_direct<VEC4, DIRECT == 1>(d, ok ? (int)i : 0, ok ? (int)c : 0, qs, es);
+        if constexpr (DIRECT != 0) sc = lp_pair_score_staged_ch<VEC4, DIRECT>(d, ok ? (int)i : 0, ok ? (int)c : 0, qs, es);
         else sc = lp_pair_score_staged<VEC4>(d, ok ? (int)i : 0, ok ? (int)c : 0, qs, es);
         if (p < P) out[p] = ok ? sc : 0.f;
     }
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(FS_SCAN_T) void fsub_off_kernel(int64_t B, int64_t 
 }
 
 // scores of the flattened (claimed key, target) pairs: one lane per pair, 64 pairs per wavefront round
-template <bool STAGED, bool VEC4, int DIRECT = 0>   // DIRECT: 0 MFMA modes / scalar; 1 plain L1 direct, 2 plain L2 direct (staged)
+template <bool STAGED, bool VEC4, int DIRECT = 0>   // DIRECT: 0 MFMA modes / scalar; 1 plain L1 direct, 2 plain L2 direct, KGE_LP_TORUS_* (staged)
 __global__ __launch_bounds__(64, 2) void fsub_score_kernel(const kge_lp_desc d, const int64_t *__restrict__ seg_lo,
                                                         const int32_t *__restrict__ targets,
                                                         const int64_t *__restrict__ woff, float *fs)
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(64, 2) void fsub_score_kernel(const kge_lp_desc d, 
         }
         const bool ok = valid && c >= 0 && c < d.N;
         float sc;
-        if (STAGED && DIRECT) sc = lp_pair_score_staged_direct<VEC4, DIRECT == 1>(d, ok ? (int)i : 0, ok ? (int)c : 0, qs, es);
+        if constexpr (STAGED && DIRECT != 0) sc = lp_pair_score_staged_ch<VEC4, DIRECT>(d, ok ? (int)i : 0, ok ? (int)c : 0, qs, es);
         else if (STAGED) sc = lp_pair_score_staged<VEC4>(d, ok ? (int)i : 0, ok ? (int)c : 0, qs, es);
         else sc = ok ? lp_pair_score(d, i, c) : 0.f;
         if (ok) fs[j] = sc;
@@ -632,11 +632,25 @@ __global__ __launch_bounds__(256) void lp_batched_kernel(int mode, const float *
             if (mode == KGE_LP_DOT) acc = fmaf(qq[k], cc[k], acc);
             else {
                 const float diff = qq[k] - cc[k];
-                acc = (mode == KGE_LP_L1_DIRECT) ? acc + fabsf(diff) : fmaf(diff, diff, acc);
+                switch (mode) {
+                case KGE_LP_L1_DIRECT: acc = acc + fabsf(diff); break;
+                case KGE_LP_TORUS_L1: acc = acc + lp_direct_term<KGE_LP_TORUS_L1>(diff); break;
+                case KGE_LP_TORUS_L2: acc = acc + lp_direct_term<KGE_LP_TORUS_L2>(diff); break;
+                case KGE_LP_TORUS_EL2: acc = acc + lp_direct_term<KGE_LP_TORUS_EL2>(diff); break;
+                default: acc = fmaf(diff, diff, acc);
+                }
             }
         }
         acc = wave_sum(acc);
-        if (lane == 0) out[i * ldo + c] = (mode == KGE_LP_DOT) ? acc : -acc;
+        float s = acc;
+        switch (mode) {
+        case KGE_LP_DOT: break;
+        case KGE_LP_TORUS_L1: s = lp_direct_finish<KGE_LP_TORUS_L1>(acc); break;
+        case KGE_LP_TORUS_L2: s = lp_direct_finish<KGE_LP_TORUS_L2>(acc); break;
+        case KGE_LP_TORUS_EL2: s = lp_direct_finish<KGE_LP_TORUS_EL2>(acc); break;
+        default: s = -acc;
+        }
+        if (lane == 0) out[i * ldo + c] = s;
     }
 }
 
@@ -1010,10 +1024,25 @@ extern "C" int kge_lp_pair_scores(const kge_lp_desc *d, const int64_t *qi, const
                d->N <= INT32_MAX) {        // plain L1 / L2 direct: staged rows, the ascending-k chain of lp_pair_score
         const int64_t groups = (P + 63) / 64;
         const int grid = (int)(groups < 256 * 14 ? groups : 256 * 14);
-        if (d->mode == KGE_LP_L1_DIRECT)
+        switch (d->mode) {      // (the torus modes: the same staging, their per-element terms -- kge_common.h)
+        case KGE_LP_L1_DIRECT:
             hipLaunchKernelGGL((pair_scores_staged_kernel<true, 1>), dim3(grid), dim3(64), 0, kge_s(stream), *d, qi, ci, P, out);
-        else
+            break;
+        case KGE_LP_TORUS_L1:
+            hipLaunchKernelGGL((pair_scores_staged_kernel<true, KGE_LP_TORUS_L1>), dim3(grid), dim3(64), 0, kge_s(stream), *d, qi,
+                               ci, P, out);
+            break;
+        case KGE_LP_TORUS_L2:
+            hipLaunchKernelGGL((pair_scores_staged_kernel<true, KGE_LP_TORUS_L2>), dim3(grid), dim3(64), 0, kge_s(stream), *d, qi,
+                               ci, P, out);
+            break;
+        case KGE_LP_TORUS_EL2:
+            hipLaunchKernelGGL((pair_scores_staged_kernel<true, KGE_LP_TORUS_EL2>), dim3(grid), dim3(64), 0, kge_s(stream), *d, qi,
+                               ci, P, out);
+            break;
+        default:
             hipLaunchKernelGGL((pair_scores_staged_kernel<true, 2>), dim3(grid), dim3(64), 0, kge_s(stream), *d, qi, ci, P, out);
+        }
     } else {
         hipLaunchKernelGGL(pair_scores_kernel, dim3(grid1d(P, 64)), dim3(64), 0, kge_s(stream), *d, qi, ci, P, out);
     }
@@ -1070,10 +1099,25 @@ static int fsub_score_and_count(const kge_lp_desc *d, const float *s_true, const
             else
                 hipLaunchKernelGGL((fsub_score_kernel<true, false>), dim3(grid), dim3(64), 0, st, *d, seg_lo, targets, woff, fs);
         } else if (!d->Wq && kge_lp_vec4(*d)) {   // plain L1 / L2 direct: the same cooperative row staging, ascending-k chain
-            if (d->mode == KGE_LP_L1_DIRECT)
+            switch (d->mode) {
+            case KGE_LP_L1_DIRECT:
                 hipLaunchKernelGGL((fsub_score_kernel<true, true, 1>), dim3(grid), dim3(64), 0, st, *d, seg_lo, targets, woff, fs);
-            else
+                break;
+            case KGE_LP_TORUS_L1:
+                hipLaunchKernelGGL((fsub_score_kernel<true, true, KGE_LP_TORUS_L1>), dim3(grid), dim3(64), 0, st, *d, seg_lo, targets,
+                                   woff, fs);
+                break;
+            case KGE_LP_TORUS_L2:
+                hipLaunchKernelGGL((fsub_score_kernel<true, true, KGE_LP_TORUS_L2>), dim3(grid), dim3(64), 0, st, *d, seg_lo, targets,
+                                   woff, fs);
+                break;
+            case KGE_LP_TORUS_EL2:
+                hipLaunchKernelGGL((fsub_score_kernel<true, true, KGE_LP_TORUS_EL2>), dim3(grid), dim3(64), 0, st, *d, seg_lo, targets,
+                                   woff, fs);
+                break;
+            default:
                 hipLaunchKernelGGL((fsub_score_kernel<true, true, 2>), dim3(grid), dim3(64), 0, st, *d, seg_lo, targets, woff, fs);
+            }
         } else {
             hipLaunchKernelGGL((fsub_score_kernel<false, false>), dim3(grid), dim3(64), 0, st, *d, seg_lo, targets, woff, fs);
         }
@@ -1165,7 +1209,9 @@ extern "C" int kge_lp_scores_batched(int mode, const float *q, int64_t ldq, cons
                                      int64_t stride_b, int64_t stride_n, int64_t B, int64_t N, int K,
                                      float *out, int64_t ldo, kge_stream_t stream)
 {
-    if (mode != KGE_LP_DOT && mode != KGE_LP_L1_DIRECT && mode != KGE_LP_L2_DIRECT) return KGE_EINVAL;
+    if (mode != KGE_LP_DOT && mode != KGE_LP_L1_DIRECT && mode != KGE_LP_L2_DIRECT && mode != KGE_LP_TORUS_L1 &&
+        mode != KGE_LP_TORUS_L2 && mode != KGE_LP_TORUS_EL2)
+        return KGE_EINVAL;
     if (B < 0 || N < 0 || K <= 0 || ldo < N) return KGE_EINVAL;
     if (B == 0 || N == 0) return 0;
     if (!q || !cand || !out) return KGE_EINVAL;

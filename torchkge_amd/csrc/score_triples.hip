@@ -117,6 +117,48 @@ template <> struct RowSet<KGE_DISTMULT> { static constexpr int NR = 3; };
 template <> struct RowSet<KGE_TRANSH> { static constexpr int NR = 4; };
 template <> struct RowSet<KGE_COMPLEX> { static constexpr int NR = 6; };
 template <> struct RowSet<KGE_TRANSD> { static constexpr int NR = 6; };
+template <> struct RowSet<KGE_TORUSE_L1> { static constexpr int NR = 3; };
+template <> struct RowSet<KGE_TORUSE_TORUS_L1> { static constexpr int NR = 3; };
+template <> struct RowSet<KGE_TORUSE_TORUS_L2> { static constexpr int NR = 3; };
+template <> struct RowSet<KGE_TORUSE_TORUS_EL2> { static constexpr int NR = 3; };
+
+// TorusE (translation.py:705-721): frac(x) = x - trunc(x) (torch.frac: exact in fp32, keeps the sign) of the gathered
+// rows, x = (h + r) - t, score = -diss(x) -- the per-element terms of the all-candidates modes (kge_common.h)
+__host__ __device__ inline constexpr bool is_toruse(int kind) { return kind >= KGE_TORUSE_L1 && kind <= KGE_TORUSE_TORUS_EL2; }
+__host__ __device__ inline constexpr int toruse_mode(int kind)
+{
+    return kind == KGE_TORUSE_TORUS_L1 ? KGE_LP_TORUS_L1 : kind == KGE_TORUSE_TORUS_L2 ? KGE_LP_TORUS_L2
+         : kind == KGE_TORUSE_TORUS_EL2 ? KGE_LP_TORUS_EL2 : KGE_LP_L1_DIRECT;
+}
+template <int NE>
+__device__ __forceinline__ void frac_inplace(float (&x)[NE])
+{
+#pragma unroll
+    for (int e = 0; e < NE; ++e) x[e] = x[e] - truncf(x[e]);
+}
+// d score / d x of one element (closed form of torch autograd through the reference's expressions): |x| -> sign(x); a
+// min() passes the gradient to the branch it took and, at an exact tie, half to each -- the two halves cancel here
+template <int MODE>
+__device__ __forceinline__ float toruse_dscore(float x, float go)
+{
+    const float sg = (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f);
+    if (MODE == KGE_LP_TORUS_L1) {          // -2 min(a, 1 - a), a = |x|
+        const float a = fabsf(x), b = 1.0f - a;
+        const float br = (a < b) ? 1.f : ((a > b) ? -1.f : 0.f);
+        return go * (-2.f * br * sg);
+    } else if (MODE == KGE_LP_TORUS_L2) {   // -4 min(v, 1 - v), v = x * x, dv/dx = 2x
+        const float v = x * x, b = 1.0f - v;
+        const float br = (v < b) ? 1.f : ((v > b) ? -1.f : 0.f);
+        return br * (go * (-8.f * x));
+    } else if (MODE == KGE_LP_TORUS_EL2) {  // -(1/4) 2 (1 - cos(2 pi u)), u = min(x, 1 - x)
+        const float b = 1.0f - x;
+        const float br = (x < b) ? 1.f : ((x > b) ? -1.f : 0.f);
+        const float u = fminf(x, b);
+        const float gu = (-(go * 0.5f) * sinf(KGE_TWO_PI_F * u)) * KGE_TWO_PI_F;
+        return br * gu;
+    }
+    return go * -sg;                        // 'L1': -|x|
+}
 
 template <int KIND, bool VEC4, int NE>
 __device__ __forceinline__ void gather_rows(const ScoreParams &p, int64_t hi, int64_t ti, int64_t ri, int lane,
@@ -161,6 +203,16 @@ __device__ __forceinline__ float score_rows(const ScoreParams &p, int lane, floa
         s = wave_sum_dpp(s);
         if (KIND == KGE_TRANSE_L2) { const float n = sqrtf(s); s = n * n; } // norm(p=2)**2
         return -s;
+    } else if (is_toruse(KIND)) {
+        constexpr int MODE = toruse_mode(KIND);
+        float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2];
+        frac_inplace<NE>(h);
+        frac_inplace<NE>(t);
+        frac_inplace<NE>(r);
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) s = s + lp_direct_term<MODE>((h[e] + r[e]) - t[e]);   // (padding: x = 0, term 0)
+        return lp_direct_finish<MODE>(wave_sum_dpp(s));
     } else if (KIND == KGE_DISTMULT) {
         float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2];
         normalize_inplace<NE, false>(h);
@@ -346,6 +398,32 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void score_bwd_kernel(const B
             normalize_bwd<NE>(h, nh, gh);
             normalize_bwd<NE>(t, nt, gt);
             KGE_EMIT(0, q.g0, hi, de, gh);
+            KGE_EMIT(1, q.g0, ti, de, gt);
+        } else if (is_toruse(p.kind)) {
+            // frac is applied to the gathered copies' .data: autograd sees the identity, so d/dh = d/dr = dscore/dx and
+            // d/dt = -dscore/dx with x = (frac h + frac r) - frac t
+            float h[NE], t[NE], r[NE], gd[NE], gt[NE];
+            load_row<VEC4, NE>(p.t0 + hi * de, de, lane, h);
+            load_row<VEC4, NE>(p.t0 + ti * de, de, lane, t);
+            load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, r);
+            frac_inplace<NE>(h);
+            frac_inplace<NE>(t);
+            frac_inplace<NE>(r);
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                const float x = (h[e] + r[e]) - t[e];
+                float g;
+                switch (p.kind) {
+                case KGE_TORUSE_TORUS_L1: g = toruse_dscore<KGE_LP_TORUS_L1>(x, go); break;
+                case KGE_TORUSE_TORUS_L2: g = toruse_dscore<KGE_LP_TORUS_L2>(x, go); break;
+                case KGE_TORUSE_TORUS_EL2: g = toruse_dscore<KGE_LP_TORUS_EL2>(x, go); break;
+                default: g = toruse_dscore<KGE_LP_L1_DIRECT>(x, go);
+                }
+                gd[e] = g;
+                gt[e] = -g;
+            }
+            KGE_EMIT(2, q.g1, ri, dr, gd);
+            KGE_EMIT(0, q.g0, hi, de, gd);
             KGE_EMIT(1, q.g0, ti, de, gt);
         } else if (p.kind == KGE_DISTMULT) {
             float h[NE], t[NE], r[NE], gh[NE], gt[NE], gr[NE];
@@ -604,7 +682,7 @@ int dispatch_ne(const P &p, int dmax, bool vec4, int64_t B, hipStream_t s, Kerne
 int check_common(int kind, const float *t0, const float *t1, const float *t2, const float *t3,
                  int d_ent, int d_rel, const int64_t *h, const int64_t *t, const int64_t *r, int64_t B)
 {
-    if (kind < KGE_TRANSE_L1 || kind > KGE_COMPLEX) return KGE_EINVAL;
+    if (kind < KGE_TRANSE_L1 || (kind > KGE_COMPLEX && !is_toruse(kind))) return KGE_EINVAL;
     if (!t0 || !t1 || d_ent <= 0 || d_rel <= 0 || B < 0) return KGE_EINVAL;
     if (B > 0 && (!h || !t || !r)) return KGE_EINVAL;
     if ((kind == KGE_TRANSH || kind == KGE_TRANSD || kind == KGE_COMPLEX) && !t2) return KGE_EINVAL;
@@ -653,6 +731,10 @@ extern "C" int kge_score_triples(int kind, const float *t0, const float *t1, con
             KGE_FWD_CASE(KGE_TRANSD)
             KGE_FWD_CASE(KGE_DISTMULT)
             KGE_FWD_CASE(KGE_COMPLEX)
+            KGE_FWD_CASE(KGE_TORUSE_L1)
+            KGE_FWD_CASE(KGE_TORUSE_TORUS_L1)
+            KGE_FWD_CASE(KGE_TORUSE_TORUS_L2)
+            KGE_FWD_CASE(KGE_TORUSE_TORUS_EL2)
         default: return KGE_EINVAL;
         }
 #undef KGE_FWD_CASE

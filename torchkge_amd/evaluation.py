@@ -862,6 +862,11 @@ class LinkPredictionEvaluator(object):
         # plan stamps, capture key, filter indices, guard / session bookkeeping -- is ~35 us of that.  Anything unusual
         # (a guard flag up, a list overflow, every 32nd evaluation's memory check) goes through the full path.
         user_b_size = b_size
+        # the model's own in-place step of the reference's evaluation (TorusE: frac if not normalized) -- BEFORE the replay
+        # check: the capture keys the tables by address and would not see it
+        prepare = getattr(self.model, 'lp_eval_prepare', None)
+        if prepare is not None:
+            prepare()
         fast = self._st._fast if FAST_REPLAY else None
         if fast is not None:
             if self._n_evaluations % 32 != 0 and fast[0] == self._fast_sig(user_b_size) and self._evaluate_fast(fast[1]):

@@ -89,6 +89,9 @@ class EntityInference(object):
         from .filter_index import filter_index_for
         dev = _device_of(self.model)
         model = self.model
+        prepare = getattr(model, 'lp_eval_prepare', None)   # (TorusE: frac if not normalized, as inference_prepare_candidates)
+        if prepare is not None:
+            prepare()
         impl = getattr(type(model), 'lp_problem', None)
         from .models.interfaces import Model as _BaseModel
         if impl is None or impl is _BaseModel.lp_problem:

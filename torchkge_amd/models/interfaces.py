@@ -18,7 +18,6 @@ import torch
 from torch.nn import Module
 
 from .. import _hip
-from ..exceptions import NotYetImplementedError
 
 
 class _ScoreTriples(torch.autograd.Function):
@@ -274,7 +273,7 @@ class Model(Module):
             P = _hip.LpProblem(mode, A0, rep[0], qn=qn, en=en, K0=K0)
         elif mode == _hip.LP_DOT:
             P = _hip.LpProblem(mode, A0, rep[0], A1=A1, T1=rep[1] if A1 is not None else None, K0=K0)
-        elif mode in (_hip.LP_L1_DIRECT, _hip.LP_L2_DIRECT):
+        elif mode in (_hip.LP_L1_DIRECT, _hip.LP_L2_DIRECT, _hip.LP_TORUS_L1, _hip.LP_TORUS_L2, _hip.LP_TORUS_EL2):
             P = _hip.LpProblem(mode, A0, rep[0], K0=K0)
         else:
             return None
@@ -435,6 +434,12 @@ class Model(Module):
         prob.pre = pre
         return prob
 
+    def lp_eval_prepare(self):
+        """Called by LinkPredictionEvaluator.evaluate / EntityInference.evaluate before anything else -- in particular
+        before a steady-state graph replay, which keys the tables by address and would skip an in-place change the
+        reference's evaluation makes through inference_prepare_candidates (TorusE: frac if not normalized).  No-op here."""
+        return None
+
     def lp_problem_both(self, h_idx, t_idx, r_idx):
         """Both sides of a batch as ONE problem of 2B queries (tail-side queries first)
         against the entity table: ``lp_problem(..., side='both')``.  Ranks are per
@@ -528,12 +533,10 @@ class TranslationModel(Model):
     def __init__(self, n_entities, n_relations, dissimilarity_type):
         super().__init__(n_entities, n_relations)
         assert dissimilarity_type in ['L1', 'L2', 'torus_L1', 'torus_L2', 'torus_eL2']
-        if dissimilarity_type not in ('L1', 'L2'):
-            raise NotYetImplementedError('torus dissimilarities (TorusE) are outside the MI355X '
-                                         'hot path (SURVEY.md section 2, row 5).')
         self.dissimilarity_type = dissimilarity_type
-        from ..utils.dissimilarities import l1_dissimilarity, l2_dissimilarity
-        self.dissimilarity = l1_dissimilarity if dissimilarity_type == 'L1' else l2_dissimilarity
+        from ..utils import dissimilarities as D
+        self.dissimilarity = {'L1': D.l1_dissimilarity, 'L2': D.l2_dissimilarity, 'torus_L1': D.l1_torus_dissimilarity,
+                              'torus_L2': D.l2_torus_dissimilarity, 'torus_eL2': D.el2_torus_dissimilarity}[dissimilarity_type]
         # 'expand': ||q-e||^2 = ||q||^2 + ||e||^2 - 2 q.e as an fp32 MFMA GEMM;
         # 'direct': broadcast-subtract on the VALU; 'auto': expand while the operands
         # are small enough for the cancellation error to stay inside the 1e-5 score
@@ -547,8 +550,12 @@ class TranslationModel(Model):
         state_dict.pop(prefix + 'projected_entities', None)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
+    _DIRECT_MODES = {'L1': _hip.LP_L1_DIRECT, 'L2': _hip.LP_L2_DIRECT, 'torus_L1': _hip.LP_TORUS_L1,
+                     'torus_L2': _hip.LP_TORUS_L2, 'torus_eL2': _hip.LP_TORUS_EL2}
+
     def _direct_mode(self):
-        return _hip.LP_L1_DIRECT if self.dissimilarity_type == 'L1' else _hip.LP_L2_DIRECT
+        """Broadcast-subtract mode of this dissimilarity (the torus ones have no norm expansion: they never leave it)."""
+        return self._DIRECT_MODES[self.dissimilarity_type]
 
     # measured: |expand - reference| ~ 2.4e-7 * (||q||^2 + ||e||^2) at d = 200 (1.2e-6 at 5)
     L2_EXPAND_LIMIT = 16.0

@@ -15,7 +15,7 @@ import torch
 from .. import _hip
 from ..exceptions import NotYetImplementedError
 from ..utils.modeling import init_embedding
-from .interfaces import TranslationModel, EntityCandidates, RelationProjections, _table_of
+from .interfaces import TranslationModel, EntityCandidates, RelationProjections, _table_of, _ScoreTriples
 
 
 def _projections(kind, tabs, d_ent, d_rel, h_idx, t_idx, r_idx):
@@ -178,6 +178,101 @@ class TransEModel(TranslationModel):
         prob.split = split
         prob.pre = pre
         return prob
+
+
+class TorusEModel(TranslationModel):
+    """TorusE (translation.py:655-767).  ``TorusEModel(emb_dim, n_entities, n_relations, dissimilarity_type)`` with type
+    'L1', 'torus_L1', 'torus_L2' or 'torus_eL2'; parameters ``ent_emb``, ``rel_emb``.
+
+    Embeddings live in (-1, 1) -- ``normalize_parameters`` is ``frac_`` (x - trunc(x), the sign kept).  The torus
+    dissimilarities have no GEMM form: every all-candidates problem is a broadcast-subtract one on the VALU
+    (KGE_LP_TORUS_L1 / _L2 / _EL2; 'L1' is KGE_LP_L1_DIRECT), and the reference's (b, N, d) candidate broadcast is never
+    built.  Relation prediction scores -diss(h + r_c, t) over the relation table (the reference raises AttributeError
+    there, translation.py:765)."""
+
+    _ENT_TABLES = ('ent_emb',)
+    _SCORE_KIND = {'L1': _hip.TORUSE_L1, 'torus_L1': _hip.TORUSE_TORUS_L1, 'torus_L2': _hip.TORUSE_TORUS_L2,
+                   'torus_eL2': _hip.TORUSE_TORUS_EL2}
+
+    def __init__(self, emb_dim, n_entities, n_relations, dissimilarity_type):
+        assert dissimilarity_type in ['L1', 'torus_L1', 'torus_L2', 'torus_eL2']
+        super().__init__(n_entities, n_relations, dissimilarity_type)
+        self.emb_dim = emb_dim
+        self.ent_emb = init_embedding(self.n_ent, self.emb_dim)
+        self.rel_emb = init_embedding(self.n_rel, self.emb_dim)
+        self.normalized = False
+        # translation.py:701-702: normalize_parameters() on the freshly initialised (host) tables
+        self.ent_emb.weight.data.frac_()
+        self.rel_emb.weight.data.frac_()
+        self.normalized = True
+
+    def _tables(self):
+        return [self.ent_emb.weight, self.rel_emb.weight]
+
+    def _hip_kind(self):
+        # the query rows of every all-candidates problem are TransE's: E[h] + R[r] | E[t] - R[r] (kge_lp_prep)
+        return _hip.TRANSE_L1
+
+    def scoring_function(self, h_idx, t_idx, r_idx):
+        """-diss(frac(h) + frac(r), frac(t)) of the gathered rows (translation.py:705-721), one fused HIP kernel; the
+        tables are not changed, and autograd sees frac as the identity (the reference applies it to ``.data``)."""
+        object.__setattr__(self, 'normalized', False)
+        self._check_unsharded('scoring_function')
+        tables = self._tables()
+        _hip.require_cuda(h_idx, t_idx, r_idx, *tables)
+        return _ScoreTriples.apply(self._SCORE_KIND[self.dissimilarity_type], self.emb_dim, self.emb_dim, h_idx, t_idx,
+                                   r_idx, *tables)
+
+    def normalize_parameters(self):
+        """Project the embeddings on the torus: frac_ of both tables in place (translation.py:723-728, kge_frac_rows)."""
+        for emb in (self.ent_emb, self.rel_emb):
+            w = emb.weight.data
+            _hip.require_cuda(w)
+            if not w.is_contiguous():
+                w = w.contiguous()
+                emb.weight.data = w
+            _hip.frac_rows_(w)
+        object.__setattr__(self, 'normalized', True)
+
+    def lp_eval_prepare(self):
+        """The reference's evaluation calls inference_prepare_candidates, which frac's the tables when
+        scoring_function ran since the last normalisation (translation.py:752-753)."""
+        if not self.normalized:
+            self.normalize_parameters()
+
+    def get_embeddings(self):
+        self.normalize_parameters()
+        return self.ent_emb.weight.data, self.rel_emb.weight.data
+
+    def inference_prepare_candidates(self, h_idx, t_idx, r_idx, entities=True):
+        """(h, t, r, candidates) (translation.py:742-767), after the in-place frac if the tables are not normalized.
+        Entity candidates are an EntityCandidates handle, not a (b, N, d) tensor; relation candidates are the
+        stride-0 (b, n_rel, d) view of the relation table."""
+        self._check_unsharded('inference_prepare_candidates')
+        if not self.normalized:
+            self.normalize_parameters()
+        b_size = max(h_idx.shape[0], t_idx.shape[0], r_idx.shape[0])   # inference passes one empty index
+        E, R = self.ent_emb.weight.data, self.rel_emb.weight.data
+        h, t, r = _hip.gather_rows(E, h_idx), _hip.gather_rows(E, t_idx), _hip.gather_rows(R, r_idx)
+        if entities:
+            candidates = EntityCandidates(self, _hip.i64c(r_idx), b_size)
+        else:
+            candidates = R.view(1, self.n_rel, self.emb_dim).expand(b_size, self.n_rel, self.emb_dim)
+        return h, t, r, candidates
+
+    def _handle_problem(self, q, cand, ent_lo=0, ent_hi=None):
+        ent_hi = self.n_ent if ent_hi is None else ent_hi
+        E = _hip.f32c(self.ent_emb.weight.data)
+        return self._translational_problem(q, self._cand_rows(E, ent_lo, ent_hi), c_base=ent_lo)
+
+    def lp_problem(self, h_idx, t_idx, r_idx, side, ent_lo=0, ent_hi=None, exchange=None, qtabs=None, cols=None):
+        """s[i, c] = -diss(q_i - e_c) with q = h + r (tail side) / t - r (head side) for the entities [ent_lo, ent_hi):
+        one broadcast-subtract problem (row-sharded tables: ``exchange`` / ``qtabs`` as TransE)."""
+        ent_lo, ent_hi = _ent_range(self, ent_lo, ent_hi)
+        tabs = [x.data for x in self._tables()]
+        sd = _hip.side_code(side)
+        Q0, _, _, _ = self._lp_prep(sd, h_idx, t_idx, r_idx, exchange, qtabs=qtabs)
+        return self._translational_problem(Q0, self._cand_rows(_hip.f32c(tabs[0]), ent_lo, ent_hi), c_base=ent_lo)
 
 
 def _both_r(r_idx, sd, hint=None):
