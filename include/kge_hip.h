@@ -54,6 +54,14 @@
  *                                  M_r.t (bilinear.py:98-114, :365-381) that a KGE_LP_DOT problem then scores
  *   kge_bilinear_relation_rows   RESCAL / HolE relation candidates (bilinear.py:115-121, :382-389)
  *   kge_rescal_rel_grad          autograd of RESCAL's scoring_function wrt rel_mat (bilinear.py:60-71)
+ *   kge_transr_proj_sqnorm       TransRModel.evaluate_projectionss (translation.py:432-458): all the (n_rel, n_ent, d_r)
+ *                                  cache is needed for is || M_r e_c ||^2, one float per (relation, entity); with
+ *                                  x = e_h - e_t and b = rel_emb also the relation candidates of :405-430 scored as
+ *                                  interfaces.py:261-272
+ *   kge_transr_query             TransRModel.inference_prepare_candidates / inference_scoring_function on entity
+ *                                  candidates (translation.py:405-430, interfaces.py:240-260): q = M_r e +- r and
+ *                                  u = M_r^T q, which a KGE_LP_L2_PROJH problem then scores
+ *   kge_transr_rel_grad          autograd of TransR's scoring_function (translation.py:345-366) wrt proj_mat
  */
 #ifndef KGE_HIP_H
 #define KGE_HIP_H
@@ -86,7 +94,10 @@ enum {
     KGE_TORUSE_L1 = 8,          /* 'L1':        sum |x|                                                      */
     KGE_TORUSE_TORUS_L1 = 9,    /* 'torus_L1':  2 sum min(|x|, 1 - |x|)                                      */
     KGE_TORUSE_TORUS_L2 = 10,   /* 'torus_L2':  4 sum min(x*x, 1 - x*x)                                      */
-    KGE_TORUSE_TORUS_EL2 = 11   /* 'torus_eL2': sum (1 - cos(2 pi min(x, 1 - x))) / 2                        */
+    KGE_TORUSE_TORUS_EL2 = 11,  /* 'torus_eL2': sum (1 - cos(2 pi min(x, 1 - x))) / 2                        */
+    /* TransR (translation.py:287-458), tables {E, R, proj_mat}, d_ent = d_e, d_rel = d_r, proj_mat (n_rel, d_r * d_e) with
+     * M_r[c][k] = row[c*d_e + k]; kge_score_triples / _bwd only (additive: the ABI stays 33) */
+    KGE_TRANSR = 12
 };
 
 /* which entity is replaced by the candidates */
@@ -137,6 +148,11 @@ enum {
  *                  v = fmaf(y, fmaf(y, z_i, fmaf(2, g, p_i)), v); s = -fmaxf(v, 0)
  *                  (TransD candidates e'_c + y_c w_i, g = e'_c.w_{r_i}: p_i = -2 u_i.w_i, z_i = ||w_i||^2)
  *                  with (p_i, z_i) = Wq[i*ldw + {0,1}] and X[r, c] = scal[r*scal_ld + c]
+ *                  TransR uses L2_PROJH too: || q_i - M_r e_c ||^2 = ||q_i||^2 - 2 u_i.e_c + Z[r_i, c] with q_i = M_r e +- r,
+ *                  u_i = M_r^T q_i (kge_transr_query) and Z[r, c] = || M_r e_c ||^2 (kge_transr_proj_sqnorm): A0 = u,
+ *                  T0 = the raw entity rows, qn = ||q_i||^2, en = a ZERO vector, (p_i, z_i) = (1, 0), X = Z, so that the
+ *                  epilogue adds x = Z[r_i, c] and nothing else (Z is not reduced by ||e_c||^2: no term of that size
+ *                  enters the sum only to cancel).
  *     L1/L2_DIRECT: diff_k = A0[i,k] - T0[c,k]; if Wq: diff_k = fmaf(a, Wq[i,k], diff_k)
  *                   with a = scal[c*scal_ld + (scal_ld > 1 ? r_idx[i] : 0)];
  *                   L2: acc = fmaf(diff_k, diff_k, acc), k ascending;
@@ -180,7 +196,7 @@ typedef struct kge_lp_desc {
 
 /* ---- K1: fused gather + normalise + score (scoring_function) ------------- */
 /* tables: TransE/DistMult {E,R}; TransH {E,R,W}; TransD {E,R,Ep,Rp}; ComplEx {Ere,Eim,Rre,Rim};
- * RESCAL {E,rel_mat}; HolE {E,R}; TorusE (KGE_TORUSE_*) {E,R}.
+ * RESCAL {E,rel_mat}; HolE {E,R}; TorusE (KGE_TORUSE_*) {E,R}; TransR {E,R,proj_mat}.
  * d_ent = row length of entity tables, d_rel = row length of relation tables
  * (equal except TransD, which needs d_ent >= d_rel, and RESCAL, d_rel = d_ent^2).  Tables are contiguous.
  * RESCAL / HolE (ABI 33, bilinear.py:60-71, :311-323): score = h^ . B_r . t^ with B_r = M_r = rel_mat[r] viewed (d, d)
@@ -201,6 +217,8 @@ int kge_score_triples(int kind, const float *t0, const float *t1, const float *t
  *     HolE:    0 (g0,h) 1 (g0,t) 2 (g1,r)
  *     TorusE:  0 (g0,h) 1 (g0,t) 2 (g1,r)   (closed form: d|x| = sign(x), the taken branch of each min, 0 at an exact tie)
  *     RESCAL:  0 (g0,h) 1 (g0,t), and the operands of kge_rescal_rel_grad: 2 U_i = go_i h^_i, 3 V_i = t^_i
+ *     TransR:  0 (g0,h) 1 (g0,t) 2 (g1,r), which is also U_i = g_i = -2 go_i p_i of kge_transr_rel_grad, 3 V_i = h^_i - t^_i
+ *              (rows_ld >= max(d_ent, d_rel); row mode only, as RESCAL: d proj_mat is d_r * d_e wide per triple)
  *   and the caller reduces them per target table with kge_segment_sum_rows.
  * RESCAL needs the row mode (rows != NULL, g0..g3 unused): its rel_mat gradient is d^2 wide per triple and is never
  * scattered per triple; kge_rescal_rel_grad reduces it per relation. */
@@ -303,6 +321,36 @@ int kge_bilinear_relation_rows(int kind, const float *H, int64_t ldh, const floa
  * without triples get zeros): no atomics, no B x d^2 scratch, the same bits on every run. */
 int kge_rescal_rel_grad(const float *U, const float *V, int64_t ld, int d, const int64_t *r, const int64_t *perm,
                         int64_t B, int64_t n_rel, float *gM, int64_t ldg, kge_stream_t stream);
+
+/* ---- TransR (ABI 33, additive): kind KGE_TRANSR and three exports; 1 <= d_e, d_r <= 512 (any alignment), outside that
+ * KGE_EUNSUPPORTED.  kge_score_triples: x^ = x / max(||x||, 1e-12) of the gathered h, t rows, v = h^ - t^,
+ * p_c = chain_k M_r[c][k] v_k (k ascending) + R[r][c], score = -sum_c p_c^2.
+ *
+ * Projected squared norms, nothing of the (rows, d_r) projection is stored:
+ *   out[rel*os_r + j*os_j] = || M_rel X[j] + b[rel] ||^2    for j in [0, n) and rel = rels[y] (rels NULL: y), y in [0, n_list)
+ * on v_mfma_f32_32x32x2_f32 (exact fp32).  Order: p_c = chain(M_rel[c], X[j], d_e) -- the `chain` of kge_lp_desc -- then
+ * p_c += b[rel*ldb + c] when b is given, and out = fmaf(p_c, p_c, out) over ASCENDING c from 0.  The result depends on
+ * (rel, X[j]) only: not on n, on the position of the row or on the list.  b NULL: no bias.  n_list <= 65535.
+ * Callers: the Z table of an evaluation (X = the local entity rows, out the (n_rel, N padded) buffer of KGE_LP_L2_PROJH,
+ * os_r = its row length, os_j = 1) and relation prediction (X = E[h] - E[t], b = rel_emb, out (B, n_rel): os_r = 1,
+ * os_j = n_rel; score = -out). */
+int kge_transr_proj_sqnorm(const float *M, int64_t ldm, const float *X, int64_t ldx, const float *b, int64_t ldb,
+                           const int64_t *rels, int64_t n_list, int64_t n, int d_e, int d_r, float *out, int64_t os_r,
+                           int64_t os_j, kge_stream_t stream);
+/* Query rows of TransR: Q[i][c] = fmaf(s, R[r][c], chain_k M_r[c][k] x[k]) with s = +1 (tail side, x = the head's row) or
+ * -1 (head side, x = the tail's row), and -- U not NULL -- U[i][k] = chain_c Q[i][c] M_r[c][k]; both chains in ascending
+ * index, one accumulator per output: a row depends on (entity row, relation, side) only.  h, t not NULL: x = X[h[f]] /
+ * X[t[f]] (X = the entity table or replicas of its rows); h = t = NULL: x = X[i], the gathered rows in output order (what a
+ * row-sharded table delivers after zero-fill + all-reduce).  R NULL: no relation term.  X NULL: Q is an INPUT (queries already in relation space) and only U is
+ * written.  Sides and perm as kge_bilinear_query. */
+int kge_transr_query(int side, const float *X, int64_t ldx, const float *M, int64_t ldm, const float *R, int64_t ldr,
+                     int d_e, int d_r, const int64_t *h, const int64_t *t, const int64_t *r, int64_t B,
+                     const int64_t *perm, float *Q, int64_t ldq, float *U, int64_t ldu, kge_stream_t stream);
+/* Gradient of TransR's scoring_function wrt proj_mat, reduced per relation as kge_rescal_rel_grad, rectangular:
+ *   gM[rho*ldg + a*d_e + b] = chain over the triples i of rho, in the order of perm, of U[i][a] * V[i][b]   (a < d_r, b < d_e)
+ * with U / V the row streams 2 / 3 of kge_score_triples_bwd.  Blocks WRITE their outputs: no atomics, the same bits on every run. */
+int kge_transr_rel_grad(const float *U, int64_t ldu, const float *V, int64_t ldv, int d_r, int d_e, const int64_t *r,
+                        const int64_t *perm, int64_t B, int64_t n_rel, float *gM, int64_t ldg, kge_stream_t stream);
 
 /* Per-query scalars of the projection modes (KGE_LP_L2_PROJH / _PROJD) in ONE launch: qn[i] = ||Q[i]||^2 and
  * pz[i] = (scale * (Q[i] . W[r_idx[i]]), ||W[r_idx[i]]||^2 + z_add) -- kge_lp_desc.Wq of those modes (TransH: scale 2,

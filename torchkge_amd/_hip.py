@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libkge_hip.so')
 # enums of include/kge_hip.h
 TRANSE_L1, TRANSE_L2, TRANSH, TRANSD, DISTMULT, COMPLEX, RESCAL, HOLE = range(8)
 TORUSE_L1, TORUSE_TORUS_L1, TORUSE_TORUS_L2, TORUSE_TORUS_EL2 = range(8, 12)
+TRANSR = 12
 SIDE_TAIL, SIDE_HEAD, SIDE_PROJ_H, SIDE_PROJ_T, SIDE_BOTH = range(5)
 EW_ADD, EW_SUB, EW_MUL, EW_MULSUB, EW_MULADD = range(5)
 LP_DOT, LP_L2_EXPAND, LP_L1_DIRECT, LP_L2_DIRECT, LP_L2_PROJH, LP_L2_PROJD = range(6)
@@ -149,6 +150,10 @@ _SIGNATURES = {
     'kge_bilinear_query': [_int, _int, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
     'kge_bilinear_relation_rows': [_int, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp],
     'kge_rescal_rel_grad': [_vp, _vp, _i64, _int, _vp, _vp, _i64, _i64, _vp, _i64, _vp],
+    'kge_transr_proj_sqnorm': [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _i64, _i64, _vp],
+    'kge_transr_query': [_int, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64,
+                         _vp],
+    'kge_transr_rel_grad': [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, _i64, _vp, _i64, _vp],
 }
 # every symbol include/kge_hip.h declares
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ['kge_corrupt_ws_elems', 'kge_abi_version', 'kge_lp_split_rows_padded',
@@ -328,6 +333,8 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
     dev = h.device
     if kind == RESCAL:
         return _rescal_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
+    if kind == TRANSR:
+        return _transr_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
     # (TorusE: always the row mode -- no per-element float atomics; a batch whose rows fit one 32-entry chunk per stream
     # of kge_segment_sum_rows gets the same bits on every run)
     if B < BWD_SORTED_MIN_BATCH and kind < TORUSE_L1:
@@ -416,6 +423,88 @@ def _rescal_bwd(tabs, d, d_rel, h, t, r, go, grads, needs):
     return [g if n else None for g, n in zip(grads[:2], needs)]
 
 
+def _transr_bwd(tabs, d_e, d_r, h, t, r, go, grads, needs):
+    """TransR's backward: entity and rel_emb gradients through the row mode + kge_segment_sum_rows, proj_mat's by the
+    relation-grouped reduction kge_transr_rel_grad (sorted by relation: no atomics on proj_mat, the same bits on every
+    run)."""
+    lib = load_library()
+    B, dev = h.shape[0], h.device
+    ld = max(d_e, d_r)
+    rows = torch.empty(4 * B * ld, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _check(lib.kge_score_triples_bwd(TRANSR, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), None, d_e, d_r, _p(h), _p(t), _p(r), B,
+                                         _p(go), None, None, None, None, _p(rows), ld, _stream()), 'kge_score_triples_bwd')
+        if needs[0]:
+            g = grads[0]
+            perm = _key_perm(h, t, g.shape[0])
+            _check(lib.kge_segment_sum_rows(_p(rows), ld, d_e, _p(h), B, _p(t), B, _p(perm), _p(g), g.stride(0), _stream()),
+                   'kge_segment_sum_rows')
+        if needs[1] or needs[2]:
+            perm = _key_perm(r, None, grads[1].shape[0])
+            gp, vp = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
+            if needs[1]:
+                g = grads[1]
+                _check(lib.kge_segment_sum_rows(gp, ld, d_r, _p(r), B, None, 0, _p(perm), _p(g), g.stride(0), _stream()),
+                       'kge_segment_sum_rows')
+            if needs[2]:
+                g = grads[2]
+                _check(lib.kge_transr_rel_grad(gp, ld, vp, ld, d_r, d_e, _p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
+                                               _stream()), 'kge_transr_rel_grad')
+    return [g if n else None for g, n in zip(grads[:3], needs)]
+
+
+def transr_proj_sqnorm(M, X, d_e, d_r, b=None, out=None, by_row=False, rels=None):
+    """kge_transr_proj_sqnorm: || M_r X[j] + b[r] ||^2 for every relation r (or those of ``rels``) and row j of X.
+    out (n_rel, >= n) given: written there (the Z table of an evaluation); by_row: a fresh (n, n_rel) matrix (relation
+    prediction); else a fresh (n_rel, n) one."""
+    lib = load_library()
+    require_cuda(M, X, b, out, rels)
+    M, X = f32c(M), f32c(X)
+    b = None if b is None else f32c(b)
+    n, n_rel = X.shape[0], M.shape[0]
+    if out is None:
+        out = torch.zeros((n, n_rel) if by_row else (n_rel, n), dtype=torch.float32, device=X.device)
+    os_r, os_j = (out.stride(1), out.stride(0)) if by_row else (out.stride(0), out.stride(1))
+    rels = None if rels is None else i64c(rels)
+    n_list = n_rel if rels is None else rels.shape[0]
+    if n and n_list:
+        with _on(X.device):
+            _check(lib.kge_transr_proj_sqnorm(_p(M), M.stride(0), _p(X), X.stride(0), _p(b), 0 if b is None else b.stride(0),
+                                              _p(rels), n_list, n, d_e, d_r, _p(out), os_r, os_j, _stream()),
+                   'kge_transr_proj_sqnorm')
+    return out
+
+
+def transr_query(side, X, M, R, d_e, d_r, h, t, r, want_u=True, sort=True, Q=None):
+    """kge_transr_query: (Q, U) -- Q (rows, d_r) = M_r x +- R[r], U (rows, d_e) = M_r^T Q (None without want_u); rows = B or,
+    side 'both', 2B.  h / t index X; both None: X holds the gathered rows in output order.  sort: rows visited in relation
+    order (kge_key_sort), which does not change a value."""
+    lib = load_library()
+    require_cuda(X, M, R, h, t, r, Q)
+    M = f32c(M)
+    X = None if X is None else f32c(X)
+    R = None if R is None else f32c(R)
+    r = i64c(r)
+    h = None if h is None else i64c(h)
+    t = None if t is None else i64c(t)
+    B = r.shape[0]
+    rows = 2 * B if side == SIDE_BOTH else B
+    if X is None:       # Q given (queries already in relation space): only U = M_r^T Q
+        Q = f32c(Q)
+        assert want_u and Q.shape == (rows, d_r)
+    else:
+        Q = torch.empty(rows, d_r, dtype=torch.float32, device=M.device)
+    U = torch.empty(rows, d_e, dtype=torch.float32, device=M.device) if want_u else None
+    if rows == 0:
+        return Q, U
+    with _on(M.device):
+        perm = _key_perm(r, r if side == SIDE_BOTH else None, max(M.shape[0], 1)) if sort else None
+        _check(lib.kge_transr_query(side, _p(X), 0 if X is None else X.stride(0), _p(M), M.stride(0), _p(R), 0 if R is None else R.stride(0),
+                                    d_e, d_r, _p(h), _p(t), _p(r), B, _p(perm), _p(Q), Q.stride(0), _p(U),
+                                    0 if U is None else U.stride(0), _stream()), 'kge_transr_query')
+    return Q, U
+
+
 def bilinear_query(kind, side, X, Rt, h, t, r, ent_lo=0, ent_n=-1, sort=True):
     """kge_bilinear_query: the (B, d) -- side 'both': (2B, d) -- query rows of RESCAL / HolE, x . B_r (tail side) or
     x . B_r^T (head side), rows taken from X by h / t.  sort: order the rows by relation first (kge_key_sort of [r] or
@@ -467,6 +556,10 @@ def lp_prep(kind, side, tables, d_ent, d_rel, h, t, r, want_qn=False, want_w=Fal
         assert not (want_qn or want_w or want_q1 or want_hi)
         return bilinear_query(kind, side, tables[0], tables[1], h, t, r, ent_lo=ent_lo if ent_n >= 0 else 0,
                               ent_n=ent_n), None, None, None
+    if kind == TRANSR:      # the projected rows M_r e of the named side (no relation term); whole tables only
+        assert side in (SIDE_PROJ_H, SIDE_PROJ_T) and ent_n < 0 and not (want_qn or want_q1 or want_hi)
+        e = h if side == SIDE_PROJ_H else t
+        return transr_query(SIDE_TAIL, tables[0], tables[2], None, d_ent, d_rel, e, e, r, want_u=False)[0], None, None, None
     lib = load_library()
     require_cuda(h, t, r, *tables)
     tabs = [f32c(x) for x in tables] + [None] * (4 - len(tables))

@@ -16,7 +16,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfma.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip',
-           'lp_l1_sad.hip', 'rank_filter.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip']
+           'lp_l1_sad.hip', 'rank_filter.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip',
+           'transr_xform.hip']
 HEADERS = ['kge_common.h', os.path.join('..', '..', 'include', 'kge_hip.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
@@ -44,7 +45,9 @@ _NO_SLP = ['-fno-slp-vectorize', '-DKGE_BUILD_NO_SLP=1']
 # bilinear_xform.hip (RESCAL / HolE query transform, fmaf chains): no packed f32 either -- the same lane-crossing
 # op_sel form would be the vectoriser's to emit there (tests/test_rescal_hole_host.py checks its ISA)
 EXTRA_FLAGS = {'lp_direct.hip': ['-fno-slp-vectorize'], 'lp_hi_stream.hip': _NO_SLP, 'lp_hi_chunk.hip': _NO_SLP,
-               'lp_split_mfma.hip': _NO_SLP, 'bilinear_xform.hip': ['-fno-slp-vectorize']}
+               'lp_split_mfma.hip': _NO_SLP, 'bilinear_xform.hip': ['-fno-slp-vectorize'],
+               # transr_xform.hip (TransR: MFMA squared norms with a VALU epilogue beside other waves' MFMAs, fmaf chains): the same
+               'transr_xform.hip': ['-fno-slp-vectorize']}
 
 
 def _hipcc():

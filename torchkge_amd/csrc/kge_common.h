@@ -25,6 +25,13 @@ int kge_bilinear_score_bwd(int kind, const float *t0, const float *t1, int d_ent
                            const int64_t *t, const int64_t *r, int64_t B, const float *go, float *g0, float *g1,
                            float *rows, int64_t rows_ld, hipStream_t s);
 
+// KGE_TRANSR behind kge_score_triples / kge_score_triples_bwd (transr_xform.hip)
+int kge_transr_score_fwd(const float *E, const float *R, const float *M, int d_ent, int d_rel, const int64_t *h,
+                         const int64_t *t, const int64_t *r, int64_t B, float *out, hipStream_t s);
+int kge_transr_score_bwd(const float *E, const float *R, const float *M, int d_ent, int d_rel, const int64_t *h,
+                         const int64_t *t, const int64_t *r, int64_t B, const float *go, float *rows, int64_t rows_ld,
+                         hipStream_t s);
+
 static inline bool kge_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Running maximum in a device scalar (non-negative floats compared as bit patterns).  Same-address atomics

@@ -1,12 +1,13 @@
 # -*- coding: utf-8 -*-
-"""TransE / TransH / TransD with the reference's constructors, attributes and
-state_dict keys (torchkge/models/translation.py:18-652) on the HIP engine.
+"""TransE / TransH / TransR / TransD / TorusE with the reference's constructors, attributes and
+state_dict keys (torchkge/models/translation.py:18-767) on the HIP engine.
 
 TransH / TransD never build the reference's (n_rel, n_ent, d) projection cache
 (`projected_entities`, filled by an n_ent-iteration Python loop,
 translation.py:260-284 / :629-652): one scalar per (entity, relation) [TransH:
 a = E.W^T] or per entity [TransD: s = Ep.E] is enough, and the rank-1
-correction is applied inside the all-candidates kernel.
+correction is applied inside the all-candidates kernel.  TransR (:432-458)
+likewise: Z[r, c] = ||M_r e_c||^2 is all its cache is needed for.
 """
 import os
 
@@ -554,3 +555,257 @@ class TransDModel(TranslationModel):
         prob = self._problem(Q0, Wq, ent_lo, ent_hi, r_idx=r_both)
         prob.cols = cols if (sd == _hip.SIDE_BOTH and prob.split is not None) else None
         return prob
+
+
+class _RelationGroupedProblem(object):
+    """TransR's exact all-candidates problem: for every relation rho among the queries, P_rho = E M_rho^T (one KGE_LP_DOT
+    problem, (N, d_r)) and then KGE_LP_L2_DIRECT of rho's queries against P_rho -- the reference's
+    -||q - M_rho e_c||^2 without any cancellation.  One P_rho exists at a time; nothing of (n_rel, N, d_r) is kept.  It
+    answers what the evaluators ask of an LpProblem.  Building it reads the batch's relations on the host (one sync)."""
+
+    split = sad = pre = cols = pre_q = region_count = zero_counts = None
+
+    def __init__(self, Q, r_q, table, M, d_e, d_r, c_base):
+        self.Q, self.table, self.c_base = Q, table, c_base
+        self.M3 = M.view(M.shape[0], d_r, d_e)
+        self.B, self.N, self.device = Q.shape[0], table.shape[0], Q.device
+        if Q.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('torchkge_amd: TransR\'s exact relation-grouped path reads the batch\'s relations on the host '
+                               'and cannot be captured into a graph: evaluate with graph=False when l2_mode is not \'auto\'')
+        rels, inv = torch.unique(r_q, return_inverse=True)
+        order = _hip.sort_perm(inv, max(int(rels.shape[0]), 1)) if Q.shape[0] else inv
+        counts = torch.bincount(inv, minlength=rels.shape[0]).tolist()
+        self.groups, lo = [], 0
+        for rho, n in zip(rels.tolist(), counts):
+            self.groups.append((rho, order[lo:lo + n]))
+            lo += n
+
+    def _each(self, q0=None, q1=None):
+        """(query positions, KGE_LP_L2_DIRECT problem) per relation present; q0 / q1: only the queries of that range."""
+        for rho, idx in self.groups:
+            if q0 is not None:
+                idx = idx[(idx >= q0) & (idx < q1)]
+            if idx.shape[0] == 0 or self.N == 0:
+                continue
+            P = _hip.LpProblem(_hip.LP_DOT, self.table, _hip.f32c(self.M3[rho])).scores()
+            yield idx, _hip.LpProblem(_hip.LP_L2_DIRECT, _hip.gather_rows(self.Q, idx), P, c_base=self.c_base)
+
+    def scores(self, out=None):
+        if out is None:
+            out = torch.empty(self.B, self.N, dtype=torch.float32, device=self.device)
+        for idx, prob in self._each():
+            out[idx] = prob.scores()
+        return out
+
+    def scores_chunk(self, c0, c1, out):
+        for idx, prob in self._each():
+            tmp = torch.empty(idx.shape[0], c1 - c0, dtype=torch.float32, device=self.device)
+            out[idx, :c1 - c0] = prob.scores_chunk(c0, c1, tmp)
+        return out
+
+    def scores_rows(self, q0, q1, out):
+        for idx, prob in self._each(q0, q1):
+            out[idx - q0, :self.N] = prob.scores()
+        return out
+
+    def pair_scores(self, ci, qi=None):
+        ci = _hip.i64c(ci)
+        out = torch.zeros(ci.shape[0], dtype=torch.float32, device=self.device)
+        if qi is None:
+            for idx, prob in self._each():
+                out[idx] = prob.pair_scores(ci[idx])
+            return out
+        qi = _hip.i64c(qi)
+        pos_of = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        for idx, prob in self._each():      # the pairs whose query belongs to this relation, re-indexed into its sub-problem
+            member = torch.zeros(self.B, dtype=torch.bool, device=self.device)
+            member[idx] = True
+            pos_of[idx] = torch.arange(idx.shape[0], device=self.device)
+            sel = member[qi].nonzero().view(-1)
+            if sel.shape[0]:
+                out[sel] = prob.pair_scores(ci[sel], pos_of[qi[sel]])
+        return out
+
+    def count_ge(self, s_true, raw=None):
+        if raw is None:
+            raw = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        for idx, prob in self._each():
+            raw[idx] += prob.count_ge(s_true[idx].contiguous())
+        return raw
+
+    def filter_sub(self, s_true, true_idx, seg_lo, seg_hi, targets, sub=None, found=None, grouped=False, plan=None):
+        if sub is None:
+            sub = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        if found is None:
+            found = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        for idx, prob in self._each():
+            s, f = prob.filter_sub(s_true[idx].contiguous(), true_idx[idx].contiguous(), seg_lo[idx].contiguous(),
+                                   seg_hi[idx].contiguous(), targets)
+            sub[idx] = s
+            found[idx] = f
+        return sub, found
+
+
+class TransRModel(TranslationModel):
+    """TransR (translation.py:287-458).  ``TransRModel(ent_emb_dim, rel_emb_dim, n_entities, n_relations)``; parameters
+    ``ent_emb``, ``rel_emb``, ``proj_mat`` (n_rel, rel_emb_dim * ent_emb_dim).
+
+    The reference's (n_rel, n_ent, rel_emb_dim) ``projected_entities`` cache is never built: with q = M_r e +- r and
+    u = M_r^T q,  ||q - M_r e_c||^2 = ||q||^2 - 2 u.e_c + Z[r, c]  and  Z[r, c] = ||M_r e_c||^2  is one float per
+    (relation, entity) (kge_transr_proj_sqnorm) -- a KGE_LP_L2_PROJH problem against the RAW entity table.  The rank counts
+    run on the fp32 MFMA path: the f16 split prefilter is not attached (``prob.split`` stays None), because its certified
+    band bounds |A0.T0| by sqrt(qn) max||e||, which does not hold for A0 = u.  Beyond ``L2_EXPAND_LIMIT`` (measured on
+    max ||q||^2 + max Z) the exact relation-grouped path takes over (_RelationGroupedProblem); ``lp_last_path`` names
+    the path the last problem took ('expand' or 'exact')."""
+
+    _kind = _hip.TRANSR
+    _ENT_TABLES = ('ent_emb',)
+    lp_sort_queries_by_relation = True     # (the epilogue gathers Z[r_i, c]: queries in relation order share those rows)
+    lp_last_path = None
+
+    def __init__(self, ent_emb_dim, rel_emb_dim, n_entities, n_relations):
+        super().__init__(n_entities, n_relations, 'L2')
+        self.ent_emb_dim = ent_emb_dim
+        self.rel_emb_dim = rel_emb_dim
+        self.ent_emb = init_embedding(self.n_ent, self.ent_emb_dim)
+        self.rel_emb = init_embedding(self.n_rel, self.rel_emb_dim)
+        self.proj_mat = init_embedding(self.n_rel, self.rel_emb_dim * self.ent_emb_dim)
+        F = torch.nn.functional     # translation.py:343: normalize_parameters() on the freshly initialised (host) tables
+        self.ent_emb.weight.data = F.normalize(self.ent_emb.weight.data, p=2, dim=1)
+        self.rel_emb.weight.data = F.normalize(self.rel_emb.weight.data, p=2, dim=1)
+        self.evaluated_projections = False
+
+    def _tables(self):
+        return [self.ent_emb.weight, self.rel_emb.weight, self.proj_mat.weight]
+
+    def scoring_function(self, h_idx, t_idx, r_idx):
+        """-||M_r h^ + r - M_r t^||^2 (translation.py:345-366), one fused HIP kernel; as in the reference a call marks
+        the projections stale."""
+        object.__setattr__(self, 'evaluated_projections', False)
+        return super().scoring_function(h_idx, t_idx, r_idx)
+
+    def project(self, ent, proj_mat):
+        """M e for (b, d_e) rows and (b, d_r, d_e) operators (translation.py:368-370; not on the engine's paths)."""
+        return torch.matmul(proj_mat, ent.view(-1, self.ent_emb_dim, 1)).view(-1, self.rel_emb_dim)
+
+    def normalize_parameters(self):
+        """L2-normalise entity and relation embeddings; proj_mat is left alone (translation.py:372-381)."""
+        self._normalize_weight_(self.ent_emb)
+        self._normalize_weight_(self.rel_emb)
+
+    def get_embeddings(self):
+        self.normalize_parameters()
+        return (self.ent_emb.weight.data, self.rel_emb.weight.data,
+                self.proj_mat.weight.data.view(-1, self.rel_emb_dim, self.ent_emb_dim))
+
+    def evaluate_projectionss(self):
+        """Kept for API compatibility (translation.py:432-458, reference spelling): there is no cache to fill."""
+        self.evaluated_projections = True
+
+    def lp_true_scores_replica(self, prob, qctx):
+        return None     # (the Z row of a true entity belongs to its owner shard: the owner's score, summed over the ranks)
+
+    # ---- candidate side --------------------------------------------------------------------------------------------
+    def _z_table(self, table, c_base, guard_max=None):
+        """Z[r, c] = ||M_r e_c||^2 for the candidate rows, an (n_rel, n) view of a buffer padded as the projection modes
+        want it; per evaluation.  ``guard_max``: its maximum is folded into that device scalar."""
+        M = _hip.f32c(self.proj_mat.weight.data)
+        n = table.shape[0]
+
+        def build():
+            buf = torch.empty(self.n_rel, _hip.padded_cols(n), dtype=torch.float32, device=table.device)
+            if buf.shape[1] > n:
+                buf[:, n:].zero_()
+            _hip.transr_proj_sqnorm(M, table, self.ent_emb_dim, self.rel_emb_dim, out=buf)
+            return buf
+        buf = self._cache.get('transr_z_%d_%d' % (c_base, n), [table, M], build)
+        if guard_max is not None:
+            self._cache.get('transr_zmax_%d_%d' % (c_base, n), [buf], lambda: _hip.absmax(buf, guard_max))
+        return buf[:, :n]
+
+    def _problem(self, Q, U, r_q, table, c_base):
+        """The all-candidates problem of the queries Q (rows, d_r) in relation space, U = M_r^T Q, relations r_q."""
+        guarded = self.l2_mode == 'auto' and self._expand_ok is None and self._guard_on
+        if self.l2_mode in ('expand', 'auto') and table.shape[0] > 0:
+            gq, ge = (self._lp_guard[0:1], self._lp_guard[1:2]) if guarded else (None, None)
+            qn = _hip.row_sqnorm(Q, max_io=gq)
+            ok = True
+            Z = None
+            if self.l2_mode == 'auto' and not guarded:
+                ok = self._expand_ok
+                if ok is None:          # drop-in API call: decide now on the actual operands (one sync)
+                    Z = self._z_table(table, c_base)
+                    ok = Q.shape[0] == 0 or float((qn.max() + Z.max()).item()) <= self.L2_EXPAND_LIMIT
+            if ok:
+                if Z is None:
+                    Z = self._z_table(table, c_base, ge)
+                rows, n = Q.shape[0], table.shape[0]
+
+                def ones_zeros():
+                    pz = torch.zeros(rows, 2, dtype=torch.float32, device=Q.device)
+                    pz[:, 0] = 1.0
+                    return pz
+                pz = self._cache.get('transr_pz_%d' % rows, [table], ones_zeros)
+                en = self._cache.get('transr_en0_%d' % n, [table],
+                                     lambda: torch.zeros(max(n, 1), dtype=torch.float32, device=Q.device))
+                object.__setattr__(self, 'lp_last_path', 'expand')
+                return _hip.LpProblem(_hip.LP_L2_PROJH, U, table, qn=qn, en=en, Wq=pz, scal=Z, r_idx=r_q, c_base=c_base)
+        object.__setattr__(self, 'lp_last_path', 'exact')
+        return _RelationGroupedProblem(Q, r_q, table, _hip.f32c(self.proj_mat.weight.data), self.ent_emb_dim,
+                                       self.rel_emb_dim, c_base)
+
+    def lp_problem(self, h_idx, t_idx, r_idx, side, ent_lo=0, ent_hi=None, exchange=None, qtabs=None, cols=None):
+        ent_lo, ent_hi = _ent_range(self, ent_lo, ent_hi)
+        E, R, M = [_hip.f32c(x.data) for x in self._tables()]
+        sd = _hip.side_code(side)
+        de, dr = self.ent_emb_dim, self.rel_emb_dim
+        table = self._cand_rows(E, ent_lo, ent_hi)
+        r_q = _both_r(r_idx, sd, getattr(self, '_lp_r_both', None))
+        if qtabs is not None:               # replicas of the query entities' rows: h_idx / t_idx index them
+            Q, U = _hip.transr_query(sd, _hip.f32c(qtabs[0]), M, R, de, dr, h_idx, t_idx, r_idx)
+        elif self._row_shard is not None:   # the owner's rows, zero elsewhere, summed over the shards (x + 0 is exact)
+            if exchange is None:
+                raise RuntimeError('torchkge_amd: a row-sharded model needs the evaluator\'s query exchange')
+            ids = torch.cat([h_idx, t_idx]) if sd == _hip.SIDE_BOTH else (h_idx if sd == _hip.SIDE_TAIL else t_idx)
+            lo, hi = self._row_shard
+            rows = _hip.lp_prep(_hip.TRANSE_L2, _hip.SIDE_PROJ_H, [E, E], de, de, ids, ids, torch.zeros_like(ids),
+                                ent_lo=lo, ent_n=hi - lo)[0]
+            exchange([rows])
+            Q, U = _hip.transr_query(sd, rows, M, R, de, dr, None, None, r_idx)
+        else:
+            Q, U = _hip.transr_query(sd, E, M, R, de, dr, h_idx, t_idx, r_idx)
+        return self._problem(Q, U, r_q, table, ent_lo)
+
+    # ---- reference inference API -------------------------------------------------------------------------------------
+    def inference_prepare_candidates(self, h_idx, t_idx, r_idx, entities=True):
+        """(proj_h, proj_t, r, candidates) (translation.py:405-430); entity candidates are an EntityCandidates handle,
+        never a (b, N, d_r) copy; ``entities=False``: RelationProjections handles and the expanded relation table."""
+        self._check_unsharded('inference_prepare_candidates')
+        object.__setattr__(self, 'evaluated_projections', True)
+        tabs = [x.data for x in self._tables()]
+        de, dr = self.ent_emb_dim, self.rel_emb_dim
+        r = _hip.gather_rows(tabs[1], r_idx)
+        if not entities:
+            cand = tabs[1].view(1, self.n_rel, dr).expand(h_idx.shape[0], self.n_rel, dr)
+            return (RelationProjections(self, _hip.i64c(h_idx), _hip.SIDE_PROJ_H),
+                    RelationProjections(self, _hip.i64c(t_idx), _hip.SIDE_PROJ_T), r, cand)
+        proj_h, proj_t = _projections(_hip.TRANSR, tabs, de, dr, h_idx, t_idx, r_idx)
+        return proj_h, proj_t, r, EntityCandidates(self, _hip.i64c(r_idx), max(h_idx.shape[0], t_idx.shape[0]))
+
+    def _relation_scores_proj(self, proj_h, proj_t, r):
+        R = self.rel_emb.weight.data
+        tab = _table_of(r)
+        if tab is None or tab.data_ptr() != R.data_ptr() or tab.shape != R.shape:
+            return None
+        E = self.ent_emb.weight.data
+        X = _hip.ewise(_hip.EW_SUB, _hip.gather_rows(E, proj_h.idx), _hip.gather_rows(E, proj_t.idx))
+        return _hip.transr_proj_sqnorm(self.proj_mat.weight.data, X, self.ent_emb_dim, self.rel_emb_dim, b=R,
+                                       by_row=True).neg_()
+
+    def _handle_problem(self, q, cand, ent_lo=0, ent_hi=None):
+        ent_hi = self.n_ent if ent_hi is None else ent_hi
+        E, _, M = [_hip.f32c(x.data) for x in self._tables()]
+        q = _hip.f32c(q)
+        _, U = _hip.transr_query(_hip.SIDE_TAIL, None, M, None, self.ent_emb_dim, self.rel_emb_dim, None, None,
+                                 cand.r_idx, Q=q)
+        return self._problem(q, U, cand.r_idx, self._cand_rows(E, ent_lo, ent_hi), ent_lo)
