@@ -75,7 +75,9 @@ extern "C" {
 typedef void *kge_stream_t; /* hipStream_t */
 
 #define KGE_EINVAL (-1)   /* bad argument (null pointer, bad size / kind) */
-#define KGE_EALIGN (-2)   /* pointer or leading dimension not aligned as required */
+#define KGE_EALIGN (-2)   /* RESERVED: no entry point returns it.  Unaligned input is either taken by a kernel's scalar body
+                           * (every entry point with a leading dimension, unless its comment says otherwise) or refused with
+                           * the code that entry point documents (KGE_EUNSUPPORTED / KGE_EINVAL) before anything is launched */
 #define KGE_EUNSUPPORTED (-3) /* valid arguments outside what the kernel handles (the caller takes its general path) */
 
 /* model kinds (kge_score_triples, kge_lp_prep) */
@@ -400,7 +402,10 @@ int kge_lp_count_ge(const kge_lp_desc *d, const float *s_true, int32_t *raw_coun
                     kge_stream_t stream);
 /* The same counts for a plain KGE_LP_L2_DIRECT problem (no rank-1 term, 16-byte aligned operands, K0 % 4 == 0) swept over
  * query COLUMNS (see kge_split_args.col_q): column r is scored with query row rep[r]; columns [0, n_single_p) carry one
- * query each (col_q), the next n_multi_p up to kge_lp_split_group_sets() (members); raw_count stays indexed by query. */
+ * query each (col_q), the next n_multi_p up to kge_lp_split_group_sets() (members); raw_count stays indexed by query.
+ * KGE_EINVAL -- nothing is launched, raw_count is not touched -- for any other mode, a rank-1 term (Wq), K0 % 4 != 0,
+ * lda0 % 4 != 0, ldt0 % 4 != 0 or A0 / T0 off a 16-byte boundary: the caller then counts with kge_lp_count_ge, which takes
+ * every layout. */
 int kge_lp_count_ge_cols(const kge_lp_desc *d, const float *s_true, int32_t *raw_count, const int64_t *rep,
                          const int32_t *col_q, int64_t n_single_p, const int32_t *members, int64_t n_multi_p,
                          kge_stream_t stream);
@@ -736,7 +741,11 @@ int kge_lp_table_prep_l2(const float *X, int64_t ld, int64_t rows, int K, float 
 int kge_lp_split_count(const kge_lp_desc *d, const kge_split_args *a, const float *s_true, int32_t *raw_count,
                        kge_stream_t stream);
 /* The exact recheck of a list cut into regions (kge_split_args.region_count): same decrements of raw_count as
- * kge_lp_split_recheck; *list_stat += pairs re-scored, *list_count += pairs re-scored (both optional). */
+ * kge_lp_split_recheck; *list_stat += pairs re-scored, *list_count += pairs re-scored (both optional).
+ * kge_lp_split_regions_supported(d) is 1 for an MFMA mode of at most 32 k16 units whose operand rows are float4-readable
+ * (K0, K1, lda*, ldt* % 4 == 0, 16-byte aligned A* / T*: the region's query rows are staged through LDS in 16-byte pieces);
+ * otherwise kge_lp_split_count with region_count and kge_lp_split_recheck_regions return KGE_EINVAL before anything is
+ * launched, and the caller keeps the one global list + kge_lp_split_recheck, which take every layout. */
 int kge_lp_split_regions(int64_t B);
 int kge_lp_split_regions_supported(const kge_lp_desc *d);
 int kge_lp_split_recheck_regions(const kge_lp_desc *d, const float *s_true, const int32_t *list, int32_t cap,
@@ -799,7 +808,9 @@ int kge_lp_dot_table_prep_fused(const float *X0, int64_t ld0, int K0, const floa
  * (2 * rows_padded(B,1) floats), *list_count = 0; *qmax_io = max(*qmax_io, max qn).  en = ||E[c]||^2 over
  * the WHOLE entity table (no shard), emax its device-side maximum.  Follow with kge_lp_split_count
  * (thr_ready = 1).  side = KGE_SIDE_BOTH: both sides of the B facts as ONE batch of 2B queries (tail-side
- * queries first; every output has 2B rows) -- the ranks of evaluation.py:290-300 from one count launch. */
+ * queries first; every output has 2B rows) -- the ranks of evaluation.py:290-300 from one count launch.
+ * KGE_EINVAL -- nothing is launched, no output is touched -- unless d % 4 == 0 and E, R are 16-byte aligned (float4 staging
+ * of the contiguous table rows; then: the separate kernels, which take every layout). */
 int kge_lp_query_pipeline(int side, const float *E, const float *R, int d, const int64_t *h, const int64_t *t,
                           const int64_t *r, int64_t B, const float *en, const float *emax, float *qmax_io,
                           int accum_model, float eps_scale, float *Q, float *qn, float *s_true, void *Qs,

@@ -171,6 +171,18 @@ void orc_row_sqnorm_chain(const float *X, int64_t ld, int64_t rows, int64_t K, f
     }
 }
 
+/* row dots with the same ascending chain: out[i] = scale * sum_k x[i,k] y[i,k] (kge_row_dot; each matrix has its own
+ * leading dimension here so that a test may hand over packed or strided copies). */
+void orc_row_dot_chain(const float *X, int64_t ldx, const float *Y, int64_t ldy, int64_t rows, int64_t K, float scale,
+                       float *out)
+{
+    for (int64_t i = 0; i < rows; ++i) {
+        float acc = 0.0f;
+        for (int64_t k = 0; k < K; ++k) acc = fmaf(X[i * ldx + k], Y[i * ldy + k], acc);
+        out[i] = scale * acc;
+    }
+}
+
 /* direct translational all-candidates (broadcast-subtract + L_p reduction):
  *   diff_k = (q[i,k] - e[c,k])            [+ a(i,c) * w[i,k]  when w != NULL]
  *   p==2: acc = fmaf(diff_k, diff_k, acc), k ascending

@@ -36,6 +36,109 @@ def fptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+# ---------------------------------------------------------------------------
+# layout-contract helpers: strided / offset operands cut out of ONE poisoned buffer
+# ---------------------------------------------------------------------------
+# Slack (rows of a matrix, elements of a vector) in front of and behind every carved operand: the widest over-read a
+# vectorised or 256-padded kernel body could make stays inside the live allocation and fetches poison -- a wrong kernel
+# fails by VALUE, nothing is arranged to fault.
+SLACK = 256
+_INT_OF_SIZE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+# sentinel bit patterns of guarded outputs (a quiet NaN with a payload as fp32 / fp64, an out-of-pattern integer)
+_SENTINEL = {1: 0xA5, 2: 0x7BAD, 4: 0x7FC0BEEF, 8: 0x7FF8BEEF7FC0BEEF}
+
+
+def _bits(t):
+    """The same memory as integers of the element size (NaN sentinels compare equal as integers)."""
+    return t.view(_INT_OF_SIZE[t.element_size()])
+
+
+def _start(buf, front, off):
+    """Smallest element index >= front whose address is `off` elements past a 16-byte boundary."""
+    size = buf.element_size()
+    per16 = 16 // size
+    assert 0 <= off < per16
+    base = (buf.data_ptr() // size) % per16
+    s = front + ((off - base - front) % per16)
+    assert (buf.data_ptr() + s * size) % 16 == off * size
+    return s
+
+
+def _carve_from(buf, rows, cols, ld, front, off):
+    s = _start(buf, front, off)
+    view = buf.as_strided((rows, cols), (ld, 1), s) if cols is not None else buf.as_strided((rows,), (1,), s)
+    view._guard_buf, view._guard_start, view._guard_ld = buf, s, ld
+    view._guard_bits = _bits(buf)[0].clone()
+    return view
+
+
+def carve(mat, pad=0, off=0, poison=float('nan'), device=None):
+    """A view with mat's shape and values, row stride mat.shape[1] + pad, whose data_ptr() lies `off` elements past a
+    16-byte boundary, inside ONE larger 1-D buffer pre-filled with `poison` (SLACK rows of it on either side, and in
+    every row's pad).  1-D input: the vector variant (SLACK elements of slack, no pad)."""
+    mat = torch.as_tensor(mat)
+    device = mat.device if device is None else device
+    if mat.dim() == 1:
+        n = mat.shape[0]
+        buf = torch.full((n + 2 * SLACK + 16,), poison, dtype=mat.dtype, device=device)
+        view = _carve_from(buf, n, None, 1, SLACK, off)
+    else:
+        rows, cols = mat.shape
+        ld = cols + pad
+        buf = torch.full(((rows + 2 * SLACK) * ld + 16,), poison, dtype=mat.dtype, device=device)
+        view = _carve_from(buf, rows, cols, ld, SLACK * ld, off)
+    view.copy_(mat)
+    return view
+
+
+def guarded_out(rows, cols=None, pad=0, off=0, dtype=torch.float32, device='cuda'):
+    """An OUTPUT view (rows, cols) -- cols None: a vector of `rows` elements -- laid out like carve(), the whole buffer
+    (the view included) pre-filled with a sentinel bit pattern; check it with assert_guard_intact."""
+    size = torch.empty(0, dtype=dtype).element_size()
+    ld = 1 if cols is None else cols + pad
+    n = (rows + 2 * SLACK) * ld + 16
+    buf = torch.full((n,), _SENTINEL[size], dtype=_INT_OF_SIZE[size], device=device).view(dtype)
+    return _carve_from(buf, rows, cols, ld, SLACK * ld, off)
+
+
+def assert_guard_intact(view, rows=None, cols=None, col0=0):
+    """Every element of the buffer behind a carve() / guarded_out() view that lies outside view[:rows, col0:cols] still
+    holds its fill, bit for bit."""
+    buf, s, ld = view._guard_buf, view._guard_start, view._guard_ld
+    bits = _bits(buf).clone()
+    fill = view._guard_bits.to(bits.device)
+    if view.dim() == 1:
+        inner = bits.as_strided((view.shape[0] if rows is None else rows,), (1,), s)
+    else:
+        inner = bits.as_strided((view.shape[0] if rows is None else rows,
+                                 (view.shape[1] if cols is None else cols) - col0), (ld, 1), s + col0)
+    inner.copy_(fill.expand_as(inner))
+    bad = (bits != fill).nonzero().view(-1)
+    if bad.numel():
+        i = int(bad[0]) - s
+        raise AssertionError('guard overwritten at %d element(s), first at buffer offset %+d from the view (row %d, column %d of '
+                             'leading dimension %d)' % (bad.numel(), i, i // ld, i % ld, ld))
+
+
+def raw(lib, name, *args):
+    """Call the C-ABI symbol `name` of the loaded library with explicit arguments (tensors pass their data_ptr(), a
+    ctypes structure its address; the current stream is appended when the stream argument is left out) and RETURN its
+    integer code: the tensor-level wrappers would copy a strided view, and raise on a refusal."""
+    fn = getattr(lib, name)
+    conv = []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            conv.append(ctypes.c_void_p(a.data_ptr()))
+        elif isinstance(a, ctypes.Structure):
+            conv.append(ctypes.byref(a))
+        else:
+            conv.append(a)
+    if len(conv) == len(fn.argtypes) - 1:
+        conv.append(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert len(conv) == len(fn.argtypes), '%s takes %d arguments' % (name, len(fn.argtypes))
+    return int(fn(*conv))
+
+
 def dict_to_csr(dictionary, key1, key2):
     """Per-query CSR view of dictionary[(key1_i, key2_i)] (python, test-only)."""
     has, off, tgt = [], [0], []

@@ -2032,10 +2032,17 @@ def test_bound_only_row_norms_match_the_chain_to_rounding(hip, rows, K):
     assert float(((b.double() - ref).abs() / ref.clamp_min(1e-30)).max()) < 1e-6
     assert float(((a - b).abs() / a.clamp_min(1e-30)).max()) < 1e-5
     assert abs(float(m[0]) - float(m[1])) <= 1e-5 * float(m[0]) and float(m[1]) == float(b.max())
-    Xs = X[:, :K - 1] if K > 1 else X          # a strided view (ld != K): the scalar path
     if K > 1:
-        c = hip.row_sqnorm(Xs, K=K - 1, bound_only=True)
+        from tests.helpers import raw
+        Xs = X[:, :K - 1]
         refs = (Xs.double() ** 2).sum(1)
+        # the first K - 1 columns of the ORIGINAL matrix: ld = K != K - 1 really reaches the kernel (the tensor-level
+        # wrapper would pack the view), so an odd K - 1 or an odd ld takes the scalar body on a strided table
+        c = torch.empty(rows, device='cuda')
+        assert raw(hip.load_library(), 'kge_row_sqnorm_any_order', X, K, rows, K - 1, c, None) == 0
+        assert float(((c.double() - refs).abs() / refs.clamp_min(1e-30)).max()) < 1e-6
+        # ... and the packed copy of that view (ld == K - 1), which is what this test ran before
+        c = hip.row_sqnorm(Xs, K=K - 1, bound_only=True)
         assert float(((c.double() - refs).abs() / refs.clamp_min(1e-30)).max()) < 1e-6
 
 
