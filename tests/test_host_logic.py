@@ -631,6 +631,76 @@ def test_region_policy_and_lazy_rank_rows_of_the_evaluator():
     assert evm.level1_thresholds(100) == (e1, l1)                   # never below the FB15k-237 figures
 
 
+def test_level_policy_of_the_split_prefilter():
+    """_EvalState.observe / leave_level1, the one copy of the level policy both evaluate() paths call (the guard vector that
+    feeds it exists on the GPU only): enter the one-product level at <= `enter` re-scored pairs per query (never under a
+    forced level), leave it above `leave`, and come back only once the three-product count has halved."""
+    from torchkge_amd import evaluation as evm
+    th = evm.level1_thresholds(14541)
+    assert th == (4, 30)
+    nq = 200.0      # queries (2 per fact)
+    # (state before: _level, _level0_seen, _level1_seen, _level1_max), (level run, pairs per query, auto) -> state after
+    table = [
+        ((0, None, None, None), (0, 3.0, True), (1, 3.0, None, None)),
+        ((0, None, None, None), (0, 5.0, True), (0, 5.0, None, None)),
+        ((0, None, None, None), (0, 3.0, False), (0, 3.0, None, None)),     # a forced split_level: stays
+        ((0, None, None, None), (0, 0.0, True), (0, None, None, None)),     # nothing re-scored: nothing learned
+        ((1, 3.0, None, None), (1, 31.0, True), (0, 3.0, 31.0, 1.5)),
+        ((0, 3.0, 31.0, 1.5), (0, 2.0, True), (0, 2.0, 31.0, 1.5)),
+        ((0, 2.0, 31.0, 1.5), (0, 1.5, True), (1, 1.5, 31.0, 1.5)),
+        ((1, 3.0, None, None), (1, 30.0, True), (1, 3.0, 30.0, None)),      # at the threshold: stays
+    ]
+    for before, (level_run, per_q, auto), after in table:
+        st = evm._EvalState()
+        st._level, st._level0_seen, st._level1_seen, st._level1_max = before
+        assert st.observe(level_run, per_q * nq, nq, th, auto) == per_q
+        assert (st._level, st._level0_seen, st._level1_seen, st._level1_max) == after, (before, level_run, per_q, auto)
+    # zero queries: nothing changes, nothing to report
+    st = evm._EvalState()
+    st._level, st._level0_seen = 1, 3.0
+    assert st.observe(1, 0.0, 0, th, True) is None
+    assert (st._level, st._level0_seen, st._level1_seen, st._level1_max) == (1, 3.0, None, None)
+    # the one-product level's list overflowed: back to level 0; half the last three-product count -- the entry threshold
+    # where none was seen -- caps the re-entry
+    st = evm._EvalState()
+    st._level = 1
+    st.leave_level1(th[0])
+    assert (st._level, st._level1_max) == (0, 2.0)
+    st = evm._EvalState()
+    st._level, st._level0_seen = 1, 3.0
+    st.leave_level1(th[0])
+    assert (st._level, st._level1_max) == (0, 1.5)
+
+
+def test_verdict_on_the_guard_flags():
+    """evaluation._verdict, the one reading of the flags behind the ranks (the redo loop of evaluate() applies it, the
+    steady-state path asks it whether the full path is needed): exactly one of four outcomes; a NaN norm sum means redo."""
+    from torchkge_amd import evaluation as evm
+    A, E, S, G = evm.ACCEPT, evm.REDO_EXPAND, evm.REDO_SPLIT, evm.REDO_AGAIN
+    assert len({A, E, S, G}) == 4
+    lim = 16.0
+    # (worst, overflow, level_now, attempt, split_level) -> outcome
+    table = [
+        ((float('nan'), 0.0, 0, 0, 'auto'), E),
+        ((17.0, 0.0, 0, 0, 'auto'), E),
+        ((17.0, 2.0, 1, 0, 'auto'), E),             # the norm guard comes first
+        ((3.0, 2.0, 0, 0, 'auto'), G),              # stale table scale: the same path again, flags checked again
+        ((3.0, 2.0, 1, 0, 1), G),
+        ((3.0, 2.0, 0, 1, 'auto'), S),              # ... once
+        ((3.0, 1.0, 1, 0, 'auto'), G),              # level-1 list overflow: again on level 0, flags checked again
+        ((3.0, 1.0, 1, 0, 1), S),                   # a forced level: no fallback
+        ((3.0, 1.0, 1, 0, 0), S),
+        ((3.0, 1.0, 1, 1, 'auto'), S),              # the second run: final
+        ((3.0, 1.0, 0, 0, 'auto'), S),              # level 0 has no level to fall back to
+        ((3.0, 0.0, 0, 0, 'auto'), A),
+        ((16.0, 0.0, 1, 1, 1), A),
+        ((0.0, 0.0, 1, 0, 'auto'), A),
+    ]
+    for (worst, overflow, level_now, attempt, split_level), want in table:
+        assert evm._verdict(worst, overflow, level_now, attempt, split_level, lim) == want, (worst, overflow, level_now, attempt)
+    assert evm._verdict(float('inf'), 0.0, 0, 0, 'auto', float('inf')) == A     # models without a norm guard: no limit
+
+
 def test_evaluator_state_cache_is_bounded_weak_and_clearable():
     """What evaluators learn about (model, kg, options) is shared at module level (evaluation._EvalState): at most
     MAX_STATES_PER_MODEL states per model (least recently used first out), none once the model is gone, and

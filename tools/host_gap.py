@@ -41,8 +41,8 @@ def main():
     print('steady-state evaluate(): median %.1f us per call (fast path %s)' % (med(whole), 'armed' if fast else 'NOT armed'))
     if not fast:
         return
-    info = fast[1]
-    out = info['static']['out'][0]
+    info = fast[1]                  # the capture's static state (LinkPredictionEvaluator._capture)
+    out = info['out'][0]
     T = {k: [] for k in ('sig', 'replay_call', 'pinned_empty', 'copy_call', 'sync_wait', 'tolist_views')}
     for _ in range(a.reps):
         t0 = now()

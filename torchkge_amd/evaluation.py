@@ -26,9 +26,15 @@ north star names) or as rank counts (``exchange='counts'``: one int32
 all-reduce of 3*B values, bit-identical ranks).  ``shard='queries'`` splits the
 facts instead (no data-path collective, ranks all-gathered once at the end).
 """
+import collections
+import contextlib
 import ctypes
+import gc
 import os
 import struct
+import sys
+import types
+import warnings
 import weakref
 
 import torch
@@ -38,6 +44,7 @@ from . import _hip
 from . import distributed as kdist
 from .exceptions import NotYetEvaluatedError
 from .filter_index import ColumnPlan, filter_index_for, KEY2_SPAN, FilterPlan
+from .models.interfaces import Model as _BaseModel
 from .utils.data import get_n_batches
 from .utils.modeling import filter_scores
 from .utils.operations import get_rank
@@ -322,6 +329,42 @@ class _EvalState(object):
         self.kg_ref = None
         self.group_ref = None   # the process group of the options key (held so that its id() cannot be reused while this state lives)
 
+    # -- the level policy of the split prefilter (LEVEL1_ENTER / LEVEL1_LEAVE) --------
+    def observe(self, level_run, rescored, n_queries, thresholds, auto):
+        """The level of the NEXT evaluation from an accepted one's re-scored pairs; returns the pairs per query (or None)."""
+        # (`level_run`: the level that one ran on; `thresholds`: level1_thresholds(n_ent); `auto`: the model leaves the level
+        # to the policy; without queries nothing is learned)
+        if n_queries <= 0:
+            return None
+        per_q, (enter, leave) = rescored / n_queries, thresholds
+        if level_run == 0 and rescored > 0:
+            self._level0_seen = per_q
+            cap_ = enter if self._level1_max is None else min(enter, self._level1_max)
+            if per_q <= cap_ and auto:
+                self._level = 1
+        elif level_run == 1 and per_q > leave:
+            self.leave_level1()
+        if level_run == 1 and rescored > 0:
+            self._level1_seen = per_q
+        return per_q
+
+    def leave_level1(self, enter=None):
+        """Back to the three-product level, and not to level 1 again before the three-product count has halved."""
+        # (a model at the boundary must not flip between two captured graphs.  Also the way out when the one-product level's
+        # wider band overflowed the list: `enter`, the entry threshold, then stands in for a three-product count never seen
+        # -- an evaluator whose count sits below it would otherwise enter, overflow and redo on every other evaluation)
+        self._level = 0
+        if self._level0_seen is not None or enter is not None:
+            self._level1_max = 0.5 * (self._level0_seen if self._level0_seen is not None else enter)
+
+    def regions_for(self, level, multi):
+        """The sweep's uncertain pairs in regions of 32 queries?  From REGION_MIN_LEVEL0 re-scored pairs per query seen on the
+        three-product level -- and, once the one-product level has been measured, from REGION_MIN_LEVEL1 there."""
+        r = bool(level == 1 and not multi and self._level0_seen is not None and self._level0_seen >= REGION_MIN_LEVEL0)
+        if r and self._level1_seen is not None and self._level1_seen < REGION_MIN_LEVEL1:
+            r = False       # (too few pairs to amortise a region's query rows)
+        return r
+
 
 _STATES = weakref.WeakKeyDictionary()       # model -> {(id(kg), options): _EvalState}
 SHARE_STATE = os.environ.get('KGE_SHARE_EVAL_STATE', '1') != '0'
@@ -340,6 +383,66 @@ REGION_MIN_LEVEL0 = float(os.environ.get('KGE_REGION_MIN_LEVEL0', '1.2'))
 # longer than one LDS segment -- DistMult / ComplEx d = 400 -- gain 3.6 % at 9.6 pairs per query and lose 1-3 % at 2.0)
 REGION_MIN_LEVEL1 = float(os.environ.get('KGE_REGION_MIN_LEVEL1', '5.0'))
 
+# what the flags of a finished run say (_verdict): take the ranks -- or run again on the exact paths: for good with the norm
+# expansion off (Model._expand_ok = False) / with the split prefilter off (Model._split_ok = False), or the same way once
+# more, the second run's flags being checked like a first run's
+ACCEPT, REDO_EXPAND, REDO_SPLIT, REDO_AGAIN = 'accept', 'redo: _expand_ok', 'redo: _split_ok', 'redo, check again'
+
+
+def _verdict(worst, overflow, level_now, attempt, split_level, limit):
+    """ACCEPT / REDO_EXPAND / REDO_SPLIT / REDO_AGAIN from the flags behind the ranks of run `attempt` (0 / 1)."""
+    # (`worst`: max ||q||^2 + max ||e||^2, against `limit` = Model.L2_EXPAND_LIMIT; `overflow`: the split prefilter's list
+    # flag; `level_now`: the level the evaluation runs on; `split_level`: the model's, 'auto' or forced)
+    # the expansion was safe iff ||q||^2 + ||e||^2 stayed small; otherwise its cancellation error could exceed the score
+    # tolerance -> the VALU kernel (a NaN is not small)
+    if not worst <= limit:
+        return REDO_EXPAND
+    # (r06) not the list: a DOT candidate table converted in one pass under the scale of the PREVIOUS evaluation's norm maxima
+    # has left that binade (Model._dot_fused_problem).  The query pipeline has stored the new maxima: the same path again --
+    # a replay of the same graph -- is consistent now
+    if overflow == 2.0 and attempt == 0:
+        return REDO_AGAIN
+    # the one-product level's wider band overflowed the list: again on the three-product sweep (_EvalState.leave_level1)
+    if overflow > 0 and level_now == 1 and attempt == 0 and split_level == 'auto':
+        return REDO_AGAIN
+    # more near-ties than the split prefilter's list holds: exact fp32 counts
+    return REDO_SPLIT if overflow > 0 else ACCEPT
+
+
+def _dirty_guard(model, guard, zero=True):
+    """In front of whatever folds into the guard vector: zero it unless it is clean (Model._lp_guard_clean); flag down."""
+    # (clean: the previous evaluation's last finalize launch left it zeroed.  Whatever runs next dirties the vector: a run
+    # that raises or ends without a zeroing finalize must not leave the flag standing over stale overflow / re-scored counts)
+    if zero and not getattr(model, '_lp_guard_clean', False):
+        guard.zero_()
+    object.__setattr__(model, '_lp_guard_clean', False)
+
+
+def _read_back(packed, flat):
+    """(packed host tensor, its four flag floats) of a run: the pinned `packed` the finalize launches wrote, or a copy."""
+    if packed is None:
+        packed = _to_host(flat)
+    else:
+        torch.cuda.current_stream(flat.device).synchronize()
+    # (straight from the pinned buffer: slicing + view + tolist cost 4 us of GPU idle time per call)
+    return packed, _FLAGS4.unpack(ctypes.string_at(packed.data_ptr() + 8 * (packed.numel() - 2), 16))
+
+
+def _alloc_out(n, device):
+    """(flat, ranks, flags): (4, n) int64 ranks + two trailing int64 that carry the guard flags -- ONE device-to-host copy."""
+    # (4 floats: norm guard, list overflow, re-scored pairs, spare)
+    flat = torch.empty(4 * n + 2, dtype=torch.int64, device=device)
+    return flat, flat[:4 * n].view(4, n), flat[4 * n:].view(torch.float32)
+
+
+def _device_facts(kg, f_lo, f_hi, device):
+    """Heads, tails, relations of facts [f_lo, f_hi) on the device, in the order of `kg`."""
+    return tuple(x[f_lo:f_hi].to(device) for x in (kg.head_idx, kg.tail_idx, kg.relations))
+
+
+# _rank_side (one side of a batch, never captured as graph segments): no query-entity replicas, no segment to cut
+_PER_SIDE = types.SimpleNamespace(qb=None, cut=None)
+
 
 # states kept per model: the least recently used one goes when a new (kg, options) pair would exceed it -- its captured
 # hipGraphs, their memory pools, static fact / output buffers and plans are released then (at evaluator CONSTRUCTION: no
@@ -351,7 +454,6 @@ def _shared_state(model, kg, cfg, group=None):
     """The _EvalState of (model, kg, cfg) -- created on first use; None when the pair cannot be weakly referenced.
     ``group``: the process group whose id() is part of `cfg` -- held by the state, so that the id cannot be handed to
     another group object while the state lives."""
-    import collections
     try:
         per_model = _STATES.get(model)
         if per_model is None:
@@ -446,16 +548,12 @@ class LinkPredictionEvaluator(object):
         # both sides of a batch as ONE 2B-query problem (single GPU, fused): every latency-bound short
         # kernel of a batch runs once instead of twice, the all-candidates count kernel sees 2B queries
         self.both_sides = both_sides
-        self._cut = None        # set while evaluate() is being captured as graph segments (see _GraphSegments)
         # per-batch FilterPlans (filter segments, true ids, grouping): a function of the test facts and the filter
         # index only, kept across evaluate() calls; _plan_stamp tells when they went stale
-        self._fl, self._fl_done = None, False
         # row-sharded models: the distinct entities of the test facts and the facts re-indexed into that list
         # (static like the plans); their rows are exchanged ONCE per evaluate() (query_exchange='evaluate') instead
         # of the (2B, K) query rows of every batch ('batch')
         self.query_exchange = query_exchange
-        self._qb = None
-        self._shard_flags = None
         # models whose count kernel gathers a per-(relation, candidate) table in its epilogue (TransH / TransD) ask for
         # the facts of a batch to be PROCESSED sorted by relation: the queries of a wavefront then share one or two
         # relation rows of that table instead of 32 different ones.  _perm[j] = original position of the j-th processed
@@ -537,8 +635,7 @@ class LinkPredictionEvaluator(object):
                 and len(refs) == len(self._plan_refs) and all(a is b for a, b in zip(refs, self._plan_refs))):
             return
         self._plan_refs = refs
-        heads, tails, rels = (kg.head_idx[f_lo:f_hi].to(device), kg.tail_idx[f_lo:f_hi].to(device),
-                              kg.relations[f_lo:f_hi].to(device))
+        heads, tails, rels = _device_facts(kg, f_lo, f_hi, device)
         self._perm = None
         if want_sort and rels.shape[0] > 0:
             # stable sort by relation INSIDE every batch (batch membership is unchanged)
@@ -591,7 +688,7 @@ class LinkPredictionEvaluator(object):
         seg_lo, seg_hi = eng.lookup(index, key1, r)
         if self._generic_model:
             return self._rank_side_generic(h, t, r, side, index, true_idx, key1)
-        prob = eng.problem(self.model, h, t, r, side, lo, hi, **self._xkw(sharded))
+        prob = eng.problem(self.model, h, t, r, side, lo, hi, **self._xkw(_PER_SIDE, sharded))
         if self.fused and not (sharded and self.exchange == 'scores'):
             s_true = eng.true_scores(prob, true_idx)
             if sharded:
@@ -605,21 +702,21 @@ class LinkPredictionEvaluator(object):
             scores = self._timed(lambda: kdist.all_gather_columns(scores, self.model.n_ent, self.group))()
         return eng.ranks_from_scores(scores, true_idx, seg_lo, seg_hi, index.targets)
 
-    def _rank_batch_both(self, h, t, r, index_t, index_h, out, off, lo, hi, sharded, last=False, guard=None):
-        """Both sides of one batch through one problem of 2B queries (tail side first):
+    def _rank_batch_both(self, c, h, t, r, out, off, last=False):
+        """Both sides of one batch of the evaluation `c` through one problem of 2B queries (tail side first):
         one filter lookup, one query-side launch, one count (+ recheck), one filter
         correction, one finalize into columns off.. of the (4, n) result matrix.  Ranks
         are per query: identical to two _rank_side calls.  Entity-sharded: ONE collective per
         batch -- the (3, 2B) partial rank counts (+ the guard flags on the last batch); the (2B) true
         scores need a second one only when no query-entity replicas are at hand (the owner shard holds
         the value, the others 0; x + 0 is exact)."""
-        eng = self.engine
+        eng, sharded, guard = self.engine, c.sharded, c.guard
         plan = self._plans.get((off, h.shape[0])) if self._plans is not None else None
         if plan is not None:    # filter segments, true ids and the grouping of the batch: precomputed (FilterPlan)
             seg_lo, seg_hi, true_idx, targets = plan.seg_lo, plan.seg_hi, plan.true_idx, plan.targets
         else:
-            seg_lo, seg_hi, true_idx, targets = eng.lookup_both(index_t, index_h, h, t, r)
-        xkw = self._xkw(sharded)
+            seg_lo, seg_hi, true_idx, targets = eng.lookup_both(c.index_t, c.index_h, h, t, r)
+        xkw = self._xkw(c, sharded)
         by_scores = sharded and self.exchange == 'scores'
         lvl1 = hasattr(self.model, '_use_level1') and self.model._use_level1()      # (the policy's choice, or a forced level)
         # (one-product level: the matrix work a shared row saves is a third of what it was, the grouped columns' multi-pass
@@ -636,28 +733,28 @@ class LinkPredictionEvaluator(object):
         if hint is not None and hasattr(self.model, '_lp_r_both'):
             object.__setattr__(self.model, '_lp_r_both', hint)
         try:
-            prob = eng.problem(self.model, h, t, r, 'both', lo, hi, **xkw)
+            prob = eng.problem(self.model, h, t, r, 'both', c.lo, c.hi, **xkw)
         finally:
             if hint is not None and hasattr(self.model, '_lp_r_both'):
                 object.__setattr__(self.model, '_lp_r_both', None)
         if by_scores:
-            return self._exchange_score_tiles(prob, h.shape[0], true_idx, seg_lo, seg_hi, targets, out, off)
+            return self._exchange_score_tiles(c, prob, h.shape[0], true_idx, seg_lo, seg_hi, targets, out, off)
         s_true = None
-        if sharded and self._qb is not None and getattr(prob, 'pre', None) is not None and prob.pre.get('true_idx') is None:
+        if sharded and c.qb is not None and getattr(prob, 'pre', None) is not None and prob.pre.get('true_idx') is None:
             # row-sharded tables, fused query side fed from the query-entity replicas (r05): the pipeline has scored
             # exactly the (query, true entity) pairs -- on every rank, from the same rows: no collective
             prob.pre['true_idx'] = true_idx
             s_true = prob.pre['s_true']
             if hasattr(prob, 'split_true'):
                 prob.split_true = (s_true, true_idx)
-        elif sharded and self._qb is not None and hasattr(self.model, 'lp_true_scores_replica'):
+        elif sharded and c.qb is not None and hasattr(self.model, 'lp_true_scores_replica'):
             # row-sharded tables: the true entities' rows are in the query-entity replicas, so every rank scores
             # the (query, true entity) pairs itself -- same rows, same chain, same bits: no collective
-            s_true = self.model.lp_true_scores_replica(prob, self._qb)
+            s_true = self.model.lp_true_scores_replica(prob, c.qb)
         if s_true is None:
             s_true = eng.true_scores(prob, true_idx)
             if sharded:
-                self._collective(lambda s_=s_true, g_=self.group: kdist.all_reduce_sum(s_, g_))
+                self._collective(c, lambda s_=s_true, g_=self.group: kdist.all_reduce_sum(s_, g_))
         n2 = s_true.shape[0]
         # entity shards, last batch: the two guard decisions ride the counts exchange as 0 / 1 columns (a SUM > 0
         # means "some rank says so"; max ||q||^2 is the same on every rank, so "max_q + max_e_p > limit on some
@@ -666,7 +763,7 @@ class LinkPredictionEvaluator(object):
         kw = {'plan': plan} if plan is not None else {}
         if ride:
             kw['pad'] = 3
-        if self._use_aux and not sharded and isinstance(eng, HipRankEngine) and s_true.is_cuda:
+        if c.use_aux and not sharded and isinstance(eng, HipRankEngine) and s_true.is_cuda:
             kw['aux'] = self._aux_stream        # (created by evaluate(), outside any capture)
             kw['count_first'] = bool(getattr(self.model, 'lp_count_first', False)) if COUNT_FIRST is None else COUNT_FIRST
         counts = eng.partial_counts(prob, s_true, true_idx, seg_lo, seg_hi, targets, **kw)
@@ -676,17 +773,17 @@ class LinkPredictionEvaluator(object):
             counts[0, n2 + 1:n2 + 2] = (guard[2:3] > 0).to(torch.int32)
             counts[0, n2 + 2:n2 + 3] = guard[6:7].to(torch.int32)      # pairs this shard re-scored (level policy: their SUM)
         if sharded:     # (the recorded call runs again at every graph replay: bind the tensor, not the name)
-            self._collective(lambda c_=counts, g_=self.group: kdist.all_reduce_sum(c_, g_))
+            self._collective(c, lambda c_=counts, g_=self.group: kdist.all_reduce_sum(c_, g_))
         if ride:
-            self._shard_flags = counts[0, n2:n2 + 3]
+            c.shard_flags = counts[0, n2:n2 + 3]
         fkw = {}
-        if (last and guard is not None and not sharded and self._fl is not None and getattr(eng, 'writes_flags', False)):
-            fkw = {'guard': guard, 'flags': self._fl}       # the last finalize also writes the two guard flags
-            self._fl_done = True
+        if (last and guard is not None and not sharded and c.fl is not None and getattr(eng, 'writes_flags', False)):
+            fkw = {'guard': guard, 'flags': c.fl}       # the last finalize also writes the two guard flags
+            c.fl_done = True
             if getattr(eng, 'zeroes_guard', False):         # ... and leaves the guard vector zeroed for the next evaluation
                 fkw['zero_guard'] = True
-                self._guard_zeroed = True
-        direct = self.__dict__.get('_direct_ptr') if not sharded else None
+                c.guard_zeroed = True
+        direct = c.direct_ptr if not sharded else None
         if direct and self._perm is None:
             fkw['indirect'] = direct            # ranks (and flags) straight into pinned host memory
         if self._perm is not None:
@@ -698,7 +795,7 @@ class LinkPredictionEvaluator(object):
         else:
             eng.finalize_both(counts[:, :n2] if ride else counts, out, off, **fkw)
 
-    def _exchange_score_tiles(self, prob, B, true_idx, seg_lo, seg_hi, targets, out, off):
+    def _exchange_score_tiles(self, c, prob, B, true_idx, seg_lo, seg_hi, targets, out, off):
         """exchange='scores' of one both-sides batch (2B queries): the collective north_star names, as a path that
         scales.  The queries are cut into row tiles of P * m rows; every rank scores a tile against ITS candidates
         (fp32 scores, (P * m, N/P) -- bounded by SCORE_TILE_BYTES whatever b_size is), ONE all-to-all hands rank j the
@@ -723,7 +820,7 @@ class LinkPredictionEvaluator(object):
             # (a world of one -- forced collectives -- exchanges nothing: the rank kernel reads the own block from `loc`;
             # a property of the process group, so it is the same when this call is recorded into graph segments)
             in_place = world == 1
-            self._collective(lambda a_=loc, b_=recv, g_=self.group: kdist.all_to_all_rows(a_, b_, g_))
+            self._collective(c, lambda a_=loc, b_=recv, g_=self.group: kdist.all_to_all_rows(a_, b_, g_))
             my0 = q0 + rank * m
             rows = min(m, q1 - my0)
             if rows > 0:
@@ -731,16 +828,16 @@ class LinkPredictionEvaluator(object):
                 eng.rank_tiles(recv, n_ent, true_idx[my0:], seg_lo[my0:], seg_hi[my0:], targets, rows, my0, B, out, off,
                                self._perm, **kw)
 
-    def _xkw(self, sharded):
+    def _xkw(self, c, sharded):
         """Engine keyword for the query exchange of row-sharded entity tables: every rank builds the
         query rows whose entity it owns (zeros elsewhere) and ONE all-reduce SUM per query matrix
         hands the (2B, K) rows to every rank (x + 0 is exact)."""
         if not sharded:
             return {}
         kw = {'exchange': lambda tensors, g_=self.group: self._collective(
-            lambda: [kdist.all_reduce_sum(x, g_) for x in tensors])}
-        if self._qb is not None:
-            kw['qctx'] = self._qb
+            c, lambda: [kdist.all_reduce_sum(x, g_) for x in tensors])}
+        if c.qb is not None:
+            kw['qctx'] = c.qb
         return kw
 
     def _timed(self, fn):
@@ -777,25 +874,25 @@ class LinkPredictionEvaluator(object):
             ev[-1][1].synchronize()
         return {'collectives': len(ev), 'ms': round(sum(a.elapsed_time(b) for a, b in ev), 4)}
 
-    def _collective_value(self, fn, shape, like):
+    def _collective_value(self, c, fn, shape, like):
         """A collective that RETURNS a tensor: run it now -- or, while evaluate() is being captured, allocate the
         result in the graph's pool, cut the capture, and record a call that fills that buffer at replay."""
         buf = like.new_empty(shape)
         fn = self._timed(fn)
-        if self._cut is None:
+        if c.cut is None:
             fn(buf)
         else:
-            self._cut(lambda: fn(buf))
+            c.cut(lambda: fn(buf))
         return buf
 
-    def _collective(self, fn):
+    def _collective(self, c, fn):
         """Run a collective now -- or, while evaluate() is being captured, close the current
         graph segment, record the call, and open the next segment."""
         fn = self._timed(fn)
-        if self._cut is None:
+        if c.cut is None:
             fn()
         else:
-            self._cut(fn)
+            c.cut(fn)
 
     def _rank_batch_overlapped(self, h, t, r, index_t, index_h):
         """Both sides of one batch on two HIP streams: the short kernels (filter
@@ -855,412 +952,384 @@ class LinkPredictionEvaluator(object):
     def evaluate(self, b_size, verbose=True):
         """Rank the true head and tail of every fact of ``kg`` among all
         entities, raw and filtered (evaluation.py:263-308)."""
-        # STEADY STATE (r06): the previous evaluation of this (model, kg, options) was a plain single-GPU graph replay and
-        # nothing that keys the capture has changed -- same b_size, same fact tensors (identity + version), same table
-        # addresses, same kernel-choice switches, same split level: replay at once.  The GPU idles while the host prepares a
-        # replay (~65 us of a 0.49 ms step at cfg2: profiles/r05/timeline_transe_fb15k237.txt); the full prologue below --
-        # plan stamps, capture key, filter indices, guard / session bookkeeping -- is ~35 us of that.  Anything unusual
-        # (a guard flag up, a list overflow, every 32nd evaluation's memory check) goes through the full path.
-        user_b_size = b_size
         # the model's own in-place step of the reference's evaluation (TorusE: frac if not normalized) -- BEFORE the replay
         # check: the capture keys the tables by address and would not see it
         prepare = getattr(self.model, 'lp_eval_prepare', None)
         if prepare is not None:
             prepare()
+        # STEADY STATE (r06): the previous evaluation of this (model, kg, options) was a plain single-GPU graph replay and
+        # nothing that keys the capture has changed -- same b_size, same fact tensors (identity + version), same table
+        # addresses, same kernel-choice switches, same split level: replay at once.  The GPU idles while the host prepares a
+        # replay (~65 us of a 0.49 ms step at cfg2: profiles/r05/timeline_transe_fb15k237.txt); the full path below --
+        # plan stamps, capture key, filter indices, guard / session bookkeeping -- is ~35 us of that.  Anything unusual
+        # (a guard flag up, a list overflow, every 32nd evaluation's memory check) goes through the full path.
         fast = self._st._fast if FAST_REPLAY else None
         if fast is not None:
-            if self._n_evaluations % 32 != 0 and fast[0] == self._fast_sig(user_b_size) and self._evaluate_fast(fast[1]):
+            if self._n_evaluations % 32 != 0 and fast[0] == self._fast_sig(b_size) and self._evaluate_fast(fast[1]):
                 return
             self._st._fast = None
+        c = self._begin(b_size, verbose)
+        try:
+            self._choose_path(c)
+            self._choose_graph(c)
+            if not c.use_graph:
+                self._run_eager(c)
+            else:
+                # the whole evaluate() as ONE hipGraph: ~20 short launches per batch replayed without host gaps
+                if self._graph_key != c.key:
+                    self._capture(c)
+                if self._graph_key == c.key:    # (not after a capture that failed: that one has run eagerly)
+                    self._replay_captured(c)
+            res, any_redo = self._settle(c)
+        finally:
+            c.qb = c.direct_ptr = None
+            object.__setattr__(self.model, '_lp_side_stream', None)
+            if c.guard is not None:      # never leave the model in guarded mode (exceptions included)
+                self.model.lp_guard_end()
+        self._finish(c, res, any_redo)
+
+    def _begin(self, user_b_size, verbose):
+        """The per-call state of a full-path evaluation: device, shards, batch, filter indices, guard, session, streams."""
+        # (a plain namespace that every later step takes and fills in, the scratch of the running batches included -- qb, fl,
+        # fl_done, guard_zeroed, shard_flags, cut, use_aux, direct_ptr: nothing of it outlives the call)
+        c = types.SimpleNamespace(user_b_size=user_b_size, verbose=verbose, kg=self.kg, guard=None, host_buf=None, key=None,
+                                  qb=None, fl=None, fl_done=False, guard_zeroed=False, shard_flags=None, cut=None, direct_ptr=None)
         # (the tensors whose addresses the capture key holds: the model's own table list where it has one -- a walk over
         # Module.parameters() costs three times as much host time, and the GPU idles while the host prepares the replay)
         tables_of = getattr(self.model, '_tables', None)
         try:
-            params = list(tables_of()) if callable(tables_of) else None
+            c.params = list(tables_of()) if callable(tables_of) else None
         except NotImplementedError:         # (a user model on the generic path: interfaces.Model._tables is abstract)
-            params = None
-        if not params:
-            params = list(self.model.parameters())
-        device = params[0].device
-        self._dev = device
+            c.params = None
+        if not c.params:
+            c.params = list(self.model.parameters())
+        device = c.device = self._dev = c.params[0].device
         self.engine.check_device(device)
-        kg = self.kg
-        from .models.interfaces import Model as _BaseModel
         impl = getattr(type(self.model), 'lp_problem', None)
         self._generic_model = impl is None or impl is _BaseModel.lp_problem
 
         world, rank = kdist.world_and_rank(self.group) if self.shard else (1, 0)
-        world_n = world
-        sharded = self.shard == 'entities' and kdist.multi(world)
-        lo, hi = kdist.shard_range(self.model.n_ent, world, rank) if sharded else (0, self.model.n_ent)
-        row_shard = getattr(self.model, '_row_shard', None)
-        if row_shard is not None and (not sharded or row_shard != (lo, hi)):
+        c.world, c.multi = world, kdist.multi(world)
+        sharded = c.sharded = self.shard == 'entities' and c.multi
+        c.lo, c.hi = kdist.shard_range(self.model.n_ent, world, rank) if sharded else (0, self.model.n_ent)
+        c.row_shard = getattr(self.model, '_row_shard', None)
+        if c.row_shard is not None and (not sharded or c.row_shard != (c.lo, c.hi)):
             raise RuntimeError('torchkge_amd: the model holds only entity rows [%d, %d): evaluate it with '
-                               "shard='entities' on the process group it was sharded over" % row_shard)
-        if self.shard == 'queries' and kdist.multi(world):
-            f_lo, f_hi = kdist.shard_range(kg.n_facts, world, rank)
+                               "shard='entities' on the process group it was sharded over" % c.row_shard)
+        if self.shard == 'queries' and c.multi:
+            c.f_lo, c.f_hi = kdist.shard_range(c.kg.n_facts, world, rank)
         else:
-            f_lo, f_hi = 0, kg.n_facts
+            c.f_lo, c.f_hi = 0, c.kg.n_facts
 
         # the filter correction on a second stream beside the count kernel (single GPU): from the second evaluation on --
         # creating and first using a stream costs tens of ms in a fresh process -- or at once when the caller asked for an
         # immediate capture (graph=True); the stream is created HERE, never inside a capture
-        self._use_aux = bool(self.overlap_filter and not sharded and device.type == 'cuda' and
-                             isinstance(self.engine, HipRankEngine) and (self._n_evaluations > 0 or self.graph is True))
-        if self._use_aux and self._aux_stream is None:
+        c.use_aux = bool(self.overlap_filter and not sharded and device.type == 'cuda' and
+                         isinstance(self.engine, HipRankEngine) and (self._n_evaluations > 0 or self.graph is True))
+        if c.use_aux and self._aux_stream is None:
             self._aux_stream = torch.cuda.Stream(device)
-        n_local = f_hi - f_lo
-        b_size = self._internal_batch(b_size, n_local)
-        index_h, index_t = self._filter_indices(device)
-        guard = None
+        c.n_local = c.f_hi - c.f_lo
+        c.b_size = self._internal_batch(user_b_size, c.n_local)
+        c.index_h, c.index_t = self._filter_indices(device)
         if hasattr(self.model, 'lp_guard_begin') and not self._generic_model and device.type == 'cuda':
             was_clean = bool(getattr(self.model, '_lp_guard_clean', False))
             same_guard = getattr(self.model, '_lp_guard', None)
-            guard = self.model.lp_guard_begin(device)   # TransE-L2: optimistic MFMA norm expansion
-            if was_clean and guard is not None and guard is same_guard:
+            c.guard = self.model.lp_guard_begin(device)   # TransE-L2: optimistic MFMA norm expansion
+            if was_clean and c.guard is not None and c.guard is same_guard:
                 object.__setattr__(self.model, '_lp_guard_clean', True)     # (zeroed by the last evaluation's finalize launch)
-        session = self.model.lp_session() if hasattr(self.model, 'lp_session') else _NullCtx()
+        c.session = self.model.lp_session() if hasattr(self.model, 'lp_session') else contextlib.nullcontext()
         # (TransH / TransD: the candidate-side preparation runs on the second stream beside the query side's launches --
         # Model._proj_fast_problem; KGE_PREP_SIDE_STREAM=0 keeps one stream)
-        if self._use_aux and PREP_SIDE_STREAM and not self._generic_model:
+        if c.use_aux and PREP_SIDE_STREAM and not self._generic_model:
             object.__setattr__(self.model, '_lp_side_stream', self._aux_stream)
+        return c
 
+    def _choose_path(self, c):
+        """How the batches are ranked (two streams / both sides / score tiles), their plans, the prefilter's level."""
+        sharded, device, m = c.sharded, c.device, self.model
+        c.overlap = (self.overlap and self.fused and not sharded and not self._generic_model and
+                     isinstance(self.engine, HipRankEngine) and device.type == 'cuda')
+        # (exchange='scores' on entity shards: the all-to-all of score row tiles needs an engine that ranks tiles;
+        # others keep the per-side all-gather of full score rows)
+        by_scores = sharded and self.exchange == 'scores'
+        both = c.both = (self.both_sides and self.fused and not self._generic_model and not c.overlap and
+                         (not by_scores or hasattr(self.engine, 'rank_tiles')) and hasattr(self.engine, 'lookup_both'))
+        by_scores = c.by_scores = by_scores and both
+        if both and getattr(self.engine, 'uses_plans', False) and c.n_local > 0:
+            self._ensure_plans(c.kg, c.f_lo, c.f_hi, c.b_size, c.index_t, c.index_h, device)
+        else:
+            self._plans = self._qmap = self._perm = None
+        c.use_qmap = (c.row_shard is not None and self._qmap is not None and self.query_exchange == 'evaluate')
+        # level of the split prefilter for THIS evaluation (single GPU, fused): decided by the previous one
+        # (entity shards exchanging counts: the re-scored pair count rides the counts all-reduce like the guard flags, so
+        # every rank takes the same decision -- r05; other multi-rank forms stay on the three-product level)
+        # (r06: query shards too -- their ranks meet only in the final all-gather, the re-scored pair counts are summed over
+        # the ranks beside the guard flags so that every rank takes the same decision and captures the same graphs)
+        c.level_ok = (not c.multi) or self.shard == 'queries' or (sharded and both and not by_scores and
+                                                                  getattr(self.engine, 'flag_columns', False))
+        c.level_now = self._level if (c.guard is not None and both and c.level_ok) else 0
+        c.forced_level = getattr(m, 'split_level', 'auto')
+        if c.forced_level != 'auto' and c.guard is not None and both:
+            # (a forced level is what Model._use_level1 runs whatever the policy's state says: the capture key, the region
+            # decision and Model._split_level name THAT level -- r06: a fresh shared state used to report 0 here)
+            c.level_now = 1 if (int(c.forced_level) == 1 and m._use_level1()) else 0
+        # (the WHOLE candidate range: entity shards sum their re-scored pairs over the ranks -- same number, same decision)
+        c.thresholds = level1_thresholds(m.n_ent)
+        # the sweep's uncertain pairs in regions of 32 queries (kge_lp_split_recheck_regions) pay when a region holds
+        # enough of them to amortise its query rows: ~5 x the three-product level's count on the one-product level
+        # -> from REGION_MIN_LEVEL0 re-scored pairs per query there (TransE cfg2: 1.8 -> 9.5 per query: 0.50 -> 0.48 ms;
+        # TransH at 5 per query: 0.64 -> 0.66)
+        c.regions_now = self._st.regions_for(c.level_now, c.multi)
+        if hasattr(m, '_split_level'):
+            object.__setattr__(m, '_split_level', c.level_now)
+            object.__setattr__(m, '_lp_regions', c.regions_now)
+
+    def _choose_graph(self, c):
+        """Eager, one hipGraph or graph segments; the pinned result buffer; the capture key (None: eager)."""
+        # one hipGraph when the batches contain no collective (single GPU, query shards); graph segments with
+        # the collectives between them for entity shards exchanging counts; eager otherwise
+        device, m = c.device, self.model
+        c.segmented = c.multi and c.sharded and c.both
+        c.one_graph = c.segmented and self.graph_collectives and kdist.backend_name(self.group) == 'nccl'
+        c.use_graph = (self.graph is not False and device.type == 'cuda' and c.n_local > 0 and
+                       not self._generic_model and
+                       (not c.multi or self.shard == 'queries' or c.segmented))
+        if c.segmented and os.environ.get('KGE_EAGER_COLLECTIVES') == '1':
+            # escape hatch for a multi-GPU box (no code change): no graph segments, no captured collectives --
+            # every kernel and every RCCL call of a sharded evaluate() is an ordinary eager launch
+            c.use_graph = c.one_graph = False
+        # (r06) single GPU, both-sides batches: the finalize launches write ranks and flags straight into a pinned host
+        # buffer (its address reaches them through a mailbox the host fills before every run / replay): no rank copy
+        # (where the facts are processed in another order -- TransH / TransD sort them by relation -- the finalize launches
+        # keep scattering on the device, scattered 8-byte stores across PCIe cost 0.60 -> 0.66 ms, and one coalesced pass
+        # at the end of the graph carries the packed result over: _rank_batch_both)
+        if (DIRECT_HOST_RANKS and not c.multi and c.both and c.guard is not None and c.n_local > 0 and not c.by_scores
+                and not c.overlap and device.type == 'cuda' and getattr(self.engine, 'writes_host', False)
+                and getattr(self.engine, 'writes_flags', False)):
+            c.host_buf = self._arm_host_out(c.n_local)
+            if c.host_buf is not None:
+                c.direct_ptr = self._st.__dict__['_mailbox'][1]
+        if c.use_graph:
+            # capture is keyed on everything that fixes shapes and ADDRESSES (tables, filter index); table
+            # VALUES may change freely.  The filter indices are kept alive with the graph (their pointers
+            # are baked into it).
+            key = c.key = (
+                c.b_size, c.n_local, str(device), self.fused, c.overlap, c.both, c.segmented, c.one_graph, c.lo, c.hi,
+                c.f_lo, c.f_hi, getattr(m, 'l2_mode', None), getattr(m, 'split_filter', None),   # kernel choice is baked in
+                c.level_now, c.regions_now, getattr(m, 'split_level', None), self.overlap_filter, c.host_buf is not None,
+                tuple(p_.data_ptr() for p_ in c.params), self._plan_gen, c.use_qmap,
+                tuple((x.data_ptr(), x.shape[0]) for ix in (c.index_h, c.index_t) for x in (ix.keys, ix.offsets, ix.targets)))
+            if self.graph is None and self._graph_key != key and self._graph_seen != key and key not in self._graph_cache \
+                    and self._n_evaluations == 0:
+                # 'auto', the FIRST evaluation of this (model, kg): eager -- it is the warm-up (and pays the process's
+                # first-use costs once), the next one captures.  A later change of key (the other level of the split
+                # prefilter, another b_size) warms up and captures in the same call: no second eager evaluation.
+                self._graph_seen = key
+                c.use_graph = False
+
+    def _facts(self, c):
+        """The facts of this evaluation on the device, in processing order."""
+        facts = _device_facts(c.kg, c.f_lo, c.f_hi, c.device)
+        return facts if self._perm is None else tuple(x[self._perm] for x in facts)
+
+    def _run_eager(self, c):
+        """All batches as ordinary launches into a fresh result buffer."""
+        c.flat, c.out, c.flags = _alloc_out(c.n_local, c.device)
+        self._run_batches(c, *self._facts(c), c.out, c.flags)
+
+    def _run_batches(self, c, heads, tails, rels, out, fl):
+        """Every batch of the evaluation `c` enqueued (or captured): ranks into `out`, the guard flags into `fl`."""
+        guard, n_local, b_size = c.guard, c.n_local, c.b_size
+        with c.session, torch.no_grad():
+            c.guard_zeroed = False
+            if guard is not None:
+                # (no fill under a forced path; replays of a graph captured without this fill: _replay)
+                _dirty_guard(self.model, guard, zero=self.model._expand_ok is None)
+            n_batches = get_n_batches(n_local, b_size)
+            if c.by_scores:     # every rank writes only the columns of the queries it ranks
+                out.zero_()
+            c.shard_flags = None
+            c.fl, c.fl_done = fl, False
+            qt = None
+            if c.use_qmap:      # row-sharded tables: replicas of the rows of the query entities, once per evaluate()
+                gather = None
+                if getattr(self.engine, 'uses_plans', False):
+                    gather = lambda blk, g_=self.group, w_=c.world: self._collective_value(
+                        c, lambda out_: kdist.all_gather_blocks(blk, out_, g_), (blk.shape[0] * w_, blk.shape[1]), blk)
+                qt = self.model.lp_query_tables(self._qmap, self._xkw(c, True)['exchange'], gather)
+            for i in tqdm(range(n_batches), total=n_batches, unit='batch', disable=(not c.verbose),
+                          desc='Link prediction evaluation'):
+                sl = slice(i * b_size, (i + 1) * b_size)
+                h, t, r = heads[sl], tails[sl], rels[sl]
+                c.qb = (qt, self._qmap['hq'][sl], self._qmap['tq'][sl]) if qt is not None else None
+                if c.overlap:
+                    out[1, sl], out[3, sl], out[0, sl], out[2, sl] = \
+                        self._rank_batch_overlapped(h, t, r, c.index_t, c.index_h)
+                    continue
+                if c.both:
+                    self._rank_batch_both(c, h, t, r, out, i * b_size, last=(i == n_batches - 1))
+                    continue
+                out[1, sl], out[3, sl] = self._rank_side(h, t, r, 'tail', c.index_t, c.lo, c.hi, c.sharded)
+                out[0, sl], out[2, sl] = self._rank_side(h, t, r, 'head', c.index_h, c.lo, c.hi, c.sharded)
+            if c.by_scores:     # ... and one SUM completes the (4, n) rank matrix on every rank
+                self._collective(c, lambda o_=out, g_=self.group: kdist.all_reduce_sum(o_, g_))
+            if guard is not None and c.shard_flags is not None:
+                # entity shards: the flags came back summed over the ranks with the last batch's counts
+                fl[0:1].copy_(torch.where(c.shard_flags[0:1] > 0, float('inf'), 0.0))
+                fl[1:2].copy_(c.shard_flags[1:2].to(torch.float32))
+                fl[2:3].copy_(c.shard_flags[2:3].to(torch.float32))
+            elif guard is not None and not c.fl_done:
+                # [max ||q||^2 + max ||e||^2, split-prefilter overflow] behind the ranks (the both-sides path
+                # has the last batch's finalize write them)
+                torch.add(guard[0:1], guard[1:2], out=fl[0:1])
+                fl[1:2].copy_(guard[2:3])
+                fl[2:3].copy_(guard[6:7])
+            c.fl = None
+            if guard is not None and c.guard_zeroed:
+                object.__setattr__(self.model, '_lp_guard_clean', True)
+
+    def _capture(self, c):
+        """Make the capture of c.key the current one: a kept one, or warm up and capture (on failure: eager for good)."""
+        key, device = c.key, c.device
+        if key in self._graph_cache:
+            # (e.g. the other level of the split prefilter, captured earlier: switch back without a new capture)
+            if self._graph_key is not None and self._graph is not None:
+                self._graph_cache[self._graph_key] = (self._graph, self._graph_static)
+            self._graph, self._graph_static = self._graph_cache.pop(key)
+            self._graph_key, self._graph_src = key, None
+            return
+        hh_, tt_, rr_ = self._facts(c)
+        st = {'h': hh_.clone(), 't': tt_.clone(), 'r': rr_.clone(), 'out': _alloc_out(c.n_local, device),
+              'index': (c.index_h, c.index_t), 'engine': self.engine, 'plans': self._plans, 'qmap': self._qmap}
+        run = (c, st['h'], st['t'], st['r'], st['out'][1], st['out'][2])
+        # A hipGraph must not be DESTROYED while a stream is capturing (hipErrorStreamCaptureUnsupported, and
+        # ~CUDAGraph throwing takes the process down): garbage that holds old graphs -- e.g. a previous
+        # evaluator, which sits in a reference cycle with its graph segments -- is collected now, and the
+        # cyclic collector stays off until the capture is over.
+        gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
         try:
-            overlap = (self.overlap and self.fused and not sharded and not self._generic_model and
-                       isinstance(self.engine, HipRankEngine) and device.type == 'cuda')
-
-            # (exchange='scores' on entity shards: the all-to-all of score row tiles needs an engine that ranks tiles;
-            # others keep the per-side all-gather of full score rows)
-            by_scores = sharded and self.exchange == 'scores'
-            both = (self.both_sides and self.fused and not self._generic_model and not overlap and
-                    (not by_scores or hasattr(self.engine, 'rank_tiles')) and hasattr(self.engine, 'lookup_both'))
-            by_scores = by_scores and both
-            if both and getattr(self.engine, 'uses_plans', False) and n_local > 0:
-                self._ensure_plans(kg, f_lo, f_hi, b_size, index_t, index_h, device)
-            else:
-                self._plans = self._qmap = self._perm = None
-            use_qmap = (row_shard is not None and self._qmap is not None and self.query_exchange == 'evaluate')
-            self._qb = None
-
-            def facts():
-                """The facts of this evaluation on the device, in processing order."""
-                hh, tt, rr = (kg.head_idx[f_lo:f_hi].to(device), kg.tail_idx[f_lo:f_hi].to(device),
-                              kg.relations[f_lo:f_hi].to(device))
-                if self._perm is not None:
-                    hh, tt, rr = hh[self._perm], tt[self._perm], rr[self._perm]
-                return hh, tt, rr
-
-            def alloc_out():
-                # (4, n) ranks + two trailing int64 that carry the guard flags (4 floats: norm guard, list overflow,
-                # re-scored pairs, spare): ONE device-to-host copy
-                flat = torch.empty(4 * n_local + 2, dtype=torch.int64, device=device)
-                return flat, flat[:4 * n_local].view(4, n_local), flat[4 * n_local:].view(torch.float32)
-
-            def run(heads, tails, rels, out, fl):
-                with session, torch.no_grad():
-                    self._guard_zeroed = False
-                    if guard is not None:
-                        # (clean when the previous evaluation's last finalize zeroed it -- Model._lp_guard_clean; replays
-                        # of a graph captured without this fill check the flag in front of the replay)
-                        if self.model._expand_ok is None and not getattr(self.model, '_lp_guard_clean', False):
-                            guard.zero_()
-                        # whatever this run does, it dirties the vector: a redo that raises or ends without a zeroing
-                        # finalize must not leave the flag standing over stale overflow / re-scored counts
-                        object.__setattr__(self.model, '_lp_guard_clean', False)
-                    n_batches = get_n_batches(n_local, b_size)
-                    if by_scores:       # every rank writes only the columns of the queries it ranks
-                        out.zero_()
-                    self._shard_flags = None
-                    self._fl, self._fl_done = fl, False
-                    qt = None
-                    if use_qmap:    # row-sharded tables: replicas of the rows of the query entities, once per evaluate()
-                        gather = None
-                        if getattr(self.engine, 'uses_plans', False):
-                            gather = lambda blk, g_=self.group: self._collective_value(
-                                lambda out_: kdist.all_gather_blocks(blk, out_, g_),
-                                (blk.shape[0] * world_n, blk.shape[1]), blk)
-                        qt = self.model.lp_query_tables(self._qmap, self._xkw(True)['exchange'], gather)
-                    for i in tqdm(range(n_batches), total=n_batches, unit='batch', disable=(not verbose),
-                                  desc='Link prediction evaluation'):
-                        sl = slice(i * b_size, (i + 1) * b_size)
-                        h, t, r = heads[sl], tails[sl], rels[sl]
-                        self._qb = (qt, self._qmap['hq'][sl], self._qmap['tq'][sl]) if qt is not None else None
-                        if overlap:
-                            out[1, sl], out[3, sl], out[0, sl], out[2, sl] = \
-                                self._rank_batch_overlapped(h, t, r, index_t, index_h)
-                            continue
-                        if both:
-                            self._rank_batch_both(h, t, r, index_t, index_h, out, i * b_size, lo, hi, sharded,
-                                                  last=(i == n_batches - 1), guard=guard)
-                            continue
-                        out[1, sl], out[3, sl] = self._rank_side(h, t, r, 'tail', index_t, lo, hi, sharded)
-                        out[0, sl], out[2, sl] = self._rank_side(h, t, r, 'head', index_h, lo, hi, sharded)
-                    if by_scores:       # ... and one SUM completes the (4, n) rank matrix on every rank
-                        self._collective(lambda o_=out, g_=self.group: kdist.all_reduce_sum(o_, g_))
-                    if guard is not None and self._shard_flags is not None:
-                        # entity shards: the flags came back summed over the ranks with the last batch's counts
-                        fl[0:1].copy_(torch.where(self._shard_flags[0:1] > 0, float('inf'), 0.0))
-                        fl[1:2].copy_(self._shard_flags[1:2].to(torch.float32))
-                        fl[2:3].copy_(self._shard_flags[2:3].to(torch.float32))
-                    elif guard is not None and not self._fl_done:
-                        # [max ||q||^2 + max ||e||^2, split-prefilter overflow] behind the ranks (the both-sides path
-                        # has the last batch's finalize write them)
-                        torch.add(guard[0:1], guard[1:2], out=fl[0:1])
-                        fl[1:2].copy_(guard[2:3])
-                        fl[2:3].copy_(guard[6:7])
-                    self._fl = None
-                    if guard is not None and self._guard_zeroed:
-                        object.__setattr__(self.model, '_lp_guard_clean', True)
-
-            # one hipGraph when run() contains no collective (single GPU, query shards); graph segments with
-            # the collectives between them for entity shards exchanging counts; eager otherwise
-            # level of the split prefilter for THIS evaluation (single GPU, fused): decided by the previous one
-            # (entity shards exchanging counts: the re-scored pair count rides the counts all-reduce like the guard flags, so
-            # every rank takes the same decision -- r05; other multi-rank forms stay on the three-product level)
-            # (r06: query shards too -- their ranks meet only in the final all-gather, the re-scored pair counts are summed over
-            # the ranks beside the guard flags so that every rank takes the same decision and captures the same graphs)
-            level_ok = (not kdist.multi(world)) or self.shard == 'queries' or (sharded and both and not by_scores and
-                                                                                getattr(self.engine, 'flag_columns', False))
-            level_now = self._level if (guard is not None and both and level_ok) else 0
-            forced_level = getattr(self.model, 'split_level', 'auto')
-            if forced_level != 'auto' and guard is not None and both:
-                # (a forced level is what Model._use_level1 runs whatever the policy's state says: the capture key, the region
-                # decision and Model._split_level name THAT level -- r06: a fresh shared state used to report 0 here)
-                level_now = 1 if (int(forced_level) == 1 and self.model._use_level1()) else 0
-            # (the WHOLE candidate range: entity shards sum their re-scored pairs over the ranks -- same number, same decision)
-            lvl_enter, lvl_leave = level1_thresholds(self.model.n_ent)
-            if hasattr(self.model, '_split_level'):
-                object.__setattr__(self.model, '_split_level', level_now)
-            # the sweep's uncertain pairs in regions of 32 queries (kge_lp_split_recheck_regions) pay when a region holds
-            # enough of them to amortise its query rows: ~5 x the three-product level's count on the one-product level
-            # -> from REGION_MIN_LEVEL0 re-scored pairs per query there (TransE cfg2: 1.8 -> 9.5 per query: 0.50 -> 0.48 ms;
-            # TransH at 5 per query: 0.64 -> 0.66)
-            regions_now = self._regions_for(level_now, kdist.multi(world))
-            if hasattr(self.model, '_split_level'):
-                object.__setattr__(self.model, '_lp_regions', regions_now)
-            multi = kdist.multi(world)
-            segmented = multi and sharded and both
-            one_graph = segmented and self.graph_collectives and kdist.backend_name(self.group) == 'nccl'
-            use_graph = (self.graph is not False and device.type == 'cuda' and n_local > 0 and
-                         not self._generic_model and
-                         (not multi or self.shard == 'queries' or segmented))
-            if segmented and os.environ.get('KGE_EAGER_COLLECTIVES') == '1':
-                # escape hatch for a multi-GPU box (no code change): no graph segments, no captured collectives --
-                # every kernel and every RCCL call of a sharded evaluate() is an ordinary eager launch
-                use_graph = one_graph = False
-            # (r06) single GPU, both-sides batches: the finalize launches write ranks and flags straight into a pinned host
-            # buffer (its address reaches them through a mailbox the host fills before every run / replay): no rank copy
-            host_buf = None
-            self.__dict__['_direct_ptr'] = None
-            # (where the facts are processed in another order -- TransH / TransD sort them by relation -- the finalize launches
-            # keep scattering on the device, scattered 8-byte stores across PCIe cost 0.60 -> 0.66 ms, and one coalesced pass
-            # at the end of the graph carries the packed result over: _rank_batch_both)
-            if (DIRECT_HOST_RANKS and not multi and both and guard is not None and n_local > 0 and not by_scores and not overlap
-                    and device.type == 'cuda' and getattr(self.engine, 'writes_host', False)
-                    and getattr(self.engine, 'writes_flags', False)):
-                host_buf = self._arm_host_out(n_local)
-                if host_buf is not None:
-                    self.__dict__['_direct_ptr'] = self._st.__dict__['_mailbox'][1]
-            direct_now = host_buf is not None
-            key = None
-            if use_graph:
-                # capture is keyed on everything that fixes shapes and ADDRESSES (tables, filter index); table
-                # VALUES may change freely.  The filter indices are kept alive with the graph (their pointers
-                # are baked into it).
-                key = (b_size, n_local, str(device), self.fused, overlap, both, segmented, one_graph, lo, hi, f_lo, f_hi,
-                       getattr(self.model, 'l2_mode', None), getattr(self.model, 'split_filter', None),   # kernel choice is baked in
-                       level_now, regions_now, getattr(self.model, 'split_level', None), self.overlap_filter, direct_now,
-                       tuple(p_.data_ptr() for p_ in params), self._plan_gen, use_qmap,
-                       tuple((x.data_ptr(), x.shape[0]) for ix in (index_h, index_t)
-                             for x in (ix.keys, ix.offsets, ix.targets)))
-                if self.graph is None and self._graph_key != key and self._graph_seen != key and key not in self._graph_cache \
-                        and self._n_evaluations == 0:
-                    # 'auto', the FIRST evaluation of this (model, kg): eager -- it is the warm-up (and pays the process's
-                    # first-use costs once), the next one captures.  A later change of key (the other level of the split
-                    # prefilter, another b_size) warms up and captures in the same call: no second eager evaluation.
-                    self._graph_seen = key
-                    use_graph = False
-            if not use_graph:
-                heads, tails, rels = facts()
-                flat, out, fl = alloc_out()
-                run(heads, tails, rels, out, fl)
-            else:
-                # the whole evaluate() as ONE hipGraph: ~20 short launches per batch replayed without host gaps
-                if self._graph_key != key and key in self._graph_cache:
-                    # (e.g. the other level of the split prefilter, captured earlier: switch back without a new capture)
-                    if self._graph_key is not None and self._graph is not None:
-                        self._graph_cache[self._graph_key] = (self._graph, self._graph_static)
-                    self._graph, self._graph_static = self._graph_cache.pop(key)
-                    self._graph_key, self._graph_src = key, None
-                if self._graph_key != key:
-                    hh_, tt_, rr_ = facts()
-                    st = {'h': hh_.clone(), 't': tt_.clone(), 'r': rr_.clone(),
-                          'out': alloc_out(), 'index': (index_h, index_t), 'engine': self.engine, 'plans': self._plans,
-                          'qmap': self._qmap}
-                    # A hipGraph must not be DESTROYED while a stream is capturing (hipErrorStreamCaptureUnsupported, and
-                    # ~CUDAGraph throwing takes the process down): garbage that holds old graphs -- e.g. a previous
-                    # evaluator, which sits in a reference cycle with its graph segments -- is collected now, and the
-                    # cyclic collector stays off until the capture is over.
-                    import gc
-                    gc_was_on = gc.isenabled()
-                    gc.collect()
-                    gc.disable()
-                    try:
-                        if self.graph is not None or self._graph_seen != key:
-                            side = self._aux_stream if self._aux_stream is not None else torch.cuda.Stream(device)
-                            side.wait_stream(torch.cuda.current_stream(device))
-                            with torch.cuda.stream(side):            # warm-up outside capture (lazy inits, attribute sets)
-                                run(st['h'], st['t'], st['r'], st['out'][1], st['out'][2])
-                            torch.cuda.current_stream(device).wait_stream(side)
-                        if one_graph:       # collectives captured with the kernels (see graph_collectives)
-                            g = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                                run(st['h'], st['t'], st['r'], st['out'][1], st['out'][2])
-                        elif segmented:
-                            g = _GraphSegments()
-                            self._cut = g.cut
-                            g.begin()
-                            try:
-                                run(st['h'], st['t'], st['r'], st['out'][1], st['out'][2])
-                            except BaseException:
-                                import sys
-                                g.end(sys.exc_info())
-                                raise
-                            finally:
-                                self._cut = None
-                            g.end()
-                        else:
-                            g = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(g):
-                                run(st['h'], st['t'], st['r'], st['out'][1], st['out'][2])
-                    except Exception as exc:
-                        if self.graph is True:
-                            raise
-                        import warnings
-                        warnings.warn('torchkge_amd: hipGraph capture of evaluate() failed (%s); running eagerly' % (exc,))
-                        self.graph = False
-                        self._graph_failed = True
-                        self._graph = self._graph_static = self._graph_key = None
-                        self._graph_cache = {}
-                        torch.cuda.synchronize(device)
-                        flat, out, fl = alloc_out()
-                        run(*facts(), out, fl)
-                        g = None
-                    finally:
-                        if gc_was_on:
-                            gc.enable()
-                    if g is not None:
-                        st['zeroes_guard'] = bool(self._guard_zeroed)     # the captured run() ended with a guard-zeroing finalize
-                        st['shard_flags'] = self._shard_flags             # (entity shards: where the summed flags land)
-                        st['needs_clean_guard'] = guard is not None
-                        st['targets_cat'] = getattr(self.engine, '_targets_cat', None)   # baked into the graph too
-                        if self._graph_key is not None and self._graph is not None:
-                            # keep ONE earlier capture (the other split level); older ones go -- outside any capture
-                            self._graph_cache = {self._graph_key: (self._graph, self._graph_static)}
-                        self._graph, self._graph_static, self._graph_key = g, st, key
-                        self._graph_src = None
-                if self._graph_key == key:
-                    st = self._graph_static
-                    src = tuple((x.data_ptr(), x._version, f_lo, f_hi) for x in (kg.head_idx, kg.tail_idx, kg.relations))
-                    if src != self._graph_src:      # refresh the graph's static inputs only when the facts changed
-                        hh_, tt_, rr_ = facts()
-                        st['h'].copy_(hh_, non_blocking=True)
-                        st['t'].copy_(tt_, non_blocking=True)
-                        st['r'].copy_(rr_, non_blocking=True)
-                        self._graph_src = src
-                    if guard is not None and st.get('needs_clean_guard'):
-                        # the graph holds no fill of the guard vector: it relies on the previous evaluation's zeroing finalize
-                        if not getattr(self.model, '_lp_guard_clean', False):
-                            guard.zero_()
-                        object.__setattr__(self.model, '_lp_guard_clean', False)
-                    self._graph.replay()
-                    self._shard_flags = st.get('shard_flags')
-                    if guard is not None and st.get('zeroes_guard'):
-                        object.__setattr__(self.model, '_lp_guard_clean', True)
-                    flat, out, fl = st['out']
-
-            res = None
-            n_pol = None
-            any_redo = False
-            for attempt in (0, 1):
-                if guard is None:
-                    break
-                # the expansion was safe iff ||q||^2 + ||e||^2 stayed small; otherwise its
-                # cancellation error could exceed the score tolerance -> redo on the VALU kernel
-                if kdist.multi(world) and self._shard_flags is None:
-                    flags = fl[:2].clone()
-                    kdist.all_reduce_max(flags, self.group)     # every rank must take the same branch
-                    worst, overflow = flags.tolist()
-                    rescored = 0.0
-                    if self.shard == 'queries' and level_ok:
-                        resc = fl[2:3].clone()
-                        kdist.all_reduce_sum(resc, self.group)
-                        rescored = float(resc.item())
-                        n_pol = kg.n_facts          # (the sum covers every rank's facts)
-                else:   # one device-to-host transfer for the ranks and the flags (16 bytes = two int64)
-                    if host_buf is not None:    # ... which the last finalize launch has made itself
-                        torch.cuda.current_stream(device).synchronize()
-                        packed = host_buf
-                    else:
-                        packed = _to_host(flat)
-                    worst, overflow, rescored, _ = packed[-2:].view(torch.float32).tolist()
-                    res = packed[:-2].view(4, n_local)
-                redo = check_again = False
-                if not worst <= self.model.L2_EXPAND_LIMIT:
-                    self.model._expand_ok = False
-                    redo = True
-                elif overflow == 2.0 and attempt == 0:
-                    # (r06) not the list: a DOT candidate table converted in one pass under the scale of the PREVIOUS
-                    # evaluation's norm maxima has left that binade (Model._dot_fused_problem).  The query pipeline has stored
-                    # the new maxima: the same path again -- a replay of the same graph -- is consistent now
-                    redo = check_again = True
-                elif overflow > 0 and level_now == 1 and attempt == 0 and getattr(self.model, 'split_level', 0) == 'auto':
-                    # the one-product level's wider band overflowed the list: this evaluation again on the three-product
-                    # sweep (whose own flags are then checked like a first run's)
-                    self._level = level_now = 0
-                    # (... and do not come back before the three-product count has halved -- as when LEAVING level 1: an
-                    # evaluator whose level-0 count sits below LEVEL1_ENTER would otherwise enter, overflow and redo on
-                    # every other evaluation)
-                    self._level1_max = 0.5 * (self._level0_seen if self._level0_seen is not None else lvl_enter)
-                    object.__setattr__(self.model, '_split_level', 0)
-                    redo = check_again = True
-                elif overflow > 0:      # more near-ties than the split prefilter's list holds: exact fp32 counts
-                    self.model._split_ok = False
-                    redo = True
-                elif n_local > 0 and (not kdist.multi(world) or (level_ok and (self._shard_flags is not None or n_pol is not None))):
-                    # level policy for the NEXT evaluation, from the pairs this one re-scored (flags[2])
-                    per_q = rescored / (2.0 * (n_pol if n_pol is not None else n_local))
-                    self.last_rescored_per_query = per_q
-                    if level_now == 0 and rescored > 0:
-                        self._level0_seen = per_q
-                        cap_ = lvl_enter if self._level1_max is None else min(lvl_enter, self._level1_max)
-                        if per_q <= cap_ and getattr(self.model, 'split_level', 0) == 'auto':
-                            self._level = 1
-                    elif level_now == 1 and per_q > lvl_leave:
-                        self._level = 0
-                        if self._level0_seen is not None:       # do not come back before the model has changed a lot
-                            self._level1_max = 0.5 * self._level0_seen
-                    if level_now == 1 and rescored > 0:
-                        self._level1_seen = per_q
-                if not redo:
-                    break
-                any_redo = True
-                res = None
-                flat, out, fl = alloc_out()
-                run(*facts(), out, fl)
-                if not check_again:
-                    break
+            if self.graph is not None or self._graph_seen != key:
+                side = self._aux_stream if self._aux_stream is not None else torch.cuda.Stream(device)
+                side.wait_stream(torch.cuda.current_stream(device))
+                with torch.cuda.stream(side):            # warm-up outside capture (lazy inits, attribute sets)
+                    self._run_batches(*run)
+                torch.cuda.current_stream(device).wait_stream(side)
+            if c.segmented and not c.one_graph:
+                g = _GraphSegments()
+                c.cut = g.cut
+                g.begin()
+                try:
+                    self._run_batches(*run)
+                except BaseException:
+                    g.end(sys.exc_info())
+                    raise
+                finally:
+                    c.cut = None
+                g.end()
+            else:   # (one_graph: collectives captured with the kernels, see graph_collectives; 'global' is the default mode)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode='thread_local' if c.one_graph else 'global'):
+                    self._run_batches(*run)
+        except Exception as exc:
+            if self.graph is True:
+                raise
+            warnings.warn('torchkge_amd: hipGraph capture of evaluate() failed (%s); running eagerly' % (exc,))
+            self.graph = False
+            self._graph_failed = True
+            self._graph = self._graph_static = self._graph_key = None
+            self._graph_cache = {}
+            torch.cuda.synchronize(device)
+            self._run_eager(c)
+            return
         finally:
-            self._qb = None
-            self.__dict__['_direct_ptr'] = None
-            object.__setattr__(self.model, '_lp_side_stream', None)
-            if guard is not None:      # never leave the model in guarded mode (exceptions included)
-                self.model.lp_guard_end()
-        if self.shard == 'queries' and kdist.multi(world):
-            out = kdist.all_gather_facts(out, kg.n_facts, self.group)
-        if res is None and host_buf is not None:     # (a redone evaluation: its finalize launches wrote there too)
-            torch.cuda.current_stream(device).synchronize()
-            res = host_buf[:-2].view(4, n_local)
+            if gc_was_on:
+                gc.enable()
+        # what a replay needs to know -- _replay, _replay_captured, and the steady-state path (_evaluate_fast) as it is
+        st.update(graph=g, n_local=c.n_local, level=c.level_now, regions=c.regions_now, direct=c.host_buf is not None,
+                  needs_clean_guard=c.guard is not None,        # (the graph holds no fill of the guard vector)
+                  zeroes_guard=bool(c.guard_zeroed),            # the captured batches ended with a guard-zeroing finalize
+                  shard_flags=c.shard_flags,                    # (entity shards: where the summed flags land)
+                  targets_cat=getattr(self.engine, '_targets_cat', None))      # baked into the graph too
+        if self._graph_key is not None and self._graph is not None:
+            # keep ONE earlier capture (the other split level); older ones go -- outside any capture
+            self._graph_cache = {self._graph_key: (self._graph, self._graph_static)}
+        self._graph, self._graph_static, self._graph_key = g, st, key
+        self._graph_src = None
+
+    def _replay(self, info, guard):
+        """Guard hygiene, replay of the capture whose static state (_capture) is `info`, clean flag."""
+        # (the graph holds no fill of the guard vector: it relies on the previous evaluation's zeroing finalize)
+        if guard is not None and info['needs_clean_guard']:
+            _dirty_guard(self.model, guard)
+        info['graph'].replay()
+        if guard is not None and info['zeroes_guard']:
+            object.__setattr__(self.model, '_lp_guard_clean', True)
+
+    def _replay_captured(self, c):
+        """The current capture on the facts as they are now."""
+        st, kg = self._graph_static, c.kg
+        src = tuple((x.data_ptr(), x._version, c.f_lo, c.f_hi) for x in (kg.head_idx, kg.tail_idx, kg.relations))
+        if src != self._graph_src:      # refresh the graph's static inputs only when the facts changed
+            for dst, x in zip((st['h'], st['t'], st['r']), self._facts(c)):
+                dst.copy_(x, non_blocking=True)
+            self._graph_src = src
+        self._replay(st, c.guard)
+        c.shard_flags = st['shard_flags']
+        c.flat, c.out, c.flags = st['out']
+
+    def _settle(self, c):
+        """Apply the _verdict on the run's flags: accept or run again.  Returns (host ranks if read with the flags, redone?)."""
+        m, st = self.model, self._st
+        split_level = getattr(m, 'split_level', 0)
+        res, n_pol, any_redo = None, None, False
+        for attempt in (0, 1):
+            if c.guard is None:
+                break
+            if c.multi and c.shard_flags is None:
+                flags = c.flags[:2].clone()
+                kdist.all_reduce_max(flags, self.group)     # every rank must take the same branch
+                worst, overflow = flags.tolist()
+                rescored = 0.0
+                if self.shard == 'queries' and c.level_ok:
+                    resc = c.flags[2:3].clone()
+                    kdist.all_reduce_sum(resc, self.group)
+                    rescored = float(resc.item())
+                    n_pol = c.kg.n_facts        # (the sum covers every rank's facts)
+            else:   # one device-to-host transfer for the ranks and the flags (16 bytes = two int64)
+                packed, (worst, overflow, rescored, _) = _read_back(c.host_buf, c.flat)
+                res = packed[:-2].view(4, c.n_local)
+            verdict = _verdict(worst, overflow, c.level_now, attempt, split_level, m.L2_EXPAND_LIMIT)
+            if verdict == ACCEPT:
+                if c.n_local > 0 and (not c.multi or (c.level_ok and (c.shard_flags is not None or n_pol is not None))):
+                    # level policy for the NEXT evaluation, from the pairs this one re-scored (flags[2])
+                    self.last_rescored_per_query = st.observe(
+                        c.level_now, rescored, 2.0 * (n_pol if n_pol is not None else c.n_local), c.thresholds,
+                        split_level == 'auto')
+                break
+            if verdict == REDO_EXPAND:
+                m._expand_ok = False
+            elif verdict == REDO_SPLIT:
+                m._split_ok = False
+            elif overflow != 2.0:       # (not a stale table scale: the one-product level's list overflowed)
+                st.leave_level1(c.thresholds[0])
+                c.level_now = 0
+                object.__setattr__(m, '_split_level', 0)
+            res, any_redo = None, True
+            self._run_eager(c)
+            if verdict != REDO_AGAIN:
+                break
+        return res, any_redo
+
+    def _finish(self, c, res, any_redo):
+        """Results on the host; arm the steady-state path if this was an undisturbed single-GPU replay of the capture."""
+        out = c.out
+        if self.shard == 'queries' and c.multi:
+            out = kdist.all_gather_facts(out, c.kg.n_facts, self.group)
+        if res is None and c.host_buf is not None:     # (a redone evaluation: its finalize launches wrote there too)
+            torch.cuda.current_stream(c.device).synchronize()
+            res = c.host_buf[:-2].view(4, c.n_local)
         if res is None:
             res = _to_host(out)
         self.rank_true_heads, self.rank_true_tails = res[0], res[1]
@@ -1269,17 +1338,13 @@ class LinkPredictionEvaluator(object):
         self._n_evaluations += 1
         # (this evaluation ran twice: guard flag, list overflow, stale table scale)
         self.__dict__['_last_redo'] = any_redo or self.__dict__.pop('_fast_flagged', False)
-        # the next call may replay at once if THIS one was an undisturbed single-GPU replay of the current capture
         self._st._fast = None
-        if (FAST_REPLAY and use_graph and key is not None and self._graph_key == key and not kdist.multi(world)
-                and guard is not None and not any_redo and isinstance(self._graph, torch.cuda.CUDAGraph)
-                and (forced_level != 'auto' or self._level == level_now) and self._regions_for(level_now, False) == regions_now
-                and self._fast_sig(user_b_size) is not None):
-            gst = self._graph_static
-            self._st._fast = (self._fast_sig(user_b_size),
-                              {'graph': self._graph, 'static': gst, 'guard': guard, 'n_local': n_local, 'level': level_now,
-                               'needs_clean_guard': bool(gst.get('needs_clean_guard')), 'zeroes_guard': bool(gst.get('zeroes_guard')),
-                               'direct': direct_now, 'regions': regions_now})
+        if (FAST_REPLAY and c.use_graph and c.key is not None and self._graph_key == c.key and not c.multi
+                and c.guard is not None and not any_redo and isinstance(self._graph, torch.cuda.CUDAGraph)
+                and (c.forced_level != 'auto' or self._level == c.level_now)
+                and self._st.regions_for(c.level_now, False) == c.regions_now):
+            sig = self._fast_sig(c.user_b_size)
+            self._st._fast = (sig, self._graph_static) if sig is not None else None
 
     def _fast_sig(self, b_size):
         """What must be unchanged for the last captured graph to be replayed without the full prologue (cheap to compute:
@@ -1296,12 +1361,7 @@ class LinkPredictionEvaluator(object):
                 id(st._graph), st._plan_gen, id(getattr(kg, '_lazy', None)), self.coalesce, st._mem_fit)
 
     def _regions_for(self, level, multi):
-        """The sweep's uncertain pairs in regions of 32 queries?  From REGION_MIN_LEVEL0 re-scored pairs per query seen on the
-        three-product level -- and, once the one-product level has been measured, from REGION_MIN_LEVEL1 there."""
-        r = bool(level == 1 and not multi and self._level0_seen is not None and self._level0_seen >= REGION_MIN_LEVEL0)
-        if r and self._level1_seen is not None and self._level1_seen < REGION_MIN_LEVEL1:
-            r = False       # (too few pairs to amortise a region's query rows)
-        return r
+        return self._st.regions_for(level, multi)
 
     def _arm_host_out(self, n_local):
         """Direct host results (r06): a fresh pinned (4 n + 2) int64 buffer whose device-visible address goes into the
@@ -1326,52 +1386,25 @@ class LinkPredictionEvaluator(object):
         return host
 
     def _evaluate_fast(self, info):
-        """One steady-state evaluation: guard hygiene, graph replay, ONE device-to-host copy (ranks + flags), the level
-        policy.  False: something needs the full path (nothing has been changed that it would not redo)."""
-        m = self.model
-        guard, n_local = info['guard'], info['n_local']
-        if info['needs_clean_guard']:
-            if not getattr(m, '_lp_guard_clean', False):
-                guard.zero_()
-            object.__setattr__(m, '_lp_guard_clean', False)
-        host = None
-        if info.get('direct'):
-            host = self._arm_host_out(n_local)
-            if host is None:
-                return False
-        info['graph'].replay()
-        if info['zeroes_guard']:
-            object.__setattr__(m, '_lp_guard_clean', True)
-        if host is not None:        # the last finalize of the graph wrote ranks and flags there
-            torch.cuda.current_stream(info['static']['out'][0].device).synchronize()
-            packed = host
-        else:
-            packed = _to_host(info['static']['out'][0])
-        # (the four flag floats straight from the pinned buffer: slicing + view + tolist cost 4 us of GPU idle time per call)
-        worst, overflow, rescored, _ = _FLAGS4.unpack(ctypes.string_at(packed.data_ptr() + 8 * (packed.numel() - 2), 16))
-        if not worst <= m.L2_EXPAND_LIMIT or overflow > 0:
+        """One steady-state evaluation: arm the host buffer, _replay, _read_back, level policy.  False: take the full path."""
+        # (nothing has been changed then that the full path would not redo)
+        m, st = self.model, self._st
+        n_local, level_now = info['n_local'], info['level']
+        host = self._arm_host_out(n_local) if info['direct'] else None
+        if info['direct'] and host is None:
+            return False
+        self._replay(info, m._lp_guard)      # (_fast_sig: still the vector the graph was captured on)
+        packed, (worst, overflow, rescored, _) = _read_back(host, info['out'][0])
+        split_level = getattr(m, 'split_level', 0)
+        if _verdict(worst, overflow, level_now, 0, split_level, m.L2_EXPAND_LIMIT) != ACCEPT:
             # (norm guard / list overflow: the full path replays, sees the same flags and redoes; a stale table scale -- flag
             # value 2 -- is gone in that replay: the query pipeline has stored the new maxima)
             self.__dict__['_fast_flagged'] = True
             return False
-        level_now = info['level']
-        if n_local > 0:
-            lvl_enter, lvl_leave = level1_thresholds(m.n_ent)
-            per_q = rescored / (2.0 * n_local)
-            self.last_rescored_per_query = per_q
-            if level_now == 0 and rescored > 0:
-                self._level0_seen = per_q
-                cap_ = lvl_enter if self._level1_max is None else min(lvl_enter, self._level1_max)
-                if per_q <= cap_ and getattr(m, 'split_level', 0) == 'auto':
-                    self._level = 1
-            elif level_now == 1 and per_q > lvl_leave:
-                self._level = 0
-                if self._level0_seen is not None:
-                    self._level1_max = 0.5 * self._level0_seen
-            if level_now == 1 and rescored > 0:
-                self._level1_seen = per_q
-                if self._regions_for(1, False) != info.get('regions'):
-                    self._st._fast = None       # (the next call decides about the regions again: full path, another capture)
+        self.last_rescored_per_query = st.observe(level_now, rescored, 2.0 * n_local, level1_thresholds(m.n_ent),
+                                                  split_level == 'auto')
+        if level_now == 1 and rescored > 0 and st.regions_for(1, False) != info['regions']:
+            st._fast = None     # (the next call decides about the regions again: full path, another capture)
         # (the four rank vectors are rows of this host tensor, handed out on access -- _rank_row: four view objects built
         # here cost 5 us between two replays)
         self.__dict__['_rank_rows'] = packed.as_strided((4, n_local), (n_local, 1))
@@ -1463,14 +1496,6 @@ def _forward(name):
 
 for _n in _EvalState.SHARED:        # evaluator attributes that live in the (possibly shared) _EvalState
     setattr(LinkPredictionEvaluator, _n, _forward(_n))
-
-
-class _NullCtx(object):
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 
 class RelationPredictionEvaluator(object):
