@@ -672,6 +672,141 @@ def test_level_policy_of_the_split_prefilter():
     assert (st._level, st._level1_max) == (0, 1.5)
 
 
+def test_split_operand_of_every_model_family(monkeypatch):
+    """Model._split_operand, the one place that builds the candidate side of the f16-split prefilter (``LpProblem.split``),
+    driven through the model methods that call it, with the table kernels replaced by recording stubs on CPU tensors:
+    for every family x level the dict's exact key set, the guard slot every scalar of it views, the launches in order,
+    and nothing but the query side on a second call inside one lp_session().  The expected rows restate what the six
+    hand-written dict literals built before there was one method."""
+    import types
+    guard = torch.zeros(8)
+    calls = []
+
+    def slot(v):        # guard slot a one-element tensor views; 'own': a scalar of its own; None
+        if v is None:
+            return None
+        return v.storage_offset() if v.untyped_storage().data_ptr() == guard.untyped_storage().data_ptr() else 'own'
+
+    def row_sqnorm(X, K=None, max_io=None, bound_only=False):
+        calls.append(('row_sqnorm', slot(max_io), bound_only))
+        return torch.zeros(X.shape[0])
+
+    def absmax(x, max_io):
+        calls.append(('absmax', slot(max_io)))
+        return max_io
+
+    def split_table(X, K=None, aug=None, X1=None, K1=None, dot=False, nmax0=None, nmax1=None):
+        calls.append(('split_table', dot, X1 is not None, slot(nmax0), slot(nmax1), aug is not None))
+        return torch.zeros(4, dtype=torch.uint8), torch.zeros(2)
+
+    def hi_table(X, K=None, aug=None, X1=None, K1=None, dot=False, nmax0=None, nmax1=None, frag=False):
+        calls.append(('hi_table', dot, X1 is not None, slot(nmax0), slot(nmax1), aug is not None, bool(frag)))
+        return torch.zeros(4, dtype=torch.uint8), torch.zeros(1)
+
+    prep_ok = [True]
+
+    def table_prep_l2(E, emax_io, de2max_io, deferred_max=False, K=None):
+        calls.append(('table_prep_l2', slot(emax_io), slot(de2max_io), deferred_max))
+        return (torch.zeros(E.shape[0]), torch.zeros(4, dtype=torch.uint8), torch.zeros(2)) if prep_ok[0] else None
+
+    def lp_query_pipeline(side, E, R, h, t, r, en, emax, qmax_io, e2pref=None, cols=None, level=0, de2max=None, tp_bmax=None,
+                          zero_counts=False, regions=False):
+        calls.append(('lp_query_pipeline', slot(emax), slot(qmax_io), level, slot(de2max), tp_bmax is not None,
+                      e2pref is not None))
+        return {'Q': torch.zeros(h.shape[0], E.shape[1]), 'qn': torch.zeros(h.shape[0])}
+
+    stream_ok = [False]
+    for name, fn in (('row_sqnorm', row_sqnorm), ('absmax', absmax), ('split_table', split_table), ('hi_table', hi_table),
+                     ('table_prep_l2', table_prep_l2), ('lp_query_pipeline', lp_query_pipeline),
+                     ('hi_stream_ok', lambda K: calls.append(('hi_stream_ok', K)) or stream_ok[0]),
+                     ('split_accum_model', lambda: calls.append(('split_accum_model',)) or 1),
+                     ('LpProblem', lambda *a, **k: types.SimpleNamespace(split=None, sad=None, pre=None, cols=None))):
+        monkeypatch.setattr(_hip, name, fn)
+
+    N, d = 11, 8
+    T0, T1, q, X = torch.ones(N, d), torch.ones(N, d), torch.ones(3, d), torch.ones(3, N)
+    yc, en, idx = torch.ones(N), torch.zeros(N), torch.zeros(3, dtype=torch.int64)
+
+    def fake_prob():
+        return types.SimpleNamespace(split=None, desc=types.SimpleNamespace(c_base=0))
+
+    # family -> (model, call that returns the problem, candidate-side launches at level 0, level-1 table launch without
+    #            its `frag`, key set at level 0, slots of the level-independent views)
+    rs, own = 'row_sqnorm', 'own'
+    base = {'Es', 'e2pref', 'enmax', 'overflow'}
+    families = {
+        # TransE-L2 off the fused path (TranslationModel._translational_problem): three products whatever the level, and no
+        # list_stat -- as before
+        'l2_plain': (tk.TransEModel(d, N, 3), lambda m: m._translational_problem(q, T0),
+                     [(rs, 1, False), (rs, 0, False), ('split_table', False, False, None, None, True)], None,
+                     base, {'enmax': 1, 'overflow': 2}),
+        'l2_fused': (tk.TransEModel(d, N, 3), lambda m: m._fused_query_problem(idx, idx, idx, _hip.SIDE_TAIL, [T0, T1]),
+                     [(rs, 1, False), ('split_table', False, False, None, None, True)],
+                     ('hi_table', False, False, None, None, True),
+                     base | {'list_stat'}, {'enmax': 1, 'overflow': 2, 'list_stat': 6}),
+        'proj': (tk.TransHModel(d, N, 3), lambda m: m._attach_proj_split(fake_prob(), T0, en, X, None, None),
+                 [('absmax', 3), ('split_table', False, False, None, None, True)], ('hi_table', False, False, None, None, True),
+                 base | {'list_stat', 'xabsmax', 'yabsmax'}, {'enmax': 1, 'overflow': 2, 'list_stat': 6, 'xabsmax': 3}),
+        'proj_yc': (tk.TransDModel(d, d, N, 3), lambda m: m._attach_proj_split(fake_prob(), T0, en, X, yc, d),
+                    [('absmax', 3), ('absmax', 4), ('split_table', False, False, None, None, True)],
+                    ('hi_table', False, False, None, None, True), base | {'list_stat', 'xabsmax', 'yabsmax'},
+                    {'enmax': 1, 'overflow': 2, 'list_stat': 6, 'xabsmax': 3, 'yabsmax': 4}),
+        'dot1': (tk.DistMultModel(d, N, 3), lambda m: m._attach_dot_split(fake_prob(), T0),
+                 [(rs, 1, True), ('split_table', True, False, 1, None, False)], ('hi_table', True, False, 1, None, False),
+                 base | {'list_stat', 'enmax1'}, {'enmax': 1, 'overflow': 2, 'list_stat': 6}),
+        'dot2': (tk.ComplExModel(d, N, 3), lambda m: m._attach_dot_split(fake_prob(), T0, T1),
+                 [(rs, 1, True), (rs, 5, True), ('split_table', True, True, 1, 5, False)],
+                 ('hi_table', True, True, 1, 5, False),
+                 base | {'list_stat', 'enmax1'}, {'enmax': 1, 'enmax1': 5, 'overflow': 2, 'list_stat': 6}),
+    }
+    viewed = ('enmax', 'enmax1', 'overflow', 'xabsmax', 'yabsmax', 'list_stat', 'de2max')
+    # level: (split_level, level the evaluator's policy runs, free-running kernel takes the width, fused table preparation
+    #         takes the table)
+    levels = {'three': (0, 1, False, True), 'policy_three': ('auto', 0, True, True), 'planar': (1, 0, False, True),
+              'frag': ('auto', 1, True, True), 'frag_unfused': (1, 0, True, False)}
+    for fam, (m, problem, launches0, hi, keys0, views0) in families.items():
+        for lname, (forced, running, stream_ok[0], prep_ok[0]) in levels.items():
+            m.split_level = forced
+            object.__setattr__(m, '_split_level', running)      # (as LinkPredictionEvaluator sets it)
+            object.__setattr__(m, '_lp_guard', guard)
+            object.__setattr__(m, '_guard_on', True)
+            level1 = (running if forced == 'auto' else forced) == 1 and hi is not None
+            decide = [('split_accum_model',), ('hi_stream_ok', m._lp_width())] if level1 else []
+            if not level1:
+                want, keys, views = list(launches0), set(keys0), dict(views0)
+            else:
+                want = launches0[:-1] + [hi + (stream_ok[0],)]
+                keys = (keys0 | {'level', 'de2max', 'es_frag'})
+                views = dict(views0, de2max=own)
+            pipeline = []
+            if fam == 'l2_fused':       # the level is chosen first: the query pipeline's launch depends on it
+                if level1 and stream_ok[0] and prep_ok[0]:      # norms + table + residual maximum from ONE launch
+                    want, views['de2max'] = [('table_prep_l2', 1, 7, True)], 7
+                elif level1 and stream_ok[0]:
+                    want = [('table_prep_l2', 1, 7, True)] + want
+                pipeline = [('lp_query_pipeline', 1, 0, int(level1), views.get('de2max'), want[0][0] == 'table_prep_l2'
+                             and prep_ok[0], not level1)]
+                want = decide + want + pipeline
+            elif fam == 'l2_plain':
+                want = want[:]
+            else:                       # the bounds and maxima first, then the level and the table
+                want = want[:-1] + decide + want[-1:]
+            with m.lp_session():
+                del calls[:]
+                sp = problem(m).split
+                assert calls == want, (fam, lname, calls)
+                assert set(sp) == keys, (fam, lname, sorted(sp))
+                assert int(sp.get('level', 0)) == int(level1) and bool(sp.get('es_frag')) == (level1 and stream_ok[0])
+                assert {k: slot(sp.get(k)) for k in viewed} == {k: views.get(k) for k in viewed}, (fam, lname)
+                assert (sp['e2pref'] is None) == level1
+                del calls[:]            # the tables cannot change inside a session: the query side only
+                sp2 = problem(m).split
+                query_side = [(rs, 0, False)] if fam == 'l2_plain' else decide + pipeline
+                assert calls == query_side, (fam, lname, calls)
+                assert sp2['Es'] is sp['Es'] and set(sp2) == keys
+            m.lp_guard_end()
+
+
 def test_verdict_on_the_guard_flags():
     """evaluation._verdict, the one reading of the flags behind the ranks (the redo loop of evaluate() applies it, the
     steady-state path asks it whether the full path is needed): exactly one of four outcomes; a NaN norm sum means redo."""

@@ -76,13 +76,14 @@ def split_for(variant):
 
 
 for variant in VARIANTS:
-    os.environ.pop('KGE_HC_FORCE', None)    # 'hs': the resident-panel free-running kernel (rows <= 32 units)
-    os.environ.pop('KGE_HS_NT', None)
+    os.environ.pop('KGE_HS_NT', None)       # 'hs': the resident-panel free-running kernel (rows <= 32 units)
     if variant in ('hs3', 'hs4'):           # ... with 96- / 128-query panels
         os.environ['KGE_HS_NT'] = variant[2]
     if variant in ('hc3', 'hc4'):
+        if (K + 2 + 15) // 16 <= 32:
+            sys.exit('%s: K = %d is %d units; rows of at most 32 units run on the resident-panel kernel (hs, hs3, hs4), '
+                     'the chunked-panel kernel takes longer rows only' % (variant, K, (K + 2 + 15) // 16))
         os.environ['KGE_HC_NT'] = variant[2]
-        os.environ['KGE_HC_FORCE'] = '1'
     guard[2] = 0
     prob.split = split_for(variant)
     prep = prob.split_prepare()

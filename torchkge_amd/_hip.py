@@ -798,24 +798,9 @@ def table_prep_l2(E, emax_io, de2max_io, deferred_max=False, K=None):
 
 # the uncertain-pair list of the free-running sweep cut into regions of 32 queries, re-scored with the region's query rows
 # resident in LDS (kge_lp_split_recheck_regions); KGE_REGION_RECHECK=0: the one global list
-# the count sweep of a fused-query-side batch as TWO launches over the halves of the queries, the first half's region recheck on
-# a side stream beside the second half's sweep (LpProblem._count_ge_split_halves)
-SWEEP_HALVES = os.environ.get('KGE_SWEEP_HALVES', '0') == '1'
-_HALVES_STREAMS = {}
-
-
-def _halves_stream(device):
-    key = str(device)
-    s = _HALVES_STREAMS.get(key)
-    if s is None:
-        s = _HALVES_STREAMS[key] = torch.cuda.Stream(device)
-    return s
-
-
+# (the fused query pipelines only: for TransH / TransD, ~5 listed pairs per query, a region's fixed cost -- 26 KB of query rows
+# for ~170 pairs -- outweighs the rows it saves: 0.64 -> 0.66 ms, profiles/r05/region_recheck_ab.txt)
 REGION_RECHECK = os.environ.get('KGE_REGION_RECHECK', '1') == '1'
-# ... for the projection models too (TransH / TransD, ~5 listed pairs per query: a region's fixed cost -- 26 KB of query rows
-# for ~170 pairs -- outweighs the rows it saves: 0.64 -> 0.66 ms, profiles/r05/region_recheck_ab.txt; off)
-REGION_RECHECK_PROJ = os.environ.get('KGE_REGION_RECHECK_PROJ', '0') == '1'
 
 
 def _counts_and_regions(Bq, dev, regions):
@@ -1096,7 +1081,6 @@ class LpProblem(object):
         self.pre = None         # outputs of the fused query pipeline (true scores, split queries, thresholds)
         self.cols = None        # filter_index.ColumnPlan of a both-sides batch: split count over distinct query rows
         self.pre_q = None       # (Qh, q_dn2): the queries' planar hi operand, already built (projection models, level 1)
-        self.region_count = None    # zeroed region counters of the sweep's uncertain-pair list (wants_regions)
         self.split_true = None  # (s_true tensor, true ids): the thresholds are the exact scores of these pairs (evaluator)
 
     def scores(self, out=None):
@@ -1187,20 +1171,6 @@ class LpProblem(object):
                    'kge_lp_count_ge')
         return raw
 
-    def wants_regions(self):
-        """Region counters the caller may zero for this problem's sweep (set them as ``self.region_count``): the
-        free-running sweep without a fused query pipeline (TransH / TransD) -- 0 when the regions do not apply."""
-        sp = self.split
-        if (not REGION_RECHECK or not REGION_RECHECK_PROJ or sp is None or self.pre is not None or self.pre_q is None or not sp.get('es_frag')
-                or int(sp.get('level', 0)) != 1 or self.B == 0 or self.N == 0):
-            return 0
-        if self.cols is not None and self.cols.n_multi_p == 0:
-            return 0        # (single-query columns keep their column -> query map; grouped ones fall back to per query)
-        lib = load_library()
-        if not int(lib.kge_lp_split_regions_supported(ctypes.byref(self.desc))):
-            return 0
-        return int(lib.kge_lp_split_regions(self.B))
-
     def split_prepare(self):
         """Per-batch operands of the f16-split prefilter: the split query matrix and
         the scratch buffers (thresholds, uncertain-pair list, its counter)."""
@@ -1247,11 +1217,9 @@ class LpProblem(object):
                 Qs = split_rows(A0, K=K, is_query=True, aug=qn, X1=A1, dot=True, nmax0=qmax[0:1],
                                 nmax1=qmax[1:2] if A1 is not None else None, cell_ss=want_ss)
                 extra = {'qn0': qn0, 'qn1': qn1, 'qmax': qmax}
-        elif level == 1 and getattr(self, 'pre_q', None) is not None and self.cols is None:
+        elif level == 1 and self.pre_q is not None and self.cols is None:
             Qs, dn2 = self.pre_q        # (the projection models' query preparation wrote the hi operand in its own launch)
             extra = {'cols': None, 'q_dn2': dn2}
-            if getattr(self, 'region_count', None) is not None and self.split.get('es_frag'):
-                extra['region_count'] = self.region_count
         elif level == 1:                # L2 on the one-product level (non-fused query path)
             cols = self.cols
             Qs, dn2 = hi_rows(A0, K=K, is_query=True, want_dn2=True, row_index=None if cols is None else cols.rep)
@@ -1324,7 +1292,7 @@ class LpProblem(object):
                                      hi_stream_groups_ok(int(self.desc.mode), int(self.desc.K0) + int(self.desc.K1))), \
                 'grouped columns on the free-running sweep: plain-threshold modes on resident panels only'
             # s_true IS the exact score of (query, split_true entity): the sweep need not list that pair
-            st_true = getattr(self, 'split_true', None)
+            st_true = self.split_true
             if st_true is not None and st_true[0] is s_true:
                 a.true_idx = _p(i64c(st_true[1]))
         if a.level == 1:        # one-product level: the band needs the operands' measured f16 residuals
@@ -1380,81 +1348,14 @@ class LpProblem(object):
         self.last_split = (n_list, (Qi, thr, lst))      # kept alive until the launches have run; tests read n_list
         return raw
 
-    def _count_ge_split(self, s_true, raw, between=None):
+    def _count_ge_split(self, s_true, raw):
         """Same counts as kge_lp_count_ge through the certified f16-split
         prefilter + exact recheck of the pairs inside the error band;
-        self.split = {'Es', 'enmax', 'overflow'} is set by the model.
-        ``between``: called after the sweep is enqueued and before the recheck (the evaluator forks its filter correction
-        there: beside the recheck instead of beside the sweep)."""
+        self.split = {'Es', 'enmax', 'overflow'} is set by the model."""
         prep = self.split_prepare()
-        if self._sweep_in_halves(prep, s_true):
-            return self._count_ge_split_halves(prep, s_true, raw, between)
         self.split_count(prep, s_true, raw)
-        if between is not None:
-            between()
         self.split_recheck(prep, s_true, raw)
         self.last_split = (prep['n_list'], prep)     # kept alive until the launches have run; tests read n_list
-        return raw
-
-    # ---- the sweep in two halves, the first half's exact recheck beside the second half's sweep (r06) -------------------------
-    def _sweep_in_halves(self, prep, s_true):
-        """Applies where the sweep's uncertain pairs go to REGIONS (free-running kernel, fused query side with ready thresholds,
-        K <= 256): a region belongs to 32 consecutive queries, so the queries [0, H) and [H, B) are two independent problems
-        on the same operands -- same kernels, pointers advanced -- and the recheck of the first need not wait for the second."""
-        if not SWEEP_HALVES or prep.get('region_count') is None or not self.split.get('es_frag') or prep.get('cols') is not None:
-            return False
-        if prep.get('s_true_pre') is not s_true or prep.get('thr_used') or self.desc.K1 or int(self.desc.mode) not in (LP_L2_EXPAND, LP_DOT):
-            return False
-        return self.B >= 8 * 192 and s_true.is_cuda
-
-    def _count_ge_split_halves(self, prep, s_true, raw, between=None):
-        lib = load_library()
-        if not int(lib.kge_lp_split_regions_supported(ctypes.byref(self.desc))):
-            prep['region_count'] = None
-            self.split_count(prep, s_true, raw)
-            if between is not None:
-                between()
-            self.split_recheck(prep, s_true, raw)
-            self.last_split = (prep['n_list'], prep)
-            return raw
-        import copy as _copy
-        Bp = int(lib.kge_lp_split_rows_padded(self.B, 1))
-        H = (Bp // 2) // 192 * 192                      # whole 192-row padding units: the halves pad like the whole
-        K = int(self.desc.K0) + int(self.desc.K1)
-        row_bytes = int(lib.kge_lp_hi_units(K)) * 32
-        cap_h = int(prep['cap']) // 2
-        st_true = getattr(self, 'split_true', None)
-        halves = []
-        for q0, q1, li in ((0, H, 0), (H, self.B, 1)):
-            sp = _copy.copy(self)
-            d = LpDesc.from_buffer_copy(self.desc)
-            d.B = q1 - q0
-            d.A0 = self.desc.A0 + 4 * q0 * self.desc.lda0
-            if self.desc.qn:
-                d.qn = self.desc.qn + 4 * q0
-            sp.desc, sp.B = d, q1 - q0
-            s_sub = s_true[q0:q1]
-            sp.split_true = (s_sub, st_true[1][q0:q1]) if (st_true is not None and st_true[0] is s_true) else None
-            sp._regions_used = False
-            pp = {'Qs': prep['Qs'][q0 * row_bytes:], 'thr': prep['thr'][2 * q0:], 'cap': cap_h,
-                  'list': prep['list'][2 * cap_h * li:2 * cap_h * (li + 1)], 'n_list': prep['n_list'], 'cols': None,
-                  's_true_pre': s_sub, 'region_count': prep['region_count'][(q0 // 32):], 'q_dn2': prep.get('q_dn2'),
-                  'q_dn2_per_query': prep.get('q_dn2_per_query')}
-            halves.append((sp, pp, s_sub, raw[q0:q1]))
-        main = torch.cuda.current_stream(self.device)
-        side = _halves_stream(self.device)
-        (p0, pp0, s0, r0), (p1, pp1, s1, r1) = halves
-        p0.split_count(pp0, s0, r0)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            p0.split_recheck(pp0, s0, r0)
-        p1.split_count(pp1, s1, r1)
-        if between is not None:
-            between()
-        p1.split_recheck(pp1, s1, r1)
-        main.wait_stream(side)
-        prep['thr_used'] = True
-        self.last_split = (prep['n_list'], (prep, pp0, pp1))
         return raw
 
     def filter_sub(self, s_true, true_idx, seg_lo, seg_hi, targets, sub=None, found=None, grouped=False, plan=None):

@@ -611,8 +611,8 @@ template <int NW, int PM>
 int hs_dispatch_units(const kge_hi_stream_params &p, int grid, int smem, int nt, hipStream_t s)
 {
     if (nt == 4) {              // 128-query panels (kge_hi_stream_launch: PM = 0, one query per column)
-        if (p.units == 13) return hs_launch<NW, 13, PM, 0, 0, 4>(p, grid, smem, s);
         if constexpr (PM == 0) {
+            if (p.units == 13) return hs_launch<NW, 13, 0, 0, 0, 4>(p, grid, smem, s);
             if (p.units == 26) return hs_launch<NW, 26, 0, 0, 0, 4>(p, grid, smem, s);
             return hs_launch<NW, 0, 0, 0, 0, 4>(p, grid, smem, s);
         }
@@ -659,7 +659,7 @@ int kge_hi_stream_launch(kge_hi_stream_params p, int pm, int num_cus, hipStream_
     const int RS = p.units * 32 + 16;
     // (r06) 128-query panels for plain thresholds, one query per column: every candidate fragment feeds four MFMAs instead of three
     // (KGE_HS_NT=3: the 96-query panels of r05)
-    const int nt = ((pm == 0 || (p.units == 13 && kge_env_int("KGE_HS_NT_PM", 0))) && !p.members &&
+    const int nt = (pm == 0 && !p.members &&
                     kge_env_int("KGE_HS_NT", HS_NT_DEFAULT) == 4 && kge_env_int("KGE_HS_PROBE", 0) == 0 &&
                     128 * RS + 8 * HS_WLIST * 8 + 128 * 20 <= 160 * 1024) ? 4 : 3;
     const int tq = 32 * nt;

@@ -2532,11 +2532,10 @@ extern "C" int kge_lp_dot_table_prep(const float *X0, int64_t ld0, int K0, const
     p.dn2 = nullptr; p.dn2max = nullptr; p.row_index = nullptr;
     p.frag = frag ? 1 : 0;
     p.nm_bmax = ws; p.nm_blocks = nb; p.dn_bmax = dn_block_max; p.prev_nmax = nullptr; p.nm_out = nullptr;
-    // fragment-major tables of float4-readable rows: the coalesced kernel (KGE_HIROWS_OLD=1: the general one, for A/B runs)
-    static const int old_only = getenv("KGE_HIROWS_OLD") ? atoi(getenv("KGE_HIROWS_OLD")) : 0;
+    // fragment-major tables of float4-readable rows: the coalesced kernel; unaligned or planar ones: the general one
     const bool vec = K0 % 4 == 0 && K1 % 4 == 0 && ld0 % 4 == 0 && ((size_t)X0 & 15) == 0 &&
                      (K1 == 0 || (ld1 % 4 == 0 && ((size_t)X1 & 15) == 0));
-    if (frag && vec && !old_only)
+    if (frag && vec)
         hipLaunchKernelGGL(hi_rows_frag_kernel<false>, dim3(kge_lp_dot_table_prep_blocks(rows, 1)), dim3(256), 0, kge_s(stream), p);
     else
         hipLaunchKernelGGL(hi_rows_kernel, dim3(kge_lp_dot_table_prep_blocks(rows, 1)), dim3(256), 0, kge_s(stream), p);
@@ -2693,10 +2692,8 @@ extern "C" int kge_lp_split_count(const kge_lp_desc *d, const kge_split_args *a,
     const int slots = split_num_cus();
     if (a->es_frag) {
         // the free-running one-product kernel (lp_hi_stream.hip): fragment-major candidate table, resident query panel
-        // long rows: the panel streamed in chunks (lp_hi_chunk.hip); KGE_HC_FORCE=1: also where the resident panel would fit (A/B)
-        const bool chunked = units > kge_hi_stream_max_units() ||
-                             (kge_env_int("KGE_HC_FORCE", 0) && kge_hi_chunk_supported(units) && !a->members && !a->region_count &&
-                              d->mode < KGE_LP_L2_PROJH);
+        // long rows: the panel streamed in chunks (lp_hi_chunk.hip)
+        const bool chunked = units > kge_hi_stream_max_units();
         const bool grouped = a->members && a->n_multi_p > 0;         // r06: + a second launch over the grouped columns
         if (!lv1 || (chunked && !kge_hi_chunk_supported(units))) return KGE_EINVAL;
         if ((a->members != nullptr) != (a->n_multi_p > 0) || (grouped && (chunked || proj || a->region_count || !a->col_q)))

@@ -44,7 +44,7 @@ from . import _hip
 from . import distributed as kdist
 from .exceptions import NotYetEvaluatedError
 from .filter_index import ColumnPlan, filter_index_for, KEY2_SPAN, FilterPlan
-from .models.interfaces import Model as _BaseModel
+from .models.interfaces import Model as _BaseModel, guard_slot, G_QMAX, G_EMAX, G_OVERFLOW, G_RESCORED
 from .utils.data import get_n_batches
 from .utils.modeling import filter_scores
 from .utils.operations import get_rank
@@ -167,19 +167,14 @@ class HipRankEngine(object):
         hipGraph of evaluate() as two parallel branches)."""
         pre_counts = prob.pre.pop('counts', None) if getattr(prob, 'pre', None) is not None else None
         if pre_counts is None and getattr(prob, 'zero_counts', None) is not None:
-            # TransH / TransD: zeroed by kge_proj_query_stats' launch -- unless this sweep wants region counters zeroed too
+            # TransH / TransD: zeroed by kge_proj_query_stats' launch
             zc, prob.zero_counts = prob.zero_counts, None
-            if pad == 0 and not (prob.wants_regions() if hasattr(prob, 'wants_regions') else 0):
+            if pad == 0:
                 pre_counts = zc
         if pre_counts is not None and pad == 0 and tuple(pre_counts.shape) == (3, prob.B):
             out = pre_counts        # zeroed by the fused query pipeline's launch: no fill node
         else:
-            # (+ the region counters of the sweep's uncertain-pair list where they apply -- TransH / TransD: the same fill)
-            nreg = prob.wants_regions() if (pad == 0 and hasattr(prob, 'wants_regions')) else 0
-            buf = torch.zeros(3 * (prob.B + pad) + nreg, dtype=torch.int32, device=s_true.device)
-            out = buf[:3 * (prob.B + pad)].view(3, prob.B + pad)
-            if nreg:
-                prob.region_count = buf[3 * (prob.B + pad):]
+            out = torch.zeros(3, prob.B + pad, dtype=torch.int32, device=s_true.device)
         # (only beside the split-prefilter count kernel -- one persistent workgroup per CU that leaves 30 KB of LDS and a
         # fifth of the registers free; the fp32 tile kernel runs TWO workgroups per CU and loses one of them to a
         # co-resident kernel's LDS: measured 2.44 -> 3.37 ms per evaluate with --no-split)
@@ -188,16 +183,6 @@ class HipRankEngine(object):
             prob.filter_sub(s_true, true_idx, seg_lo, seg_hi, targets, out[1], out[2], grouped=True, plan=plan)
             return out
         main = torch.cuda.current_stream(s_true.device)
-        if FILTER_BESIDE_RECHECK and prob.B > 0 and prob.N > 0:
-            # the filter correction forked BEHIND the count sweep, beside its exact recheck (both are short, L2-bound kernels;
-            # the sweep -- one or two persistent workgroups per CU -- then has the chip to itself)
-            def fork():
-                aux.wait_stream(main)
-                with torch.cuda.stream(aux):
-                    prob.filter_sub(s_true, true_idx, seg_lo, seg_hi, targets, out[1], out[2], grouped=True, plan=plan)
-            prob._count_ge_split(s_true, out[0], between=fork)
-            main.wait_stream(aux)
-            return out
         aux.wait_stream(main)
         if count_first:
             prob.count_ge(s_true, out[0])
@@ -368,8 +353,6 @@ class _EvalState(object):
 
 _STATES = weakref.WeakKeyDictionary()       # model -> {(id(kg), options): _EvalState}
 SHARE_STATE = os.environ.get('KGE_SHARE_EVAL_STATE', '1') != '0'
-# the filter correction of the second stream beside the exact recheck (1) instead of beside the count sweep (0)
-FILTER_BESIDE_RECHECK = os.environ.get('KGE_FILTER_BESIDE_RECHECK', '0') == '1'
 # steady-state evaluate() calls skip the full prologue (LinkPredictionEvaluator._fast_sig / _evaluate_fast, r06)
 FAST_REPLAY = os.environ.get('KGE_FAST_REPLAY', '1') != '0'
 _FLAGS4 = struct.Struct('4f')
@@ -769,9 +752,10 @@ class LinkPredictionEvaluator(object):
         counts = eng.partial_counts(prob, s_true, true_idx, seg_lo, seg_hi, targets, **kw)
         if ride:
             lim = float(self.model.L2_EXPAND_LIMIT)
-            counts[0, n2:n2 + 1] = ((guard[0:1] + guard[1:2]) > lim).to(torch.int32) if lim != float('inf') else 0
-            counts[0, n2 + 1:n2 + 2] = (guard[2:3] > 0).to(torch.int32)
-            counts[0, n2 + 2:n2 + 3] = guard[6:7].to(torch.int32)      # pairs this shard re-scored (level policy: their SUM)
+            counts[0, n2:n2 + 1] = ((guard_slot(guard, G_QMAX) + guard_slot(guard, G_EMAX)) > lim).to(torch.int32) \
+                if lim != float('inf') else 0
+            counts[0, n2 + 1:n2 + 2] = (guard_slot(guard, G_OVERFLOW) > 0).to(torch.int32)
+            counts[0, n2 + 2:n2 + 3] = guard_slot(guard, G_RESCORED).to(torch.int32)   # pairs this shard re-scored (level policy: their SUM)
         if sharded:     # (the recorded call runs again at every graph replay: bind the tensor, not the name)
             self._collective(c, lambda c_=counts, g_=self.group: kdist.all_reduce_sum(c_, g_))
         if ride:
@@ -1181,9 +1165,9 @@ class LinkPredictionEvaluator(object):
             elif guard is not None and not c.fl_done:
                 # [max ||q||^2 + max ||e||^2, split-prefilter overflow] behind the ranks (the both-sides path
                 # has the last batch's finalize write them)
-                torch.add(guard[0:1], guard[1:2], out=fl[0:1])
-                fl[1:2].copy_(guard[2:3])
-                fl[2:3].copy_(guard[6:7])
+                torch.add(guard_slot(guard, G_QMAX), guard_slot(guard, G_EMAX), out=fl[0:1])
+                fl[1:2].copy_(guard_slot(guard, G_OVERFLOW))
+                fl[2:3].copy_(guard_slot(guard, G_RESCORED))
             c.fl = None
             if guard is not None and c.guard_zeroed:
                 object.__setattr__(self.model, '_lp_guard_clean', True)

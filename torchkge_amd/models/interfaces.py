@@ -132,10 +132,25 @@ def _table_of(cand):
 
 # the DOT models' query side of a batch in one launch (kge_lp_dot_query_pipeline); KGE_DOT_FUSED=0: the separate kernels
 DOT_FUSED = os.environ.get('KGE_DOT_FUSED', '1') == '1'
-# TransH / TransD with the evaluator's second stream: which side of the preparation runs there (KGE_PREP_SIDE_SWAP=0: the candidate side; r06 same-box 0.565 -> 0.559 / 0.602 -> 0.597 ms with the query side there)
-PREP_SIDE_SWAP = os.environ.get('KGE_PREP_SIDE_SWAP', '1') == '1'
 # ... and their candidate table in one pass from the second evaluation on (kge_lp_dot_table_prep_fused); KGE_DOT_PREP_ONE_PASS=0: two
 DOT_PREP_ONE_PASS = os.environ.get('KGE_DOT_PREP_ONE_PASS', '1') != '0'
+
+
+# Slots of the evaluation-time guard vector (Model._lp_guard: device, float32 x 8).  The C side and the tests address them
+# by these numbers.
+G_QMAX = 0          # max ||q||^2 (L2 norm guard)
+G_EMAX = 1          # max ||e||^2 of the candidates (DOT: segment 0)
+G_OVERFLOW = 2      # the uncertain-pair list overflowed
+G_XABS = 3          # projection modes: max |X|    (TransE-L1 SAD prefilter: max |E|)
+G_YABS = 4          # projection modes: max |y_c|  (TransE-L1 SAD prefilter: max |R|)
+G_EMAX1 = 5         # DOT: max ||e||^2 of segment 1
+G_RESCORED = 6      # pairs the exact recheck re-scored (kge_split_args' list_stat)
+G_DE2MAX = 7        # max ||e - hi(e)||^2, the candidates' f16 residual (one-product level)
+
+
+def guard_slot(guard, slot):
+    """One-element view of a guard slot: what the kernels take as a device scalar."""
+    return guard[slot:slot + 1]
 
 
 class Model(Module):
@@ -151,9 +166,9 @@ class Model(Module):
         self.n_rel = n_relations
         self._cache = _SessionCache()
         self._row_shard = None      # (lo, hi): the entity tables hold only these rows (one shard per GPU)
-        # evaluation-time guard scalars (device, float32 x 8): [0] max ||q||^2 (L2 norm guard),
-        # [1] max ||e||^2 (segment 0), [2] split-list overflow flag, [3] max |X|, [4] max |y_c| (projection
-        # modes), [5] max ||e||^2 (segment 1)
+        # evaluation-time guard scalars (device, float32 x 8): [0] max ||q||^2 (L2 norm guard), [1] max ||e||^2
+        # (segment 0), [2] split-list overflow flag, [3] max |X|, [4] max |y_c| (projection modes; TransE-L1: max |E|,
+        # max |R|), [5] max ||e||^2 (segment 1), [6] re-scored pairs, [7] max f16 residual of the candidates: G_* above
         self._lp_guard = None
         self._lp_guard_clean = False    # the guard vector is all zero (left so by the last evaluation's finalize launch)
         self._guard_on = False
@@ -362,33 +377,77 @@ class Model(Module):
         _set(self, '_expand_ok', None)
         _set(self, '_split_ok', True)
 
+    def _level_and_frag(self):
+        """(one-product level?, and on the free-running kernel's fragment-major table?) for the running evaluation."""
+        lvl1 = self._use_level1()
+        return lvl1, lvl1 and self._level1_stream()
+
+    def _cand_norms(self, key, table, K, frag):
+        """(prep, en) of an L2 candidate table: ||e||^2 by the reference chain, maximum to the guard -- on the free-running
+        sweep from ONE launch with the fragment-major hi table and its residual maximum (kge_lp_table_prep_l2; ``prep`` =
+        (en, table, block maxima) for _split_operand, None where shape / alignment need the separate kernels).  The two
+        maxima stay per block -- hundreds of same-address atomics would serialise -- until a query pipeline or the
+        threshold kernel folds them into the guard: idempotent, 2 x 912 floats."""
+        tag = '%d_%d' % key
+        emax, de2max = guard_slot(self._lp_guard, G_EMAX), guard_slot(self._lp_guard, G_DE2MAX)
+        prep = None
+        if frag:
+            prep = self._cache.get('tp_' + tag, [table],
+                                   lambda: _hip.table_prep_l2(table, emax, de2max, deferred_max=True, K=K))
+        if prep is not None:
+            return prep, self._cache.get('en_' + tag, [table], lambda: prep[0])
+        return None, self._cache.get('en_' + tag, [table], lambda: _hip.row_sqnorm(table, K=K, max_io=emax))
+
+    def _split_operand(self, key, T0, T1=None, K=None, aug=None, dot=False, level=None, prep=None, band=None, list_stat=True):
+        """The candidate side of the f16-split prefilter, ``LpProblem.split``: the operand table of the rows ``T0``
+        (DOT with two segments: [T0 | T1]) = global entities ``key`` = (c_base, rows), built once per evaluation, and the
+        guard slots the sweep reads its bounds from and reports to.  Three constructions: three-product level --
+        split_table; one-product level -- hi_table, planar or fragment-major; or the table of a fused preparation the
+        caller has run, ``prep`` = (en, table, block maxima) (_cand_norms; dot_table_prep: the table only), whose
+        residual maximum goes to the guard instead of a scalar of its own.
+        ``K`` / ``aug`` (L2: the columns swept, ||e||^2) as split_rows takes them; ``level``: _level_and_frag() of a caller
+        whose query side had to know it first; ``band`` = (max |X| measured?, max |y_c| measured?), projection modes: the
+        dict carries xabsmax / yabsmax, None where the threshold kernel bounds the term itself; ``list_stat``: the
+        recheck adds the pairs it re-scored to the guard (the level policy's input)."""
+        tag, g = '%d_%d' % key, self._lp_guard
+        srcs = [T0] + ([T1] if T1 is not None else [])
+        emax, emax1 = guard_slot(g, G_EMAX), (guard_slot(g, G_EMAX1) if T1 is not None else None)
+        sp = {'enmax': emax, 'overflow': guard_slot(g, G_OVERFLOW)}
+        if dot:
+            sp['enmax1'] = emax1
+        if band is not None:
+            sp['xabsmax'] = guard_slot(g, G_XABS) if band[0] else None
+            sp['yabsmax'] = guard_slot(g, G_YABS) if band[1] else None
+        if list_stat:
+            sp['list_stat'] = guard_slot(g, G_RESCORED)
+        if dot and prep is None:
+            def norms():
+                _hip.row_sqnorm(T0, max_io=emax, bound_only=True)       # (only the maxima are used: the operands' scale)
+                if T1 is not None:
+                    _hip.row_sqnorm(T1, max_io=emax1, bound_only=True)
+                return True
+            self._cache.get('esn_' + tag, srcs, norms)      # the norm maxima fix the operands' scale: before either table
+        how = {'X1': T1, 'dot': True, 'nmax0': emax, 'nmax1': emax1} if dot else {'K': K, 'aug': aug}
+        lvl1, frag = self._level_and_frag() if level is None else level
+        if not lvl1:
+            Es, e2 = self._cache.get(('esd_' if dot else 'es_') + tag, srcs, lambda: _hip.split_table(T0, **how))
+            sp.update({'Es': Es, 'e2pref': e2})
+            return sp
+        # one-product level (a fitted model: the true entities sit in the sparse upper tail, the 8x wider band still holds
+        # few pairs): hi table, thresholds from the measured f16 residuals
+        if prep is not None:
+            Eh, de2 = prep[1], guard_slot(g, G_DE2MAX)
+        else:
+            Eh, de2 = self._cache.get(('ehd%d_' if dot else 'eh%d_') % frag + tag, srcs,
+                                      lambda: _hip.hi_table(T0, frag=frag, **how))
+        sp.update({'Es': Eh, 'e2pref': None, 'level': 1, 'de2max': de2, 'es_frag': frag})
+        return sp
+
     def _attach_dot_split(self, prob, T0, T1=None, c_base=0):
         """Rank counts of a KGE_LP_DOT problem through the certified f16-split
         prefilter (only inside an evaluation, where the guard vector exists)."""
-        if not (self._guard_on and self.split_filter and self._split_ok):
-            return prob
-        g = self._lp_guard
-        key = '%d_%d' % (c_base, T0.shape[0])
-
-        def norms():
-            en0 = _hip.row_sqnorm(T0, max_io=g[1:2], bound_only=True)      # (only the maxima are used: the operands' scale)
-            if T1 is not None:
-                _hip.row_sqnorm(T1, max_io=g[5:6], bound_only=True)
-            del en0
-            return True
-        srcs = [T0] + ([T1] if T1 is not None else [])
-        self._cache.get('esn_' + key, srcs, norms)       # the norm maxima fix the operands' scale: before either table
-        nm1 = g[5:6] if T1 is not None else None
-        if self._use_level1():
-            # one-product level (see TransEModel._fused_query_problem): planar hi table + its residual maximum
-            frag = self._level1_stream()
-            Eh, de2 = self._cache.get('ehd%d_' % frag + key, srcs,
-                                      lambda: _hip.hi_table(T0, X1=T1, dot=True, nmax0=g[1:2], nmax1=nm1, frag=frag))
-            prob.split = {'Es': Eh, 'e2pref': None, 'enmax': g[1:2], 'enmax1': nm1, 'overflow': g[2:3], 'level': 1,
-                          'de2max': de2, 'list_stat': g[6:7], 'es_frag': frag}
-            return prob
-        Es, e2 = self._cache.get('esd_' + key, srcs, lambda: _hip.split_table(T0, X1=T1, dot=True, nmax0=g[1:2], nmax1=nm1))
-        prob.split = {'Es': Es, 'e2pref': e2, 'enmax': g[1:2], 'enmax1': nm1, 'overflow': g[2:3], 'list_stat': g[6:7]}
+        if self._guard_on and self.split_filter and self._split_ok:
+            prob.split = self._split_operand((c_base, T0.shape[0]), T0, T1, dot=True)
         return prob
 
     def _dot_fused_problem(self, sd, h_idx, t_idx, r_idx, ent, rel):
@@ -402,12 +461,12 @@ class Model(Module):
         if h_idx.shape[0] == 0 or d % 8 != 0 or sd not in (_hip.SIDE_TAIL, _hip.SIDE_HEAD, _hip.SIDE_BOTH):
             return None
         T0, T1 = ent[0], (ent[1] if len(ent) > 1 else None)
-        g = self._lp_guard
         frag = self._level1_stream()
-        nm1 = g[5:6] if T1 is not None else None
+        g = self._lp_guard
+        emax, emax1 = guard_slot(g, G_EMAX), (guard_slot(g, G_EMAX1) if T1 is not None else None)
         # candidate side (cached per evaluation) in two launches: norm maxima per block, then the hi table whose blocks fold
-        # them into guard[1] / guard[5] and leave their residual maxima per block -- folded into guard[7] by every query
-        # pipeline launch on its way in (kge_lp_dot_table_prep; the guard vector is zeroed per evaluation)
+        # them into the guard and leave their residual maxima per block -- folded into the guard by every query pipeline
+        # launch on its way in (kge_lp_dot_table_prep; the guard vector is zeroed per evaluation)
         srcs = [T0] + ([T1] if T1 is not None else [])
         # r06: from the second evaluation on ONE launch and one pass -- the scale of the maxima the previous evaluation's
         # query pipeline left in `prev`; the pipeline folds this pass's maxima, and a table that has outgrown its scale
@@ -419,18 +478,17 @@ class Model(Module):
         sig = (T0.data_ptr(), None if T1 is None else T1.data_ptr(), tuple(T0.shape))
         one_pass = bool(DOT_PREP_ONE_PASS and frag and prev[1] == sig and _hip.dot_table_prep_fusable(T0, T1))
         ckey = 'dtp%d%d_0_%d' % (frag, one_pass, T0.shape[0])
-        Eh, dnb, ws = self._cache.get(ckey, srcs, lambda: _hip.dot_table_prep(T0, T1, g[1:2], nm1, frag,
+        Eh, dnb, ws = self._cache.get(ckey, srcs, lambda: _hip.dot_table_prep(T0, T1, emax, emax1, frag,
                                                                               prev_nmax=prev[0] if one_pass else None))
         prev[1] = sig       # (the pipeline below stores this evaluation's maxima there)
-        sp = {'Es': Eh, 'e2pref': None, 'enmax': g[1:2], 'enmax1': nm1, 'overflow': g[2:3], 'level': 1, 'de2max': g[7:8],
-              'list_stat': g[6:7], 'es_frag': frag}
         pre = _hip.lp_dot_query_pipeline(sd, T0, T1, rel[0], rel[1] if len(rel) > 1 else None, h_idx, t_idx, r_idx,
-                                         sp['enmax'], nm1, sp['de2max'], g[0:1], sp['overflow'], zero_counts=True,
-                                         dn_bmax=dnb, regions=bool(frag) and bool(getattr(self, '_lp_regions', False)),
+                                         emax, emax1, guard_slot(g, G_DE2MAX), guard_slot(g, G_QMAX),
+                                         guard_slot(g, G_OVERFLOW), zero_counts=True, dn_bmax=dnb,
+                                         regions=bool(frag) and bool(getattr(self, '_lp_regions', False)),
                                          nm_bmax=ws if one_pass else None, prev_nmax=prev[0])
         pre['true_idx'] = t_idx if sd == _hip.SIDE_TAIL else (h_idx if sd == _hip.SIDE_HEAD else None)
         prob = _hip.LpProblem(_hip.LP_DOT, pre['Q'], T0, A1=pre['Q1'], T1=T1)
-        prob.split = sp
+        prob.split = self._split_operand((0, T0.shape[0]), T0, T1, dot=True, level=(True, frag), prep=(None, Eh, None))
         prob.pre = pre
         return prob
 
@@ -578,21 +636,11 @@ class TranslationModel(Model):
         if not (self._guard_on and self._expand_ok is None and self.l2_mode == 'auto' and self.split_filter
                 and self._split_ok):
             return prob
-        g = self._lp_guard
-        key = '%d_%d' % (prob.desc.c_base, table.shape[0])
-        Kq = table.shape[1] if K0 is None else K0
-        self._cache.get('xmax_' + key, [X], lambda: _hip.absmax(X, g[3:4]))
+        key = (prob.desc.c_base, table.shape[0])
+        self._cache.get('xmax_%d_%d' % key, [X], lambda: _hip.absmax(X, guard_slot(self._lp_guard, G_XABS)))
         if yc is not None:
-            self._cache.get('ymax_' + key, [yc], lambda: _hip.absmax(yc, g[4:5]))
-        prob.split = {'enmax': g[1:2], 'overflow': g[2:3], 'xabsmax': g[3:4], 'yabsmax': g[4:5] if yc is not None else None,
-                      'list_stat': g[6:7]}
-        if self._use_level1():      # one-product level (see TransEModel._fused_query_problem)
-            frag = self._level1_stream()
-            Eh, de2 = self._cache.get('eh%d_' % frag + key, [table], lambda: _hip.hi_table(table, K=Kq, aug=en, frag=frag))
-            prob.split.update({'Es': Eh, 'e2pref': None, 'level': 1, 'de2max': de2, 'es_frag': frag})
-        else:
-            Es, e2 = self._cache.get('es_' + key, [table], lambda: _hip.split_table(table, K=Kq, aug=en))
-            prob.split.update({'Es': Es, 'e2pref': e2})
+            self._cache.get('ymax_%d_%d' % key, [yc], lambda: _hip.absmax(yc, guard_slot(self._lp_guard, G_YABS)))
+        prob.split = self._split_operand(key, table, K=K0, aug=en, band=(True, yc is not None))
         return prob
 
     def _proj_fast_problem(self, sd, h_idx, t_idx, r_idx, r_both, ent_lo, ent_hi, exchange, qtabs, spec):
@@ -604,29 +652,21 @@ class TranslationModel(Model):
         ||w_i|| max||e|| inside the threshold kernel.  ``spec`` = (mode, W table, scale, z_add, K0, tables builder).
         None: shapes / alignment need the general path."""
         mode, Wt, scale, z_add, K0, build_side = spec
-        g = self._lp_guard
         tabs = [x.data for x in self._tables()]
         table = self._cand_rows(_hip.f32c(tabs[0]), ent_lo, ent_hi)
         Kq = table.shape[1] if K0 is None else K0
         if Kq % 4 or table.stride(0) % 4 or table.data_ptr() % 16 or table.shape[0] == 0:
             return None
-        lvl1 = self._use_level1()
-        frag = lvl1 and self._level1_stream()
-        key = '%d_%d' % (ent_lo, table.shape[0])
+        level = self._level_and_frag()
+        frag = level[1]
+        key = (ent_lo, table.shape[0])
 
         def cand_side():
             """norms + fragment-major hi table + residual maximum, X = W.E^T (TransD: G, sigma): per evaluation, cached"""
-            prep_ = None
-            if frag:
-                prep_ = self._cache.get('tp_' + key, [table],
-                                        lambda: _hip.table_prep_l2(table, g[1:2], g[7:8], deferred_max=True, K=K0))
-            if prep_ is not None:
-                en_ = self._cache.get('en_' + key, [table], lambda: prep_[0])
-            else:
-                en_ = self._cache.get('en_' + key, [table], lambda: _hip.row_sqnorm(table, K=K0, max_io=g[1:2]))
+            prep_, en_ = self._cand_norms(key, table, K0, frag)
             XT_, yc_ = build_side(table, ent_lo, K0)
             if yc_ is not None:
-                self._cache.get('ymax_' + key, [yc_], lambda: _hip.absmax(yc_, g[4:5]))
+                self._cache.get('ymax_%d_%d' % key, [yc_], lambda: _hip.absmax(yc_, guard_slot(self._lp_guard, G_YABS)))
             return prep_, en_, XT_, yc_
 
         # (r06) the candidate side -- three to five launches that read tables only -- on the evaluator's second stream
@@ -640,7 +680,8 @@ class TranslationModel(Model):
             out_ = self._lp_prep(sd, h_idx, t_idx, r_idx, exchange, qtabs=qtabs, **({'want_hi': True} if hi_too else {}))
             # (r06: the launch also zeroes the batch's (3, 2B) rank counters -- the evaluator's partial_counts takes them)
             zc_ = torch.empty(3, out_[0].shape[0], dtype=torch.int32, device=out_[0].device) if out_[0].is_cuda else None
-            return out_, zc_, _hip.proj_query_stats(out_[0], Wt, r_both, scale, z_add, qmax_io=g[0:1], zero=zc_)
+            qmax = guard_slot(self._lp_guard, G_QMAX)
+            return out_, zc_, _hip.proj_query_stats(out_[0], Wt, r_both, scale, z_add, qmax_io=qmax, zero=zc_)
 
         def keep(xs):       # allocated on the side stream, consumed on the main one
             for x in xs:
@@ -649,23 +690,17 @@ class TranslationModel(Model):
                 elif isinstance(x, (tuple, list)):
                     keep(x)
         if side is not None:
+            # the QUERY side on the second stream: what follows the join -- true scores, thresholds, sweep -- then stays on
+            # the queue of the candidate side's branch (the graph executor continues a joined chain there: the other
+            # way round the critical chain changed queues twice, ~11 us per change; r06 same box 0.565 -> 0.559 /
+            # 0.602 -> 0.597 ms)
             main = torch.cuda.current_stream(table.device)
             side.wait_stream(main)
-            if PREP_SIDE_SWAP:
-                # the QUERY side on the second stream: what follows the join -- true scores, thresholds, sweep -- then stays on
-                # the queue of the candidate side's branch (the graph executor continues a joined chain there: the other
-                # way round the critical chain changed queues twice, ~11 us per change)
-                with torch.cuda.stream(side):
-                    out, zc, st = query_side()
-                cand = cand_side()
-                main.wait_stream(side)
-                keep([out, zc, st])
-            else:
-                with torch.cuda.stream(side):
-                    cand = cand_side()
+            with torch.cuda.stream(side):
                 out, zc, st = query_side()
-                main.wait_stream(side)
-                keep(cand)
+            cand = cand_side()
+            main.wait_stream(side)
+            keep([out, zc, st])
         else:
             out, zc, st = query_side()
         Q0 = out[0]
@@ -674,19 +709,9 @@ class TranslationModel(Model):
         qn, pz = st
         prep, en, XT, yc = cand if side is not None else cand_side()
         prob = _hip.LpProblem(mode, Q0, table, qn=qn, en=en, Wq=pz, scal=XT, r_idx=r_both, yc=yc, c_base=ent_lo, K0=K0)
-        split = {'enmax': g[1:2], 'overflow': g[2:3], 'xabsmax': None, 'yabsmax': None, 'list_stat': g[6:7]}
-        if yc is not None:
-            split['yabsmax'] = g[4:5]
-        if lvl1:
-            if prep is not None:
-                split.update({'Es': prep[1], 'e2pref': None, 'level': 1, 'de2max': g[7:8], 'es_frag': True, 'tp_bmax': prep[2]})
-            else:
-                Eh, de2 = self._cache.get('eh%d_' % frag + key, [table], lambda: _hip.hi_table(table, K=Kq, aug=en, frag=frag))
-                split.update({'Es': Eh, 'e2pref': None, 'level': 1, 'de2max': de2, 'es_frag': frag})
-        else:
-            Es, e2 = self._cache.get('es_' + key, [table], lambda: _hip.split_table(table, K=Kq, aug=en))
-            split.update({'Es': Es, 'e2pref': e2})
-        prob.split = split
+        prob.split = self._split_operand(key, table, K=K0, aug=en, level=level, prep=prep, band=(False, yc is not None))
+        if prep is not None:    # (no query pipeline here: the threshold kernel folds the fused preparation's block maxima)
+            prob.split['tp_bmax'] = prep[2]
         if hi_too:
             prob.pre_q = (out[4], out[5])
         prob.zero_counts = zc
@@ -703,7 +728,7 @@ class TranslationModel(Model):
             # inside evaluate() the expansion is optimistic: the two norm kernels also
             # fold their maxima into the guard scalars, which are checked once at the end
             guarded = self.l2_mode == 'auto' and self._expand_ok is None and self._guard_on
-            gq, ge = (self._lp_guard[0:1], self._lp_guard[1:2]) if guarded else (None, None)
+            gq, ge = (guard_slot(self._lp_guard, G_QMAX), guard_slot(self._lp_guard, G_EMAX)) if guarded else (None, None)
             en = self._cache.get('en_%d_%d' % (c_base, table.shape[0]), [table],
                                  lambda: _hip.row_sqnorm(table, K=K0, max_io=ge))
             qn = _hip.row_sqnorm(q, max_io=gq)
@@ -718,10 +743,11 @@ class TranslationModel(Model):
                 prob = _hip.LpProblem(_hip.LP_L2_EXPAND, q, table, qn=qn, en=en, c_base=c_base, K0=K0)
                 if guarded and self.split_filter and self._split_ok:
                     # rank counts through the certified f16-split prefilter (16x MFMA rate)
-                    Kq = q.shape[1] if K0 is None else K0
-                    Es, e2 = self._cache.get('es_%d_%d' % (c_base, table.shape[0]), [table],
-                                             lambda: _hip.split_table(table, K=Kq, aug=en))
-                    prob.split = {'Es': Es, 'e2pref': e2, 'enmax': ge, 'overflow': self._lp_guard[2:3]}
+                    # (the general path stays on the three-product level whatever the evaluation runs, and it has never
+                    # handed the recheck a list_stat: its re-scored pairs do not reach the level policy.  Both kept as
+                    # they are; whether the second should be is an open question)
+                    prob.split = self._split_operand((c_base, table.shape[0]), table, K=q.shape[1] if K0 is None else K0,
+                                                     aug=en, level=(False, False), list_stat=False)
                 return prob
         if callable(scal):          # built only when the broadcast-subtract kernel is really taken
             scal = scal()
@@ -732,10 +758,9 @@ class TranslationModel(Model):
                 and c_base == 0 and table.shape[0] == self.n_ent):     # (whole table: the bounds are taken over it)
             # TransE-L1 inside an evaluation: rank counts through the certified 16-bit SAD prefilter (lp_l1_sad.hip).
             # Every query element is e +- r, so max|e| + max|r| (device scalars in the guard vector) bounds both operands.
-            g = self._lp_guard
             emax, rmax = self._sad_bounds()
             Ei = self._cache.get('sad_%d_%d' % (c_base, table.shape[0]), [table], lambda: _hip.sad_rows(table, emax, rmax))
-            prob.sad = {'Ei': Ei, 'emax': emax, 'rmax': rmax, 'overflow': g[2:3]}
+            prob.sad = {'Ei': Ei, 'emax': emax, 'rmax': rmax, 'overflow': guard_slot(self._lp_guard, G_OVERFLOW)}
         return prob
 
     def inference_scoring_function(self, proj_h, proj_t, r):

@@ -17,6 +17,7 @@ from .. import _hip
 from ..exceptions import NotYetImplementedError
 from ..utils.modeling import init_embedding
 from .interfaces import TranslationModel, EntityCandidates, RelationProjections, _table_of, _ScoreTriples
+from .interfaces import guard_slot, G_QMAX, G_EMAX, G_XABS, G_YABS
 
 
 def _projections(kind, tabs, d_ent, d_rel, h_idx, t_idx, r_idx):
@@ -76,11 +77,11 @@ class TransEModel(TranslationModel):
     def _abs_bounds(self):
         """Device scalars (max |E|, max |R|) of this evaluation (guard slots 3 / 4, cached per session): every query
         element of TransE is e +- r, so their sum bounds both operands of the L1 prefilter."""
-        g = self._lp_guard
+        emax, rmax = guard_slot(self._lp_guard, G_XABS), guard_slot(self._lp_guard, G_YABS)
         E, R = _hip.f32c(self.ent_emb.weight.data), _hip.f32c(self.rel_emb.weight.data)
-        self._cache.get('sad_emax', [E], lambda: _hip.absmax(E, g[3:4]))
-        self._cache.get('sad_rmax', [R], lambda: _hip.absmax(R, g[4:5]))
-        return g[3:4], g[4:5]
+        self._cache.get('sad_emax', [E], lambda: _hip.absmax(E, emax))
+        self._cache.get('sad_rmax', [R], lambda: _hip.absmax(R, rmax))
+        return emax, rmax
 
     def _hip_kind(self):
         return _hip.TRANSE_L1 if self.dissimilarity_type == 'L1' else _hip.TRANSE_L2
@@ -135,44 +136,26 @@ class TransEModel(TranslationModel):
         owner shard's), while the candidate side -- norms, split / hi table, the bounds of the error band -- is this
         rank's own rows ``tabs[0]`` = global entities [c_base, c_base + rows)."""
         E = _hip.f32c(tabs[0])
-        g = self._lp_guard
-        key = '%d_%d' % (c_base, E.shape[0])
+        key = (c_base, E.shape[0])
         Eq = E if qrep is None else qrep            # where the query pipeline reads e_src / e_true
-        lvl1 = self._use_level1()
-        frag = lvl1 and self._level1_stream()       # (r06: grouped columns run on the free-running kernel too)
-        prep = None
-        if frag:
-            # the candidate side of the free-running sweep in ONE launch: ||e||^2 (the reference chain), the fragment-major
-            # hi table and its residual maximum (guard slot 7, zeroed with the guard) -- kge_lp_table_prep_l2
-            # (its two maxima stay per block -- hundreds of same-address atomics would serialise -- and every query
-            # pipeline launch folds them into guard[1] / guard[7] on its way in: idempotent, 2 x 912 floats)
-            prep = self._cache.get('tp_' + key, [E], lambda: _hip.table_prep_l2(E, g[1:2], g[7:8], deferred_max=True))
-        if prep is not None:
-            en = self._cache.get('en_' + key, [E], lambda: prep[0])
-        else:
-            en = self._cache.get('en_' + key, [E], lambda: _hip.row_sqnorm(E, max_io=g[1:2]))
+        level = self._level_and_frag()
+        lvl1, frag = level                          # (r06: grouped columns run on the free-running kernel too)
+        # the candidate side: on the free-running sweep ONE launch; every query pipeline launch folds its block maxima
+        prep, en = self._cand_norms(key, E, None, frag)
+        split = self._split_operand(key, E, aug=en, level=level, prep=prep)
 
         def enq():      # ||.||^2 of the rows the true scores are read from (replicas: their own chain norms, no maximum)
             if qrep is None:
                 return en
             return self._cache.get('en_replica', [qrep], lambda: _hip.row_sqnorm(qrep))
+        emax, qmax = guard_slot(self._lp_guard, G_EMAX), guard_slot(self._lp_guard, G_QMAX)
         if lvl1:
-            # one-product level of the split prefilter (a fitted model: the true entities sit in the sparse upper tail,
-            # the 8x wider band still holds few pairs): planar hi table, thresholds from the measured f16 residuals
-            if prep is not None:
-                Eh, de2 = prep[1], g[7:8]
-            else:
-                Eh, de2 = self._cache.get('eh%d_' % frag + key, [E], lambda: _hip.hi_table(E, aug=en, frag=frag))
-            tp_bmax = prep[2] if prep is not None else None
-            pre = _hip.lp_query_pipeline(sd, Eq, tabs[1], h_idx, t_idx, r_idx, enq(), g[1:2], g[0:1], cols=cols, level=1,
-                                         de2max=de2, tp_bmax=tp_bmax, zero_counts=True, regions=bool(frag) and bool(getattr(self, '_lp_regions', False)))
-            split = {'Es': Eh, 'e2pref': None, 'enmax': g[1:2], 'overflow': g[2:3], 'level': 1, 'de2max': de2,
-                     'list_stat': g[6:7], 'es_frag': frag}
+            pre = _hip.lp_query_pipeline(sd, Eq, tabs[1], h_idx, t_idx, r_idx, enq(), emax, qmax, cols=cols, level=1,
+                                         de2max=split['de2max'], tp_bmax=prep[2] if prep is not None else None,
+                                         zero_counts=True, regions=bool(frag) and bool(getattr(self, '_lp_regions', False)))
         else:
-            Es, e2 = self._cache.get('es_' + key, [E], lambda: _hip.split_table(E, aug=en))
-            pre = _hip.lp_query_pipeline(sd, Eq, tabs[1], h_idx, t_idx, r_idx, enq(), g[1:2], g[0:1], e2pref=e2, cols=cols,
-                                         zero_counts=True)
-            split = {'Es': Es, 'e2pref': e2, 'enmax': g[1:2], 'overflow': g[2:3], 'list_stat': g[6:7]}
+            pre = _hip.lp_query_pipeline(sd, Eq, tabs[1], h_idx, t_idx, r_idx, enq(), emax, qmax, e2pref=split['e2pref'],
+                                         cols=cols, zero_counts=True)
         # (SIDE_BOTH: the evaluator fills in the concatenated true indices it gets from the filter lookup)
         pre['true_idx'] = t_idx if sd == _hip.SIDE_TAIL else (h_idx if sd == _hip.SIDE_HEAD else None)
         prob = _hip.LpProblem(_hip.LP_L2_EXPAND, pre['Q'], E, qn=pre['qn'], en=en, c_base=c_base)
@@ -563,7 +546,7 @@ class _RelationGroupedProblem(object):
     -||q - M_rho e_c||^2 without any cancellation.  One P_rho exists at a time; nothing of (n_rel, N, d_r) is kept.  It
     answers what the evaluators ask of an LpProblem.  Building it reads the batch's relations on the host (one sync)."""
 
-    split = sad = pre = cols = pre_q = region_count = zero_counts = None
+    split = sad = pre = cols = pre_q = zero_counts = None
 
     def __init__(self, Q, r_q, table, M, d_e, d_r, c_base):
         self.Q, self.table, self.c_base = Q, table, c_base
@@ -727,7 +710,7 @@ class TransRModel(TranslationModel):
         """The all-candidates problem of the queries Q (rows, d_r) in relation space, U = M_r^T Q, relations r_q."""
         guarded = self.l2_mode == 'auto' and self._expand_ok is None and self._guard_on
         if self.l2_mode in ('expand', 'auto') and table.shape[0] > 0:
-            gq, ge = (self._lp_guard[0:1], self._lp_guard[1:2]) if guarded else (None, None)
+            gq, ge = (guard_slot(self._lp_guard, G_QMAX), guard_slot(self._lp_guard, G_EMAX)) if guarded else (None, None)
             qn = _hip.row_sqnorm(Q, max_io=gq)
             ok = True
             Z = None
