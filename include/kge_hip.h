@@ -596,7 +596,8 @@ int kge_corrupt_scatter(const int64_t *heads, const int64_t *tails, const uint8_
 
 /* library / build info */
 /* ---- certified f16-split prefilter of the fused rank count ------------------------
- * (torchkge_amd/csrc/lp_split_mfma.hip has the error analysis.)  kge_lp_split_count + kge_lp_split_recheck leave in raw_count exactly
+ * (torchkge_amd/csrc/lp_split_mfma.hip has the error analysis and the count sweep; lp_split_operands / _query / _recheck.hip
+ * the other stages, lp_split_common.h the error bands.)  kge_lp_split_count + kge_lp_split_recheck leave in raw_count exactly
  * what kge_lp_count_ge leaves there: >= 99.9% of the (query, candidate) pairs are
  * decided by an f16 hi/lo-split MFMA product with a rigorous error band, the pairs
  * inside the band are re-scored by the exact fp32 chain.

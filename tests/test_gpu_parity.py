@@ -1218,6 +1218,59 @@ def test_query_pipeline_equals_separate_kernels(hip, B, N, d, side):
     assert float(guard[2]) == 0.0
 
 
+@pytest.mark.parametrize('kind,B,d,side', [('l2', 33, 52, 'tail'), ('l2', 33, 52, 'head'), ('complex', 37, 40, 'both'),
+                                           ('distmult', 5, 64, 'tail')])
+def test_pipeline_thresholds_equal_the_threshold_kernel_bit_for_bit(hip, kind, B, d, side):
+    """One-product level: the thresholds a fused query pipeline writes (kge_lp_query_pipeline, kge_lp_dot_query_pipeline)
+    equal BIT FOR BIT those the threshold kernel of kge_lp_split_count recomputes from the pipeline's own qn, q_dn2 and
+    s_true -- both evaluate the one definition of the band (lp_split_common.h) on the same inputs; no prefix-norm term
+    on this level.  A partial query panel, K off the 16-column unit, both DOT layouts."""
+    N, n_rel = 300, 5
+    g = torch.Generator().manual_seed(B * 7 + d)
+    h = torch.randint(0, N, (B,), generator=g).cuda(); t = torch.randint(0, N, (B,), generator=g).cuda()
+    r = torch.randint(0, n_rel, (B,), generator=g).cuda()
+    sd = hip.side_code(side)
+    guard = torch.zeros(8, device='cuda')
+    if kind == 'l2':
+        E = torch.nn.functional.normalize(torch.randn(N, d, generator=g), dim=1).cuda()
+        R = (0.3 * torch.randn(n_rel, d, generator=g)).cuda()
+        en = hip.row_sqnorm(E, max_io=guard[1:2])
+        Eh, de2 = hip.hi_table(E, aug=en)
+        pre = hip.lp_query_pipeline(sd, E, R, h, t, r, en, guard[1:2], guard[0:1], level=1, de2max=de2)
+        prob = hip.LpProblem(hip.LP_L2_EXPAND, pre['Q'], E, qn=pre['qn'], en=en)
+        prob.split = {'Es': Eh, 'e2pref': None, 'enmax': guard[1:2], 'overflow': guard[2:3], 'level': 1, 'de2max': de2}
+    else:
+        cplx = kind == 'complex'
+        tables = orc.init_tables(kind, N, n_rel, d, seed=5)
+        tabs = [hip.f32c(x.data) for x in build_model(kind, 2, tables, N, n_rel)._tables()]
+        with torch.no_grad():       # rows of different magnitude: the per-query scales differ
+            tabs[0][::7] *= 3.0
+            tabs[0][1::7] *= 0.2
+        ent, rel = (tabs[:2], tabs[2:]) if cplx else (tabs[:1], tabs[1:])
+        T0, T1 = ent[0], (ent[1] if cplx else None)
+        hip.row_sqnorm(T0, max_io=guard[1:2], bound_only=True)
+        if cplx:
+            hip.row_sqnorm(T1, max_io=guard[5:6], bound_only=True)
+        nm1 = guard[5:6] if cplx else None
+        Eh, de2 = hip.hi_table(T0, X1=T1, dot=True, nmax0=guard[1:2], nmax1=nm1)
+        pre = hip.lp_dot_query_pipeline(sd, T0, T1, rel[0], rel[1] if cplx else None, h, t, r, guard[1:2], nm1, de2,
+                                        guard[0:1], guard[2:3])
+        prob = hip.LpProblem(hip.LP_DOT, pre['Q'], T0, A1=pre['Q1'], T1=T1)
+        prob.split = {'Es': Eh, 'e2pref': None, 'enmax': guard[1:2], 'enmax1': nm1, 'overflow': guard[2:3], 'level': 1,
+                      'de2max': de2}
+    prob.pre = pre
+    Bq = pre['qn'].numel()
+    Bp = pre['thr'].numel() // 4
+    thr_pipe = pre['thr'][:2 * Bp].clone()          # (the recomputation writes the same buffer)
+    assert bool(torch.isfinite(thr_pipe[:2 * Bq]).all()) and bool(torch.isinf(thr_pipe[2 * Bq:]).all())
+    prep = prob.split_prepare()
+    assert prep['thr'] is pre['thr']
+    raw = torch.zeros(Bq, dtype=torch.int32, device='cuda')
+    prob.split_count(prep, pre['s_true'].clone(), raw)      # a clone: thr_ready = 0, the threshold kernel runs
+    assert torch.equal(pre['thr'][:2 * Bp].view(torch.int32), thr_pipe.view(torch.int32))
+    assert float(guard[2]) == 0.0
+
+
 @pytest.mark.parametrize('eps', [1.0, 1.0 / 16])
 def test_split_count_on_query_columns_equals_per_query_counts(hip, eps):
     """Queries that share their key share the query row (filter_index.ColumnPlan): the count kernel sweeps one COLUMN per

@@ -569,22 +569,25 @@ def test_mfma_kernels_hold_no_lane_crossing_packed_f32_operand():
     the scalars it wants to splat sit in one register pair, selects them with op_sel -- and the form in which the LOW result
     lane reads the HIGH dword of a VGPR pair (op_sel:[.,1,.]) misreads ~once per 1e3 wave-instructions inside the free-running
     kernel, where another wave's MFMAs co-execute (tools/probe/slp_bisect.sh, profiles/r06/slp_bisect.txt).  The three MFMA
-    count kernels are therefore built without the vectoriser; this compiles each of them to gfx950 assembly with the build's
-    own flags and checks that NO packed f32 instruction carries an op_sel:[...] with a set bit."""
+    count kernels are therefore built without the vectoriser -- and so are the other stages of the split prefilter
+    (lp_split_operands / _query / _recheck.hip: VALU code that was one translation unit with lp_split_mfma.hip); this compiles
+    each of these files to gfx950 assembly with the build's own flags and checks that NO packed f32 instruction carries an
+    op_sel:[...] with a set bit, and that the count-kernel files do hold the f16 MFMA."""
     from concurrent.futures import ThreadPoolExecutor
     from torchkge_amd.csrc import build as hb
     hipcc = hb._hipcc()
     files = [f for f, fl in hb.EXTRA_FLAGS.items() if '-DKGE_BUILD_NO_SLP=1' in fl]
-    assert set(files) >= {'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_split_mfma.hip'}
+    mfma_files = {'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_split_mfma.hip'}
+    assert set(files) >= mfma_files | {'lp_split_operands.hip', 'lp_split_query.hip', 'lp_split_recheck.hip'}
 
     def isa(src):
         cmd = [hipcc] + hb.FLAGS + hb.EXTRA_FLAGS[src] + ['-S', '--cuda-device-only', os.path.join(hb.HERE, src), '-o', '-']
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
         return src, r.stdout
-    with ThreadPoolExecutor(max_workers=3) as ex:
+    with ThreadPoolExecutor(max_workers=len(files)) as ex:
         for src, text in ex.map(isa, files):
-            assert 'v_mfma_f32_32x32x16_f16' in text, src
+            assert src not in mfma_files or 'v_mfma_f32_32x32x16_f16' in text, src
             bad = [l.strip() for l in text.split('\n')
                    if re.search(r'\bv_pk_(fma|mul|add)_f32\b', l) and re.search(r'op_sel:\[[01,]*1[01,]*\]', l)]
             assert not bad, (src, bad[:4])

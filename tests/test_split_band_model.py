@@ -146,7 +146,7 @@ def test_split_band_is_certified_under_the_measured_accumulation_model(kind, K):
         assert uncertain.mean() < (0.3 if kind in ('ties', 'near', 'cancel') else 0.05)
 
 
-# ---- the ONE-PRODUCT level (kge_split_args.level = 1, lp_split_mfma.hip: split_thr_l2_hi / LV = 1 count kernel) ----------
+# ---- the ONE-PRODUCT level (kge_split_args.level = 1, lp_split_common.h: split_thr_l2_hi; lp_split_mfma.hip: LV = 1 count kernel) ----------
 def _hi_accumulate(qh, eh, units):
     """(B, N) accumulators of Sum_k qh*eh, one MFMA (two passes of 8 products) per k16 unit."""
     B, N = qh.shape[0], eh.shape[0]
@@ -225,7 +225,7 @@ def test_one_product_band_is_certified_under_the_measured_accumulation_model(kin
 
 # ---- DOT mode on the one-product level with PER-QUERY operand scales (r05: kge_lp_dot_query_pipeline, split_thr_dot_hi) ------
 def _split_scale(norm2):
-    """split_scale of lp_split_mfma.hip: the power of two that puts a row of squared norm `norm2` just inside f16 range."""
+    """split_scale of lp_split_common.h: the power of two that puts a row of squared norm `norm2` just inside f16 range."""
     m = np.sqrt(np.asarray(norm2, dtype=np.float64))
     with np.errstate(divide='ignore', invalid='ignore'):
         e = np.floor(np.log2(16384.0 / m)) - 1.0

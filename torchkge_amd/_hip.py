@@ -659,15 +659,9 @@ SPLIT_EPS_SCALE = 1.0          # multiplies the proven error band of the f16-spl
 SPLIT_LIST_PER_QUERY = 64      # capacity of the uncertain-pair list per query of the batch (floor; grows with N)
 
 
-def split_rows(X, K=None, is_query=False, aug=None, X1=None, K1=None, dot=False, nmax0=None, nmax1=None,
-               cell_ss=False, row_index=None):
-    """f16 hi/lo split operand of kge_lp_split_count (uint8 tensor holding
-    [rows_p][units_p][64 bytes]) of [X | X1].  L2 mode (dot=False): candidates
-    carry -||e||^2/2 in the extra column (aug = ||e||^2), queries carry 1, fixed
-    scale.  DOT mode: queries carry their guard column (aug = ||q||^2), the
-    scale comes from the device scalars nmax0 (+ nmax1)."""
-    lib = load_library()
-    require_cuda(X, X1, aug, nmax0, nmax1)
+def _row_operand(X, K, X1, K1, is_query, dot, row_index):
+    """The shared opening of split_rows / hi_rows: (X, X1, rows, ld, K, ld1, K1, aug_mode, aug_mul) of the contiguous
+    [X | X1] and the augmentation column of its role (L2: candidates -||e||^2/2, queries 1; DOT: guard column / 0)."""
     X = f32c(X)
     rows, ld = X.shape[0], X.stride(0)
     if row_index is not None:       # output row r <- source row row_index[r] (gather inside the kernel)
@@ -684,6 +678,19 @@ def split_rows(X, K=None, is_query=False, aug=None, X1=None, K1=None, dot=False,
         aug_mode, aug_mul = (3, 1.0) if is_query else (4, 0.0)
     else:
         aug_mode, aug_mul = (2, 1.0) if is_query else (1, -0.5)
+    return X, X1, rows, ld, K, ld1, K1, aug_mode, aug_mul
+
+
+def split_rows(X, K=None, is_query=False, aug=None, X1=None, K1=None, dot=False, nmax0=None, nmax1=None,
+               cell_ss=False, row_index=None):
+    """f16 hi/lo split operand of kge_lp_split_count (uint8 tensor holding
+    [rows_p][units_p][64 bytes]) of [X | X1].  L2 mode (dot=False): candidates
+    carry -||e||^2/2 in the extra column (aug = ||e||^2), queries carry 1, fixed
+    scale.  DOT mode: queries carry their guard column (aug = ||q||^2), the
+    scale comes from the device scalars nmax0 (+ nmax1)."""
+    lib = load_library()
+    require_cuda(X, X1, aug, nmax0, nmax1)
+    X, X1, rows, ld, K, ld1, K1, aug_mode, aug_mul = _row_operand(X, K, X1, K1, is_query, dot, row_index)
     units_p = int(lib.kge_lp_split_units(K + K1, 1))
     rows_p = int(lib.kge_lp_split_rows_padded(rows, 1 if is_query else 0))
     out = torch.empty(max(rows_p, 1) * units_p * 64, dtype=torch.uint8, device=X.device)
@@ -715,22 +722,7 @@ def hi_rows(X, K=None, is_query=False, aug=None, X1=None, K1=None, dot=False, nm
     dn2max).  Augmentation / scale conventions as split_rows."""
     lib = load_library()
     require_cuda(X, X1, aug, nmax0, nmax1, dn2max)
-    X = f32c(X)
-    rows, ld = X.shape[0], X.stride(0)
-    if row_index is not None:
-        rows = int(row_index.shape[0])
-    K = X.shape[1] if K is None else K
-    ld1 = 0
-    if X1 is not None:
-        X1 = f32c(X1)
-        K1 = X1.shape[1] if K1 is None else K1
-        ld1 = X1.stride(0)
-    else:
-        K1 = 0
-    if dot:
-        aug_mode, aug_mul = (3, 1.0) if is_query else (4, 0.0)
-    else:
-        aug_mode, aug_mul = (2, 1.0) if is_query else (1, -0.5)
+    X, X1, rows, ld, K, ld1, K1, aug_mode, aug_mul = _row_operand(X, K, X1, K1, is_query, dot, row_index)
     units_p = int(lib.kge_lp_hi_units(K + K1))
     rows_p = int(lib.kge_lp_split_rows_padded(rows, 1 if is_query else 0))
     out = torch.empty(max(rows_p, 1) * units_p * 32, dtype=torch.uint8, device=X.device)

@@ -15,10 +15,10 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfma.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip',
-           'lp_l1_sad.hip', 'rank_filter.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip',
-           'transr_xform.hip']
-HEADERS = ['kge_common.h', os.path.join('..', '..', 'include', 'kge_hip.h')]
+SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfma.hip', 'lp_split_operands.hip', 'lp_split_query.hip',
+           'lp_split_recheck.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip', 'lp_l1_sad.hip', 'rank_filter.hip',
+           'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip', 'transr_xform.hip']
+HEADERS = ['kge_common.h', 'lp_split_common.h', os.path.join('..', '..', 'include', 'kge_hip.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
 # libkge_hip.so does not depend on librccl
@@ -28,7 +28,8 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=o
 # per-file extras.  lp_direct.hip: the SLP vectoriser turns the L1 inner loop (sub, then add |.|) into v_pk_add_f32
 # pairs -- which issue at HALF rate on gfx950 (tools/probe/valu_rate_probe.hip: 34 T vs 63 T lane-ops/s) and have no
 # abs modifier, so every element pays an extra v_and: 3 issue slots per element instead of 2.
-# The MFMA count kernels (lp_hi_stream.hip, lp_hi_chunk.hip, lp_split_mfma.hip): NO SLP-packed f32 arithmetic.  r05 found
+# The MFMA count kernels (lp_hi_stream.hip, lp_hi_chunk.hip, lp_split_mfma.hip) and the other stages of the split prefilter,
+# which were one translation unit with them (lp_split_operands / _query / _recheck.hip): NO SLP-packed f32 arithmetic.  r05 found
 # ~1 pair in 3e6 of the TransH / TransD epilogue of the free-running kernel miscounted, differently from launch to launch;
 # r06 bisected it at INSTRUCTION level (tools/probe/asm_patch_build.py + slp_bisect.sh, profiles/r06/slp_bisect.txt): the only
 # instructions that matter are  v_pk_fma_f32 D, A, B, C op_sel:[0,1,0]  -- the LOW result lane taking the HIGH dword of a
@@ -45,7 +46,8 @@ _NO_SLP = ['-fno-slp-vectorize', '-DKGE_BUILD_NO_SLP=1']
 # bilinear_xform.hip (RESCAL / HolE query transform, fmaf chains): no packed f32 either -- the same lane-crossing
 # op_sel form would be the vectoriser's to emit there (tests/test_rescal_hole_host.py checks its ISA)
 EXTRA_FLAGS = {'lp_direct.hip': ['-fno-slp-vectorize'], 'lp_hi_stream.hip': _NO_SLP, 'lp_hi_chunk.hip': _NO_SLP,
-               'lp_split_mfma.hip': _NO_SLP, 'bilinear_xform.hip': ['-fno-slp-vectorize'],
+               'lp_split_mfma.hip': _NO_SLP, 'lp_split_operands.hip': _NO_SLP, 'lp_split_query.hip': _NO_SLP,
+               'lp_split_recheck.hip': _NO_SLP, 'bilinear_xform.hip': ['-fno-slp-vectorize'],
                # transr_xform.hip (TransR: MFMA squared norms with a VALU epilogue beside other waves' MFMAs, fmaf chains): the same
                'transr_xform.hip': ['-fno-slp-vectorize']}
 

@@ -56,10 +56,11 @@
 // ds_read_b128 are bank-conflict free without padding.  Queries on the lane axis
 // make thresholds and counters per-lane constants, so the epilogue is two
 // compares and an add-with-carry per element.
-#include "kge_common.h"
-#ifndef KGE_BUILD_NO_SLP
-#error "build with -fno-slp-vectorize -DKGE_BUILD_NO_SLP=1 (torchkge_amd/csrc/build.py): SLP-packed v_pk_fma_f32 with a lane-crossing op_sel misreads beside co-executing MFMAs (profiles/r06/slp_bisect.txt)"
-#endif
+//
+// This file: the thresholds (split_thr_kernel) and the count sweep.  The other stages: lp_split_operands.hip (operand
+// preparation), lp_split_query.hip (fused query side), lp_split_recheck.hip (exact recheck); lp_split_common.h holds
+// the tile geometry and the one definition of each error band.
+#include "lp_split_common.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -67,16 +68,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-constexpr int TQ = 192, TC = 256;               // 256 accumulator registers leave hipcc no slack: 4 x 3 tiles
 constexpr int NT = 3;                           // 32x32 query tiles per wave (2 wave columns)
 constexpr int E_STAGE_BYTES = TC * 128;         // candidate operand, one stage (2 k16 units)
 constexpr int Q_STAGE_BYTES = TQ * 128;
 constexpr int STAGE_BYTES = E_STAGE_BYTES + Q_STAGE_BYTES;
 constexpr int UNC_CAP = 2048;                   // uncertain pairs buffered per tile
-constexpr int GSETS = 4;                        // grouped columns: queries that share one query row (threshold sets per column)
 // + per-panel (thr4, X row) of the projection modes, or the (a_lo, a_hi) sets + counters of a grouped panel
 constexpr int SMEM_BYTES = 2 * STAGE_BYTES + 16 + UNC_CAP * 4 + TQ * 20 + TQ * GSETS * 12 + 16;
-constexpr int SPLIT_SCALE_LOG2 = 12;
 
 struct SplitParams {
     const char *Es, *Qs;  // split operands
@@ -108,681 +106,6 @@ struct SplitParams {
                           // 4096 (LV = 1) cycle stamps of the stage phases into the head of the pair list
                           // (a planar hi table would move half the bytes)
 };
-
-// ---- operand preparation ---------------------------------------------------
-// power-of-two scale that puts rows of squared norm <= norm2max just inside f16 range
-__device__ __forceinline__ float split_scale(float norm2max)
-{
-    const float m = sqrtf(norm2max);
-    if (!(m > 0.f) || !(m < INFINITY)) return 1.0f;
-    float e = floorf(log2f(16384.0f / m)) - 1.0f;      // one binade of slack for the roundings above
-    e = fminf(fmaxf(e, -100.0f), 100.0f);
-    return ldexpf(1.0f, (int)e);
-}
-
-struct SplitRowsParams {
-    const float *X0, *X1;     // segment 1 optional (ComplEx: [Re | Im])
-    int64_t ld0, ld1;
-    int K0, K1;
-    int64_t rows, rows_p;
-    int aug_mode;             // 0 none; 1: aug[row]*aug_mul (candidates, L2); 2: aug_mul (queries, L2);
-                              // 3: query guard column of the DOT mode; 4: 0 for real rows (candidates, DOT)
-    const float *aug;
-    float aug_mul;
-    const float *nmax0, *nmax1;   // device scalars: squared-norm maxima -> scale (NULL: 2^12)
-    int units_p;
-    uint4 *out;
-    float *cell_ss;           // optional [units_p][rows_p]: sum of squares of the cell's 16 data values (unscaled)
-    const int64_t *row_index; // optional: output row r is built from source row row_index[r] of X0 / X1 / aug (gather)
-};
-
-// A block converts tiles of 16 rows x 16 k16 cells: 16 consecutive threads read one row's 1-KiB run (float4 loads where the
-// cell lies inside one K-segment and is 16-byte aligned) and write its 16 cells; the cells' sums of squares go through
-// LDS so that the unit-major cell_ss array is written in 64-byte runs as well (a thread-per-cell store there touches one
-// cache line per cell: it cost as much as the split table itself).
-__global__ __launch_bounds__(256) void split_rows_kernel(const SplitRowsParams p)
-{
-    __shared__ float ss_s[16][17];
-    float scale = (float)(1 << SPLIT_SCALE_LOG2), nmax = 0.f;
-    if (p.nmax0) {
-        nmax = *p.nmax0 + (p.nmax1 ? *p.nmax1 : 0.f);
-        scale = split_scale(nmax);
-    }
-    const int K = p.K0 + p.K1;
-    const int tiles_u = (p.units_p + 15) / 16;
-    const int64_t n_tiles = (p.rows_p / 16) * tiles_u;          // rows_p is a multiple of the count kernel's tile
-    const int tr_ = threadIdx.x >> 4, tu_ = threadIdx.x & 15;
-    const bool vec0 = (p.ld0 % 4 == 0) && ((size_t)p.X0 & 15) == 0;
-    const bool vec1 = p.X1 && (p.ld1 % 4 == 0) && ((size_t)p.X1 & 15) == 0 && (p.K0 % 4 == 0);
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t row = (tile / tiles_u) * 16 + tr_;
-        const int u = (int)(tile % tiles_u) * 16 + tu_;
-        const int64_t srow = (p.row_index && row < p.rows) ? p.row_index[row] : row;    // (gathered source row)
-        float ss = 0.f;
-        if (u < p.units_p) {
-            const int k0 = u * 16;
-            float xs[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) xs[e] = 0.f;
-            if (row < p.rows) {
-                if (k0 + 16 <= p.K0 && vec0) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X0 + srow * p.ld0 + k0);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
-                } else if (k0 >= p.K0 && k0 + 16 <= K && vec1) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X1 + srow * p.ld1 + (k0 - p.K0));
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int k = k0 + e;
-                        if (k < p.K0) xs[e] = p.X0[srow * p.ld0 + k];
-                        else if (k < K) xs[e] = p.X1[srow * p.ld1 + (k - p.K0)];
-                    }
-                }
-            }
-            union { _Float16 h[16]; uint4 v[2]; } hi, lo;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int k = k0 + e;
-                float x = xs[e];
-                if (row < p.rows) {
-                    if (k < K) ss = fmaf(x, x, ss);
-                    else if (k == K && p.aug_mode == 1) x = p.aug[srow] * p.aug_mul;
-                    else if (k == K && p.aug_mode == 2) x = p.aug_mul;
-                    else if (k == K && p.aug_mode == 3) x = 0.25f * (sqrtf(p.aug[srow]) + sqrtf(nmax) * 0.00390625f);
-                }
-                x *= scale;
-                if (row < p.rows && k == K && p.aug_mode == 3) x = fmaxf(x, 1.0f);
-                _Float16 h = (_Float16)x;                   // round to nearest even
-                _Float16 l = (_Float16)(x - (float)h);      // x - hi is exact in fp32
-                if (row >= p.rows && k == K && (p.aug_mode == 1 || p.aug_mode == 4)) {
-                    // padding candidate: hi = lo = -65504 in the column that meets the queries' guard
-                    // column drives its accumulator below every threshold (L2: <= -2*65504*2^12 against
-                    // >= -16*2^24 for norm-guarded queries; DOT: <= -32752*S_q*||q|| against >= -16384*S_q*||q||)
-                    h = (_Float16)(-65504.f);
-                    l = (_Float16)(-65504.f);
-                }
-                hi.h[e] = h;
-                lo.h[e] = l;
-            }
-            uint4 *o = p.out + (row * p.units_p + u) * 4;
-            o[0] = hi.v[0]; o[1] = hi.v[1]; o[2] = lo.v[0]; o[3] = lo.v[1];
-        }
-        if (p.cell_ss) {        // (block-uniform)
-            ss_s[tu_][tr_] = ss;
-            __syncthreads();
-            const int u2 = (int)(tile % tiles_u) * 16 + tr_;     // this thread now stores unit u2, row tu_ of the tile
-            if (u2 < p.units_p) p.cell_ss[(int64_t)u2 * p.rows_p + (tile / tiles_u) * 16 + tu_] = ss_s[tr_][tu_];
-            __syncthreads();
-        }
-    }
-}
-
-// ---- one-product level: PLANAR hi operands -----------------------------------------------------------------------
-// [rows_p][units_p][32 bytes]: the f16 hi parts of the 16 values of a k16 unit (units_p a multiple of 4: one 128-byte
-// row segment = one stage of the LV = 1 count kernel).  Two extra columns K, K+1: L2 candidates carry hi and lo of
-// -||e||^2/2 there (queries 1, 1), so the norm term keeps its 2^-22 precision; DOT queries their guard column at K.
-// Also emitted: dn2[row] = ||x - hi(x)||^2 (unscaled; the exact fp32 differences, summed) and its maximum.
-struct HiRowsParams {
-    const float *X0, *X1;
-    int64_t ld0, ld1;
-    int K0, K1;
-    int64_t rows, rows_p;
-    int aug_mode;             // as SplitRowsParams
-    const float *aug;
-    float aug_mul;
-    const float *nmax0, *nmax1;
-    int units_p;
-    uint4 *out;
-    float *dn2;               // optional (rows)
-    float *dn2max;            // optional device scalar, max folded in
-    const int64_t *row_index;
-    const float *nm_bmax;     // optional [2][nm_blocks]: per-block squared-norm maxima of the two segments (dot_table_norm_max_kernel)
-    int nm_blocks;            //   -- every block folds them into *nmax0 / *nmax1 on its way in, block 0 stores the two scalars
-    float *dn_bmax;           // optional [gridDim.x]: the blocks' residual maxima as plain stores INSTEAD of the dn2max atomic
-    const float *prev_nmax;   // hi_rows_frag_kernel<true> (r06, ONE pass over the table): the two squared-norm maxima a PREVIOUS
-    float *nm_out;            //   evaluation measured fix the scale; this pass's maxima per block go to nm_out[2][gridDim.x] and
-                              //   the consumer (dot_query_pipeline_kernel) raises the overflow flag if they ask for another scale
-    int frag;                 // 1: FRAGMENT-MAJOR output [rows_p / 32][units_p][64][16 B] -- chunk (row % 32) + 32 * k-half of
-                              // the 1-KiB block of (32-row group, unit): the A operand of v_mfma_f32_32x32x16_f16 in lane
-                              // order, one coalesced global_load_dwordx4 per block (lp_hi_stream.hip)
-};
-
-__global__ __launch_bounds__(256) void hi_rows_kernel(const HiRowsParams p)
-{
-    __shared__ unsigned bmax[4];
-    float scale = (float)(1 << SPLIT_SCALE_LOG2), nmax = 0.f;
-    if (p.nm_bmax) {        // (as query_pipeline_kernel: block maxima -> the two scalars, folded into what they hold)
-        __shared__ unsigned red[8];
-        unsigned m0 = 0u, m1 = 0u;
-        for (int j = threadIdx.x; j < p.nm_blocks; j += 256) {
-            m0 = max(m0, __float_as_uint(p.nm_bmax[j]));
-            m1 = max(m1, __float_as_uint(p.nm_bmax[p.nm_blocks + j]));
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = m0; red[4 + (threadIdx.x >> 6)] = m1; }
-        __syncthreads();
-        m0 = max(max(red[0], red[1]), max(red[2], red[3]));
-        m1 = max(max(red[4], red[5]), max(red[6], red[7]));
-        const float n0 = __uint_as_float(max(m0, __float_as_uint(*p.nmax0)));
-        const float n1 = p.nmax1 ? __uint_as_float(max(m1, __float_as_uint(*p.nmax1))) : 0.f;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            *const_cast<float *>(p.nmax0) = n0;
-            if (p.nmax1) *const_cast<float *>(p.nmax1) = n1;
-        }
-        nmax = n0 + n1;
-        scale = split_scale(nmax);
-    } else if (p.nmax0) {
-        nmax = *p.nmax0 + (p.nmax1 ? *p.nmax1 : 0.f);
-        scale = split_scale(nmax);
-    }
-    const float inv2 = 1.0f / (scale * scale);
-    const int K = p.K0 + p.K1;
-    const int tr_ = threadIdx.x >> 4, tu_ = threadIdx.x & 15;
-    const bool vec0 = (p.ld0 % 4 == 0) && ((size_t)p.X0 & 15) == 0;
-    const bool vec1 = p.X1 && (p.ld1 % 4 == 0) && ((size_t)p.X1 & 15) == 0 && (p.K0 % 4 == 0);
-    float dmax = 0.f;
-    for (int64_t r0 = (int64_t)blockIdx.x * 16; r0 < p.rows_p; r0 += (int64_t)gridDim.x * 16) {
-        const int64_t row = r0 + tr_;
-        const bool real = row < p.rows;
-        const int64_t srow = (p.row_index && real) ? p.row_index[row] : row;
-        float dn = 0.f;
-        for (int u = tu_; u < p.units_p; u += 16) {
-            const int k0 = u * 16;
-            float xs[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) xs[e] = 0.f;
-            if (real) {
-                if (k0 + 16 <= p.K0 && vec0) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X0 + srow * p.ld0 + k0);
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
-                } else if (k0 >= p.K0 && k0 + 16 <= K && vec1) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X1 + srow * p.ld1 + (k0 - p.K0));
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
-                } else if (k0 < K) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int k = k0 + e;
-                        if (k < p.K0) xs[e] = p.X0[srow * p.ld0 + k];
-                        else if (k < K) xs[e] = p.X1[srow * p.ld1 + (k - p.K0)];
-                    }
-                }
-            }
-            union { _Float16 h[16]; uint4 v[2]; } hi;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int k = k0 + e;
-                float x = xs[e] * scale;
-                _Float16 h = (_Float16)x;                   // round to nearest even
-                if (real && k < K) {
-                    const float d = x - (float)h;           // exact in fp32
-                    dn = fmaf(d, d, dn);
-                }
-                if (k == K || k == K + 1) {                 // the augmentation columns
-                    float a = 0.f;
-                    if (real) {
-                        if (p.aug_mode == 1) {              // L2 candidates: hi (column K) and lo (column K + 1) of -||e||^2/2
-                            const float full = p.aug[srow] * p.aug_mul * scale;
-                            const _Float16 fh = (_Float16)full;
-                            a = k == K ? (float)fh : (float)(_Float16)(full - (float)fh);
-                        } else if (p.aug_mode == 2) {       // L2 queries: 1 against both
-                            a = p.aug_mul * scale;
-                        } else if (p.aug_mode == 3 && k == K) {   // DOT queries: the guard column (see split_rows_kernel)
-                            a = fmaxf(0.25f * (sqrtf(p.aug[srow]) + sqrtf(nmax) * 0.00390625f) * scale, 1.0f);
-                        }
-                    } else if ((p.aug_mode == 1 || (p.aug_mode == 4 && k == K))) {
-                        a = -65504.f;                       // padding candidate: can never count
-                    }
-                    h = (_Float16)a;
-                }
-                hi.h[e] = h;
-            }
-            if (p.frag) {
-                uint4 *o = p.out + (((row >> 5) * p.units_p + u) << 6) + (row & 31);
-                o[0] = hi.v[0]; o[32] = hi.v[1];
-            } else {
-                uint4 *o = p.out + (row * p.units_p + u) * 2;
-                o[0] = hi.v[0]; o[1] = hi.v[1];
-            }
-        }
-        dn += __shfl_xor(dn, 8, 64);    // the 16 lanes of a row sit in one aligned group of the wavefront
-        dn += __shfl_xor(dn, 4, 64);
-        dn += __shfl_xor(dn, 2, 64);
-        dn += __shfl_xor(dn, 1, 64);
-        dn *= inv2 * 1.0001f;           // (fp32 summation error: K * 2^-24 relative)
-        if (real && tu_ == 0 && p.dn2) p.dn2[row] = dn;
-        if (real) dmax = fmaxf(dmax, dn);
-    }
-    if (p.dn2max || p.dn_bmax) {
-        unsigned m = __float_as_uint(dmax);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if ((threadIdx.x & 63) == 0) bmax[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned mm = max(max(bmax[0], bmax[1]), max(bmax[2], bmax[3]));
-            if (p.dn_bmax) p.dn_bmax[blockIdx.x] = __uint_as_float(mm);
-            else kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.dn2max), mm);
-        }
-    }
-}
-
-// ---- the same table for DOT candidates, FRAGMENT-MAJOR, with coalesced traffic on both sides (r06) -----------------------
-// hi_rows_kernel reads 64 bytes per lane (a wave's float4 load touches 16 B of 64 different 64-byte pieces) and writes a
-// fragment block 64 bytes at a time: at ComplEx d = 512 on 4.59 M entities it moves 28.8 GB in 8.9 ms (3.2 TB/s), the
-// address pipes being the limit, not HBM.  Here a block takes a 32-row group and walks the row in spans of 256 columns:
-// a wave reads 1 KiB of ONE row per instruction (lane l: columns 4 l .. 4 l + 3), converts, and leaves the f16 values in
-// an LDS tile laid out like the output -- [unit][k-half][row][16 B], a 16-byte pad per k-half block: the 16 lanes of a
-// write pass hit 16 different 8-byte bank pairs -- from which every wave then copies whole 1-KiB fragment blocks to the
-// table, one coalesced store per block.  Two LDS tiles, ONE barrier per span, the next span's loads in flight across it.
-// Same hi values as hi_rows_kernel (aug_mode 4: guard column K = 0 for real rows, -65504 for padding rows); the residual
-// sums are the same exact differences in another order (a bound input: any order, see the 1.0001 below).
-// Needs float4-readable rows (K0, K1, ld % 4 == 0, 16-byte aligned bases).
-constexpr int HF_HST = 512 + 16, HF_UST = 2 * HF_HST;     // LDS strides of a k-half block / a unit
-
-// FUSED (r06): no norm pass in front -- the scale comes from the maxima of the PREVIOUS evaluation (p.prev_nmax; any power
-// of two under which nothing overflows is a valid scale: the band is built from residuals measured HERE), the rows'
-// squared norms are summed on the way (a bound input: any order) and their maxima left per block in p.nm_out for the
-// query pipeline, which checks that they still ask for the scale that was used.
-template <bool FUSED>
-__global__ __launch_bounds__(256) void hi_rows_frag_kernel(const HiRowsParams p)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char tile[2][16 * HF_UST];
-    __shared__ unsigned bmax[4], nbmax[8];
-    float scale, nmax;
-    if (FUSED) {
-        nmax = p.prev_nmax[0] + p.prev_nmax[1];
-        scale = split_scale(nmax);
-    } else {       // the block maxima of dot_table_norm_max_kernel -> the two scalars (as hi_rows_kernel)
-        __shared__ unsigned red[8];
-        unsigned m0 = 0u, m1 = 0u;
-        for (int j = threadIdx.x; j < p.nm_blocks; j += 256) {
-            m0 = max(m0, __float_as_uint(p.nm_bmax[j]));
-            m1 = max(m1, __float_as_uint(p.nm_bmax[p.nm_blocks + j]));
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = m0; red[4 + (threadIdx.x >> 6)] = m1; }
-        __syncthreads();
-        m0 = max(max(red[0], red[1]), max(red[2], red[3]));
-        m1 = max(max(red[4], red[5]), max(red[6], red[7]));
-        const float n0 = __uint_as_float(max(m0, __float_as_uint(*p.nmax0)));
-        const float n1 = p.nmax1 ? __uint_as_float(max(m1, __float_as_uint(*p.nmax1))) : 0.f;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            *const_cast<float *>(p.nmax0) = n0;
-            if (p.nmax1) *const_cast<float *>(p.nmax1) = n1;
-        }
-        nmax = n0 + n1;
-        scale = split_scale(nmax);
-    }
-    const float inv2 = 1.0f / (scale * scale);
-    const int K = p.K0 + p.K1;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int nspan = (p.units_p + 15) >> 4;
-    const int64_t ngroups = p.rows_p >> 5;
-    const int wo = (lane >> 2) * HF_UST + ((lane >> 1) & 1) * HF_HST + (lane & 1) * 8;     // this lane's 8 bytes of a tile row
-    const int ro = (lane >> 5) * HF_HST + (lane & 31) * 16;                                 // this lane's chunk of a fragment block
-    float4 v[8];
-    float dn[8], nn0[8], nn1[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dn[j] = nn0[j] = nn1[j] = 0.f;
-    float dmax = 0.f, n0max = 0.f, n1max = 0.f;
-    auto load = [&](int64_t g, int s) {
-        const int col = s * 256 + 4 * lane;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int64_t row = g * 32 + wv * 8 + j;
-            v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < p.rows && col < K)
-                v[j] = col < p.K0 ? *reinterpret_cast<const float4 *>(p.X0 + row * p.ld0 + col)
-                                  : *reinterpret_cast<const float4 *>(p.X1 + row * p.ld1 + (col - p.K0));
-        }
-    };
-    int64_t g = blockIdx.x;
-    int s = 0, it = 0;
-    bool have = g < ngroups;
-    if (have) load(g, s);
-    while (have) {                      // (block-uniform)
-        unsigned char *tl = tile[it & 1];
-        const int col = s * 256 + 4 * lane;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const bool real = g * 32 + wv * 8 + j < p.rows;
-            const float xs[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-            if (FUSED) {        // (padding lanes hold zeros)
-                const float ss = fmaf(xs[0], xs[0], fmaf(xs[1], xs[1], fmaf(xs[2], xs[2], xs[3] * xs[3])));
-                if (col < p.K0) nn0[j] += ss; else nn1[j] += ss;
-            }
-            _Float16 h[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float x = xs[e] * scale;
-                h[e] = (_Float16)x;                         // round to nearest even
-                if (real && col < K) {                      // (K % 4 == 0: a float4 is data or padding as a whole)
-                    const float d = x - (float)h[e];        // exact in fp32
-                    dn[j] = fmaf(d, d, dn[j]);
-                }
-            }
-            if (col == K && !real) h[0] = (_Float16)(-65504.f);      // the guard column of a padding candidate: can never count
-            union { _Float16 hh[4]; uint2 u; } pk;
-            pk.hh[0] = h[0]; pk.hh[1] = h[1]; pk.hh[2] = h[2]; pk.hh[3] = h[3];
-            *reinterpret_cast<uint2 *>(tl + wo + (wv * 8 + j) * 16) = pk.u;
-        }
-        int64_t g2 = g;
-        int s2 = s + 1;
-        if (s2 == nspan) { s2 = 0; g2 += gridDim.x; }
-        const bool have2 = g2 < ngroups;
-        if (have2) load(g2, s2);
-        __syncthreads();                // the tile is complete; the other tile's readers of two spans ago are long past
-#pragma unroll
-        for (int uu = 0; uu < 4; ++uu) {
-            const int ul = wv * 4 + uu, u = s * 16 + ul;
-            if (u < p.units_p)
-                p.out[((g * p.units_p + u) << 6) + lane] = *reinterpret_cast<const uint4 *>(tl + ul * HF_UST + ro);
-        }
-        if (s == nspan - 1) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float a = dn[j];
-                for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-                a *= inv2 * 1.0001f;    // (fp32 summation error: K * 2^-24 relative)
-                if (g * 32 + wv * 8 + j < p.rows) dmax = fmaxf(dmax, a);
-                dn[j] = 0.f;
-                if (FUSED) {
-                    float b0 = nn0[j], b1 = nn1[j];
-                    for (int off = 32; off > 0; off >>= 1) { b0 += __shfl_xor(b0, off, 64); b1 += __shfl_xor(b1, off, 64); }
-                    n0max = fmaxf(n0max, b0 * 1.0001f);     // (summation order: K * 2^-24 relative)
-                    n1max = fmaxf(n1max, b1 * 1.0001f);
-                    nn0[j] = nn1[j] = 0.f;
-                }
-            }
-        }
-        g = g2; s = s2; have = have2; ++it;
-    }
-    unsigned m = __float_as_uint(dmax);
-    if (lane == 0) { bmax[wv] = m; nbmax[wv] = __float_as_uint(n0max); nbmax[4 + wv] = __float_as_uint(n1max); }   // (wave-uniform)
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        p.dn_bmax[blockIdx.x] = __uint_as_float(max(max(bmax[0], bmax[1]), max(bmax[2], bmax[3])));
-        if (FUSED) {
-            p.nm_out[blockIdx.x] = __uint_as_float(max(max(nbmax[0], nbmax[1]), max(nbmax[2], nbmax[3])));
-            p.nm_out[gridDim.x + blockIdx.x] = __uint_as_float(max(max(nbmax[4], nbmax[5]), max(nbmax[6], nbmax[7])));
-        }
-    }
-}
-
-// Squared-norm maxima of the rows of one or two tables ([Re | Im] segments of a DOT candidate table) in ONE sweep, any
-// summation order (they fix the operand scale and bound the error band; no score contains them): row_sqnorm_any_kernel
-// for both segments without the per-row outputs, the blocks' maxima as plain stores (bmax[2][gridDim.x]) -- the consumer
-// (hi_rows_kernel, nm_bmax) reduces them: no same-address atomics, no zero-fill of the scalars.
-__global__ __launch_bounds__(256) void dot_table_norm_max_kernel(const float *__restrict__ X0, int64_t ld0, int K0,
-                                                                 const float *__restrict__ X1, int64_t ld1, int K1,
-                                                                 int64_t rows, float *bmax_out)
-{
-    __shared__ unsigned wmax[8];
-    const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    float big0 = 0.f, big1 = 0.f;
-    for (int sg = 0; sg < (X1 ? 2 : 1); ++sg) {
-        const float *X = sg ? X1 : X0;
-        const int64_t ld = sg ? ld1 : ld0;
-        const int K = sg ? K1 : K0;
-        const bool vec = (K % 4 == 0) && (ld % 4 == 0) && ((size_t)X & 15) == 0;
-        float big = 0.f;
-        for (int64_t r0 = (int64_t)blockIdx.x * 64; r0 < rows; r0 += (int64_t)gridDim.x * 64) {
-            float acc[4] = {0.f, 0.f, 0.f, 0.f};
-            if (vec) {
-                for (int k = sub * 4; k < K; k += 64) {
-                    float4 t[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[j] = *reinterpret_cast<const float4 *>(X + min(r0 + grp * 4 + j, rows - 1) * ld + k);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc[j] = fmaf(t[j].x, t[j].x, acc[j]); acc[j] = fmaf(t[j].y, t[j].y, acc[j]);
-                        acc[j] = fmaf(t[j].z, t[j].z, acc[j]); acc[j] = fmaf(t[j].w, t[j].w, acc[j]);
-                    }
-                }
-            } else {
-                for (int k = sub; k < K; k += 16)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float x = X[min(r0 + grp * 4 + j, rows - 1) * ld + k];
-                        acc[j] = fmaf(x, x, acc[j]);
-                    }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float a = acc[j];
-                a += __shfl_xor(a, 8, 64); a += __shfl_xor(a, 4, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 1, 64);
-                big = __uint_as_float(max(__float_as_uint(big), __float_as_uint(a)));   // (rows past the end repeat the last row)
-            }
-        }
-        if (sg) big1 = big; else big0 = big;
-    }
-    unsigned m0 = __float_as_uint(big0), m1 = __float_as_uint(big1);
-    for (int off = 32; off > 0; off >>= 1) {
-        m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-        m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) { wmax[threadIdx.x >> 6] = m0; wmax[4 + (threadIdx.x >> 6)] = m1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        bmax_out[blockIdx.x] = __uint_as_float(max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
-        bmax_out[gridDim.x + blockIdx.x] = __uint_as_float(max(max(wmax[4], wmax[5]), max(wmax[6], wmax[7])));
-    }
-}
-
-// ---- candidate-table preparation of the L2 one-product sweep in ONE pass (r05) -----------------------------------
-// What kge_row_sqnorm (en, its maximum) + a zero-fill + kge_lp_hi_rows_frag (hi table, residual maximum) do in three
-// launches with the table read twice: a 256-thread block stages 16 rows in LDS; lanes 0..15 run the rows' sequential
-// ||e||^2 chains (row_sqnorm_kernel's: acc = fmaf(x_k, x_k, acc), k ascending -- the score contains en, same bits)
-// while all threads convert the data units to f16 hi parts (thread = row + 16 * unit: a unit's 16 rows are one 256-byte
-// run of the fragment-major table) and sum their residuals; the two augmentation columns follow once en is known.
-struct TablePrepParams {
-    const float *X;
-    int64_t ld, rows, rows_p;
-    int K, units_p;
-    float *en;                // (rows)
-    float *en_max;            // device scalar, max folded in
-    uint4 *out;               // fragment-major hi table
-    float *dn2max;            // device scalar, max folded in
-    float *block_max;         // optional [2][gridDim.x]: the blocks' two maxima as plain stores INSTEAD of the atomics -- ~900
-                              // same-address device-scope atomics per scalar serialise for ~50 us at the end of the kernel
-                              // (measured in situ: 65 against 14 us); the consumer (kge_lp_query_pipeline) reduces them
-    int dbg;                  // env KGE_TP_DBG (timing probes, wrong results): 1 no norm chain, 2 no conversions, 4 no table reads
-};
-
-__global__ __launch_bounds__(256) void table_prep_l2_kernel(const TablePrepParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) float tp_smem[];
-    const int K = p.K, LDS_LD = ((K + 3) & ~3) + 4;         // (row stride: 16-byte aligned, 4 floats of padding)
-    float *xs = tp_smem;                                    // [16][LDS_LD]
-    float *dnp = xs + 16 * LDS_LD;                          // [16][17] partial residual sums
-    float *ens = dnp + 16 * 17;                             // [16]
-    __shared__ unsigned bmax[2];
-    const int tid = threadIdx.x, r = tid & 15, uu = tid >> 4;
-    const float scale = (float)(1 << SPLIT_SCALE_LOG2);
-    const float inv2 = 1.0f / (scale * scale);
-    const int units_d = (K + 15) >> 4;                      // units that hold data columns
-    float emax_b = 0.f, dmax_b = 0.f;
-    for (int64_t r0 = (int64_t)blockIdx.x * 16; r0 < p.rows_p; r0 += (int64_t)gridDim.x * 16) {
-        // stage the 16 rows (rows past the table: zeros)
-        const int nv = K >> 2;                              // float4 per row (K % 4 == 0, checked by the host)
-        for (int idx = tid; idx < 16 * nv; idx += 256) {
-            const int rr = idx / nv, c = idx - rr * nv;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r0 + rr < p.rows && !(p.dbg & 4)) v = *reinterpret_cast<const float4 *>(p.X + (r0 + rr) * p.ld + c * 4);
-            *reinterpret_cast<float4 *>(xs + rr * LDS_LD + c * 4) = v;
-        }
-        __syncthreads();
-        const int64_t row = r0 + r;
-        const bool real = row < p.rows;
-        if (tid < 16 && !(p.dbg & 1)) {                     // the sequential chain of ||e||^2
-            const float *x = xs + r * LDS_LD;
-            float acc = 0.f;
-            for (int k = 0; k < K; k += 4) {
-                const float4 t = *reinterpret_cast<const float4 *>(x + k);
-                acc = fmaf(t.x, t.x, acc);
-                acc = fmaf(t.y, t.y, acc);
-                acc = fmaf(t.z, t.z, acc);
-                acc = fmaf(t.w, t.w, acc);
-            }
-            ens[r] = acc;
-            if (real) {
-                p.en[row] = acc;
-                emax_b = __uint_as_float(max(__float_as_uint(emax_b), __float_as_uint(acc)));
-            }
-        }
-        // data units: hi parts + residuals (the units holding an augmentation column are finished below)
-        float dn = 0.f;
-        for (int u = uu; u < p.units_p; u += 16) {
-            const int k0 = u * 16;
-            if (k0 + 16 <= K && !(p.dbg & 2)) {
-                union { _Float16 h[16]; uint4 v[2]; } hi;
-                const float *x = xs + r * LDS_LD + k0;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float xsj = x[e] * scale;
-                    const _Float16 h = (_Float16)xsj;
-                    const float d = xsj - (float)h;
-                    dn = fmaf(d, d, dn);
-                    hi.h[e] = h;
-                }
-                uint4 *o = p.out + (((row >> 5) * p.units_p + u) << 6) + (row & 31);
-                o[0] = hi.v[0]; o[32] = hi.v[1];
-            }
-        }
-        dnp[r * 17 + uu] = dn;
-        __syncthreads();
-        // units that straddle / follow K: data tail, the two augmentation columns (hi and lo of -||e||^2/2), zeros
-        for (int u = (K >> 4) + uu; u < p.units_p; u += 16) {
-            const int k0 = u * 16;
-            union { _Float16 h[16]; uint4 v[2]; } hi;
-            float dt = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int k = k0 + e;
-                float a = 0.f;
-                if (k < K) {
-                    a = xs[r * LDS_LD + k] * scale;
-                    const float d = a - (float)(_Float16)a;
-                    dt = fmaf(d, d, dt);
-                } else if (k == K || k == K + 1) {
-                    if (real) {
-                        const float full = ens[r] * -0.5f * scale;
-                        const _Float16 fh = (_Float16)full;
-                        a = k == K ? (float)fh : (float)(_Float16)(full - (float)fh);
-                    } else {
-                        a = -65504.f;                       // padding candidate: can never count
-                    }
-                }
-                hi.h[e] = (_Float16)a;
-            }
-            if (u == (K >> 4)) dnp[r * 17 + 16] = dt;           // (the one unit that may hold a data tail; always present)
-            uint4 *o = p.out + (((row >> 5) * p.units_p + u) << 6) + (row & 31);
-            o[0] = hi.v[0]; o[32] = hi.v[1];
-        }
-        __syncthreads();
-        if (tid < 16 && real) {
-            float t = 0.f;
-            for (int j = 0; j < 17; ++j) t += dnp[r * 17 + j];
-            t *= inv2 * 1.0002f;                            // (fp32 summation error, any order: K * 2^-24 relative)
-            dmax_b = fmaxf(dmax_b, t);
-        }
-        __syncthreads();
-    }
-    // one atomic per block for each maximum
-    if (tid < 64) {
-        unsigned m0 = __float_as_uint(emax_b), m1 = __float_as_uint(dmax_b);
-        for (int off = 8; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if (tid == 0) { bmax[0] = m0; bmax[1] = m1; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (p.block_max) {
-            p.block_max[blockIdx.x] = __uint_as_float(bmax[0]);
-            p.block_max[gridDim.x + blockIdx.x] = __uint_as_float(bmax[1]);
-        } else {
-            if (p.en_max) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.en_max), bmax[0]);
-            if (p.dn2max) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.dn2max), bmax[1]);
-        }
-    }
-}
-
-// e2pref[u] = max over rows of the squared norm of the row's first (u+1)*16 data columns: with the
-// same prefix norms of a query, || q[:k] || * sqrt(e2pref) bounds every partial sum the MFMA
-// accumulator holds while it works through unit u (Cauchy-Schwarz on the prefix) -- the error band
-// then charges each unit with ITS magnitude instead of the full ||q|| ||e|| (about half of it).
-__global__ __launch_bounds__(1024) void prefix_max_kernel(const float *__restrict__ cell_ss, int64_t rows_p, int64_t rows,
-                                                          int units_p, float *e2pref)
-{
-    // block maxima in LDS, ONE global atomic per (block, unit): same-line atomics serialise at ~12 ns each
-    __shared__ unsigned smax[128];
-    const int lane = threadIdx.x & 63;
-    for (int u = threadIdx.x; u < units_p; u += blockDim.x) smax[u] = 0u;
-    __syncthreads();
-    for (int64_t r0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) - lane; r0 < rows;
-         r0 += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = r0 + lane;
-        float prefix = 0.f;
-        for (int u = 0; u < units_p; ++u) {
-            if (r < rows) prefix += cell_ss[(int64_t)u * rows_p + r];
-            unsigned m = __float_as_uint(prefix);       // sums of squares: >= 0, ordered like their bit patterns
-            for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-            if (lane == 0) atomicMax(&smax[u], m);
-        }
-    }
-    __syncthreads();
-    for (int u = threadIdx.x; u < units_p; u += blockDim.x) kge_atomic_max_u32(reinterpret_cast<unsigned *>(e2pref) + u, smax[u]);
-}
-
-// One step of the per-query magnitude sum: prefix += cell sum;  amag += sqrt(prefix * e2pref[u])
-__device__ __forceinline__ void split_amag_step(float &prefix, float &amag, float ss, float e2u)
-{
-    prefix = prefix + ss;
-    amag = amag + sqrtf(prefix * e2u);
-}
-
-__global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ x, int64_t n, float *max_io)
-{
-    // The maximum is taken on the BIT PATTERNS of |x| as unsigned integers: for non-negative floats that is the
-    // float order, +inf sorts above every finite value and every NaN above +inf -- a NaN element therefore
-    // reaches max_io as a NaN (fmaxf would skip it), and the threshold kernels that consume the scalar turn a
-    // non-finite maximum into their overflow flag -> exact path (the SAD prefilter quantised a NaN
-    // element to a finite value).  One atomic per block (thousands of same-address atomics serialise in the L2:
-    // 96 us for 14 MB when every wave issued its own).
-    __shared__ unsigned wmax[4];
-    unsigned u = 0u;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-        const int64_t n4 = n >> 2;
-        const uint4 *x4 = reinterpret_cast<const uint4 *>(x);
-        for (int64_t i = tid; i < n4; i += nth) {
-            const uint4 v = x4[i];
-            u = max(max(u, v.x & 0x7fffffffu), max(v.y & 0x7fffffffu, max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
-        }
-        for (int64_t i = (n4 << 2) + tid; i < n; i += nth) u = max(u, __float_as_uint(x[i]) & 0x7fffffffu);
-    } else {
-        for (int64_t i = tid; i < n; i += nth) u = max(u, __float_as_uint(x[i]) & 0x7fffffffu);
-    }
-    for (int off = 32; off > 0; off >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, off, 64));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = u;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
-        kge_atomic_max_u32(reinterpret_cast<unsigned *>(max_io), u);
-    }
-}
 
 // Self-test of the accumulation model behind c_acc = 1.25 (tools/probe/mfma_probe.hip is the long
 // version): v_mfma_f32_32x32x16_f16 computes each output as two passes  acc <- acc + sum of 8 products,
@@ -841,78 +164,6 @@ struct SplitThrParams {
     int q_scale_per_query;          // DOT, level 1: the query operand of row i is scaled by split_scale(||q_i||^2), its own norm
                                     // (kge_lp_dot_query_pipeline), not by the batch maximum's; qn0 then holds the total
 };
-
-// (a_lo, a_hi) of the plain L2 expansion, unscaled half-width logic shared by split_thr_kernel and the fused
-// query pipeline (which must produce the same thresholds bit for bit)
-// The count kernel reads "v >= a_lo" off the sign of v - a_lo, which is wrong only for v = -0, a_lo = +0:
-// a zero threshold is moved down to the next normal number (widening the band is always safe).
-__device__ __forceinline__ float split_nonzero_lo(float lo) { return lo == 0.f ? -1.17549435e-38f : lo; }
-
-// amag: the sum over the k16 units of the bound on the accumulator's magnitude in that unit (split_amag_step,
-// times 1.003 for the cross terms and f16 roundings), or < 0 when the prefix norms are not at hand: every unit is
-// then charged with the full ||q|| ||e||.
-__device__ __forceinline__ float split_acc_err(float amag, float aug_mag, float mag, int units, float c_acc,
-                                               float adds_per_unit = 48.0f)
-{
-    const float two24 = 5.9604645e-8f;
-    const float sum_mag = amag >= 0.f ? amag * 1.003f + aug_mag : (float)units * mag;
-    return c_acc * adds_per_unit * two24 * sum_mag;  // 48 (one-product level: 16) additions per unit, each within c_acc * 2^-24 of the magnitude
-}
-// Rounding error of the exact fp32 chain the counts are defined by: one fmaf rounding per element, each within
-// 2^-24 of the partial sum it produces (running error bound) -- 16 per unit against the same prefix magnitudes,
-// or gamma_K * ||q|| ||e|| without them.
-__device__ __forceinline__ float split_chain_err(float amag, float mag, int K)
-{
-    const float two24 = 5.9604645e-8f;
-    return amag >= 0.f ? 16.16f * two24 * amag * 1.003f : 1.01f * (float)K * two24 * mag;
-}
-
-__device__ __forceinline__ float2 split_thr_l2(float q, float st, float em, int K, int units, float c_acc, float eps_scale,
-                                               float amag)
-{
-    const float two22 = 2.3841858e-7f;
-    const float eps_rel = 3.01f * two22;             // split residual
-    const float enrm = sqrtf(em) * 1.000001f, qnrm = sqrtf(q) * 1.000001f;
-    const float out_scale = (float)(1 << SPLIT_SCALE_LOG2) * (float)(1 << SPLIT_SCALE_LOG2);
-    const float u = -st;                             // count c iff v_c <= u, v = ||q||^2 + ||e||^2 - 2 q.e
-    const float mag = qnrm * enrm + 0.5f * em;       // >= sum of |products|
-    const float eps_dot = split_acc_err(amag, 0.5f * em, mag, units, c_acc) + split_chain_err(amag, mag, K) + eps_rel * mag +
-                          2.5e-7f * (qnrm + enrm) + 4e-9f;
-    const float eps_v = (2.0f * eps_dot + 4.0f * two22 * (q + em + fabsf(u))) * eps_scale;
-    const float mid = 0.5f * (q - u);
-    const float hw = 0.5f * eps_v + two22 * (fabsf(q) + fabsf(u));
-    return make_float2(split_nonzero_lo((mid - hw) * out_scale), (mid + hw) * out_scale);
-}
-
-// ONE-PRODUCT level (LV = 1 of the count kernel): acc = sum_k qh*eh (+ the two-term augmentation column), i.e. the
-// split residual is no longer 3 * 2^-22 of the magnitude but the operands' own f16 rounding residuals,
-//     q.e - qh.eh = dq.e + qh.de,    |.| <= ||dq|| ||e|| + ||qh|| ||de||,   ||qh|| <= ||q|| + ||dq||,
-// with dq = q - hi(q) MEASURED per query (dq2 = ||dq||^2, exact differences summed in fp32) and de2m >= max_c ||de_c||^2:
-// ~4.7e-4 of ||q|| max||e|| at K = 200 (a third of the candidates' values round up, a third down ...), 8 x the band of the
-// three-product sweep -- which buys one MFMA per k16 unit instead of three and half the operand bytes.  The augmentation
-// column -||e||^2/2 rides as TWO columns (hi, lo: residual 2^-22); the accumulation term has 16 additions per unit.
-__device__ __forceinline__ float split_hi_resid(float qnrm, float enrm, float em_aug, float dq2, float de2m)
-{
-    const float two22 = 2.3841858e-7f;
-    const float dqn = sqrtf(dq2) * 1.0001f, den = sqrtf(de2m) * 1.0001f;
-    return (dqn * enrm + (qnrm + dqn) * den) * 1.0005f + 1.01f * two22 * em_aug;
-}
-
-__device__ __forceinline__ float2 split_thr_l2_hi(float q, float st, float em, int K, int units, float c_acc, float eps_scale,
-                                                  float dq2, float de2m)
-{
-    const float two22 = 2.3841858e-7f;
-    const float enrm = sqrtf(em) * 1.000001f, qnrm = sqrtf(q) * 1.000001f;
-    const float out_scale = (float)(1 << SPLIT_SCALE_LOG2) * (float)(1 << SPLIT_SCALE_LOG2);
-    const float u = -st;                             // count c iff v_c <= u, v = ||q||^2 + ||e||^2 - 2 q.e
-    const float mag = qnrm * enrm + 0.5f * em;       // >= sum of |products|
-    const float eps_dot = split_acc_err(-1.0f, 0.5f * em, mag, units, c_acc, 16.0f) + split_chain_err(-1.0f, mag, K) +
-                          split_hi_resid(qnrm, enrm, 0.5f * em, dq2, de2m) + 2.5e-7f * (qnrm + enrm) + 4e-9f;
-    const float eps_v = (2.0f * eps_dot + 4.0f * two22 * (q + em + fabsf(u))) * eps_scale;
-    const float mid = 0.5f * (q - u);
-    const float hw = 0.5f * eps_v + two22 * (fabsf(q) + fabsf(u));
-    return make_float2(split_nonzero_lo((mid - hw) * out_scale), (mid + hw) * out_scale);
-}
 
 __global__ void split_thr_kernel(const SplitThrParams p)
 {
@@ -981,630 +232,38 @@ __global__ void split_thr_kernel(const SplitThrParams p)
         } else if (p.mode == KGE_LP_L2_EXPAND) {
             p.thr[i] = split_thr_l2(q, p.s_true[i], em, p.K, p.units, p.c_acc, p.eps_scale, amag);
         } else if (p.mode >= KGE_LP_L2_PROJH) {
-            const float out_scale = (float)(1 << SPLIT_SCALE_LOG2) * (float)(1 << SPLIT_SCALE_LOG2);
-            const float u = -p.s_true[i];                    // count c iff v_c <= u, v = ||q||^2 + ||e||^2 - 2 q.e
-            const float mag = qnrm * enrm + 0.5f * em;       // >= sum of |products|
-            const float eps_dot = p.level == 1
-                ? split_acc_err(-1.0f, 0.5f * em, mag, p.units, p.c_acc, 16.0f) + split_chain_err(-1.0f, mag, p.K) +
-                  split_hi_resid(qnrm, enrm, 0.5f * em, dq2, de2m) + 2.5e-7f * (qnrm + enrm) + 4e-9f
-                : split_acc_err(amag, 0.5f * em, mag, p.units, p.c_acc) + split_chain_err(amag, mag, p.K) +
-                  eps_rel * mag + 2.5e-7f * (qnrm + enrm) + 4e-9f;
-            const float eps_v = (2.0f * eps_dot + 4.0f * two22 * (q + em + fabsf(u))) * p.eps_scale;
-            const float mid = 0.5f * (q - u);
-            float hw = 0.5f * eps_v + two22 * (fabsf(q) + fabsf(u));
-            if (p.mode >= KGE_LP_L2_PROJH) {
-                // + the projection term corr = x (x z + p)  resp.  y (y z + 2 g + p): it is computed exactly in fp32
-                // by both paths but enters in a different association -> a few ulps of its largest possible size
-                const float pi = p.pz[i * p.ldw], zi = p.pz[i * p.ldw + 1];
-                // |X[r_i, c]| = |w_i . e_c| <= ||w_i|| max||e||  (Cauchy-Schwarz; ||w_i||^2 = z_i + 2 for TransH, z_i for TransD) when
-                // no measured maximum is given: the term below is 2^-22 of cmax, a looser bound costs nothing
-                const float wn2 = p.mode == KGE_LP_L2_PROJH ? zi + 2.0f : zi;
-                const float xm = p.xabsmax ? *p.xabsmax : sqrtf(fmaxf(wn2, 0.f) * em) * 1.000001f;
-                const float ym = p.mode == KGE_LP_L2_PROJD ? *p.yabsmax : 0.f;
-                const float cmax = p.mode == KGE_LP_L2_PROJH ? xm * (xm * fabsf(zi) + fabsf(pi))
-                                                             : ym * (ym * fabsf(zi) + 2.0f * xm + fabsf(pi));
-                hw += 8.0f * two22 * cmax * p.eps_scale + two22 * cmax;
-                p.thr4[i] = make_float4(split_nonzero_lo((mid - hw) * out_scale), (mid + hw) * out_scale, pi, zi);
-                continue;
-            }
-        } else {
+            const float2 b = split_band_l2(p.level, q, p.s_true[i], em, p.K, p.units, p.c_acc, p.eps_scale, amag, dq2, de2m);
+            // + the projection term corr = x (x z + p)  resp.  y (y z + 2 g + p): it is computed exactly in fp32
+            // by both paths but enters in a different association -> a few ulps of its largest possible size
+            const float pi = p.pz[i * p.ldw], zi = p.pz[i * p.ldw + 1];
+            // |X[r_i, c]| = |w_i . e_c| <= ||w_i|| max||e||  (Cauchy-Schwarz; ||w_i||^2 = z_i + 2 for TransH, z_i for TransD) when
+            // no measured maximum is given: the term below is 2^-22 of cmax, a looser bound costs nothing
+            const float wn2 = p.mode == KGE_LP_L2_PROJH ? zi + 2.0f : zi;
+            const float xm = p.xabsmax ? *p.xabsmax : sqrtf(fmaxf(wn2, 0.f) * em) * 1.000001f;
+            const float ym = p.mode == KGE_LP_L2_PROJD ? *p.yabsmax : 0.f;
+            const float cmax = p.mode == KGE_LP_L2_PROJH ? xm * (xm * fabsf(zi) + fabsf(pi))
+                                                         : ym * (ym * fabsf(zi) + 2.0f * xm + fabsf(pi));
+            const float2 t = split_thr_pack_l2(make_float2(b.x, b.y + (8.0f * two22 * cmax * p.eps_scale + two22 * cmax)));
+            p.thr4[i] = make_float4(t.x, t.y, pi, zi);
+        } else if (p.level == 1) {
             // count c iff dot_c >= s_true; both operands carry their own power-of-two scale
             const float qm = p.q_scale_per_query ? q : *p.qmax0 + (p.qmax1 ? *p.qmax1 : 0.f);
+            p.thr[i] = split_thr_dot_hi(q, p.s_true[i], em, p.K, p.units, p.c_acc, p.eps_scale, dq2, de2m, qm, split_scale(qm),
+                                        split_scale(em));
+        } else {
+            // ... on three products: the one copy of this band (prefix magnitudes, the straddle term; per-query scales
+            // exist on the one-product level only, kge_lp_split_count checks)
+            const float qm = *p.qmax0 + (p.qmax1 ? *p.qmax1 : 0.f);
             const float out_scale = split_scale(qm) * split_scale(em);
             const float st = p.s_true[i];
             const float sqk = sqrtf((float)p.K);
             const float eps_abs = 1.4901161e-8f * sqk * (sqrtf(qm) * enrm + sqrtf(em) * qnrm) + 1e-30f;
-            const float eps_dot = p.level == 1
-                ? (split_acc_err(-1.0f, 0.f, qnrm * enrm, p.units, p.c_acc, 16.0f) + split_chain_err(-1.0f, qnrm * enrm, p.K) +
-                   split_hi_resid(qnrm, enrm, 0.f, dq2, de2m) + eps_abs) * p.eps_scale
-                : (split_acc_err(amag, 0.f, qnrm * enrm, p.units, p.c_acc) +
-                   split_chain_err(amag, qnrm * enrm, p.K) + straddle * qnrm * enrm +
-                   eps_rel * qnrm * enrm + eps_abs) * p.eps_scale;
+            const float eps_dot = (split_acc_err(amag, 0.f, qnrm * enrm, p.units, p.c_acc) +
+                                   split_chain_err(amag, qnrm * enrm, p.K) + straddle * qnrm * enrm +
+                                   eps_rel * qnrm * enrm + eps_abs) * p.eps_scale;
             const float hw = eps_dot + two22 * fabsf(st);
             p.thr[i] = make_float2(split_nonzero_lo((st - hw) * out_scale), (st + hw) * out_scale);
         }
-    }
-}
-
-// ---- fused query side of one TransE-L2 batch -----------------------------------
-// One wavefront per 64 queries does what lp_prep + row_sqnorm + pair_scores + split_rows(Q) + split_thr
-// do in five launches: q = e_src +- r (written for the later exact kernels), ||q||^2 and the exact true
-// score by the SAME sequential chains (one lane per query, rows staged cooperatively through LDS), the
-// two thresholds and the f16 split row.  Bit-identical outputs to the separate kernels.
-struct QueryPipeParams {
-    int tail;                       // 1: q = E[h] + R[r], true = t;  0: q = E[t] - R[r], true = h;
-                                    // 2: both sides in one batch -- queries [0, Bh) tail side, [Bh, 2 Bh) head side
-    int64_t Bh;                     // facts per side (tail == 2: B = 2 Bh)
-    const float *E, *R;
-    int d;
-    const int64_t *h, *t, *r;
-    int64_t B, Bp;
-    const float *en;                // ||E[c]||^2
-    const float *emax;              // device scalar max ||e||^2
-    float *qmax_io;                 // device scalar, max ||q||^2 folded in (may be NULL)
-    float c_acc, eps_scale;
-    int units, units_p;
-    float *Q, *qn, *s_true;
-    float2 *thr;
-    _Float16 *Qs;
-    int32_t *list_count;
-    const float *e2pref;            // optional: prefix squared-norm maxima of the entity table (tighter error band)
-    const int32_t *qs_row;          // optional: row of Qs that receives query i's split cells (< 0: none -- a query whose
-                                    // row another query of the same key already provides); NULL: row i
-    int level;                      // 1: one-product level -- Qs is a PLANAR hi operand (units_p = kge_lp_hi_units), two
-                                    // augmentation columns, thresholds from the measured residual ||q - hi(q)||
-    const float *de2max;            // level 1: device scalar >= max_c ||e_c - hi(e_c)||^2
-    float *q_dn2;                   // level 1, optional: ||q_i - hi(q_i)||^2 per query (for a later kge_lp_split_count
-                                    // that recomputes the thresholds: thr_ready = 0)
-    const float *tp_bmax;           // optional [2][tp_blocks]: the block maxima kge_lp_table_prep_l2 left instead of its atomics:
-    int tp_blocks;                  // every block reduces them (emax, de2max), block 0 stores the two scalars
-    float *emax_out, *de2max_out;
-    int32_t *zero_i32;              // optional: zero_n int32 zeroed by this launch (the batch's rank counters)
-    int64_t zero_n;
-    int dbg;                        // env KGE_QP_DBG (timing probes, wrong results): 1 no chains, 2 no split cells, 4 no Q store,
-                                    // 8 no row loads after the first chunk, 16 no block-maxima reduction, 32 no final atomic
-};
-
-template <int QPW>   // queries per wavefront: their chains run on lanes 0..QPW-1, loads / stores use all 64 lanes
-__global__ __launch_bounds__(256) void query_pipeline_kernel(const QueryPipeParams p)
-{
-    // rows staged cooperatively 48 k at a time (row stride 52 floats: conflict-free b128), the two
-    // sequential chains run one lane per query; few queries per wavefront = many wavefronts in flight
-    // (the chains are latency bound)
-    constexpr int KC = 48, LD = 52;
-    // (4 independent wavefronts per block, each on its own LDS slice: they only share the final atomic)
-    __shared__ __attribute__((aligned(16))) float qs_all[4 * QPW * LD];
-    __shared__ __attribute__((aligned(16))) float ts_all[4 * QPW * LD];
-    __shared__ unsigned wmax[4];
-    __shared__ float dnp_all[4 * QPW * 8];          // level 1: residual sums per (row, 8-column group) of the current chunk
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float *qs = qs_all + wv * QPW * LD, *ts = ts_all + wv * QPW * LD, *dnp = dnp_all + wv * QPW * 8;
-    const int d = p.d, kpad = p.units_p * 16;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *p.list_count = 0;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.zero_n; j += (int64_t)gridDim.x * 256) p.zero_i32[j] = 0;
-    float em, de2m = 0.f;
-    if (p.tp_bmax && !(p.dbg & 16)) {        // the table preparation's block maxima -> the two scalars (values >= 0: ordered like their bits)
-        __shared__ unsigned red[8];
-        unsigned m0 = 0u, m1 = 0u;
-        for (int j = threadIdx.x; j < p.tp_blocks; j += 256) {
-            m0 = max(m0, __float_as_uint(p.tp_bmax[j]));
-            m1 = max(m1, __float_as_uint(p.tp_bmax[p.tp_blocks + j]));
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if (lane == 0) { red[wv] = m0; red[4 + wv] = m1; }
-        __syncthreads();
-        m0 = max(max(red[0], red[1]), max(red[2], red[3]));
-        m1 = max(max(red[4], red[5]), max(red[6], red[7]));
-        // (folded into what the scalars already hold -- the guard vector is zeroed per evaluation, other shards may add)
-        em = __uint_as_float(max(m0, __float_as_uint(*p.emax)));
-        de2m = __uint_as_float(max(m1, p.de2max ? __float_as_uint(*p.de2max) : 0u));
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0) { *p.emax_out = em; if (p.de2max_out) *p.de2max_out = de2m; }
-    } else {
-        em = *p.emax;
-        if (p.level == 1) de2m = *p.de2max;
-    }
-    float qbig = 0.f;
-    const int64_t ngroups = (p.Bp + QPW - 1) / QPW;
-    for (int64_t grp = (int64_t)blockIdx.x * 4 + wv; grp < ngroups; grp += (int64_t)gridDim.x * 4) {
-        const int64_t i = grp * QPW + lane;
-        const bool valid = lane < QPW && i < p.B;
-        const int64_t ic = valid ? i : 0;
-        const bool tl = p.tail == 2 ? ic < p.Bh : p.tail == 1;          // this query's side
-        const int64_t fi = (p.tail == 2 && ic >= p.Bh) ? ic - p.Bh : ic; // its fact
-        const int64_t src = tl ? p.h[fi] : p.t[fi], tru = tl ? p.t[fi] : p.h[fi], ri = p.r[fi];
-        const int tli = tl ? 1 : 0;
-        float qn = 0.f, acc = 0.f;
-        float amag = 0.f;                                        // split_thr's magnitude sum
-        float dn = 0.f;                                          // level 1: || (q - hi(q)) * 2^12 ||^2
-        // Software-pipelined staging: the three row loads of the NEXT chunk are issued before this chunk's two
-        // sequential chains run (they are the latency of this kernel: 48 dependent FMA pairs per chunk), so a
-        // group of queries costs one load latency plus its chains instead of one load latency per chunk.
-        constexpr int NP = KC / 4, ITS = (QPW * NP + 63) / 64;     // 16-byte pieces per full row chunk; passes per chunk
-        float4 pe[ITS], pr[ITS], pt[ITS];
-#define KGE_QP_FETCH(K0)                                                                                     \
-    {                                                                                                        \
-        const int pcs_ = max(0, min(KC, d - (K0))) >> 2;                                                     \
-        _Pragma("unroll") for (int it = 0; it < ITS; ++it) {                                                 \
-            const int idx = it * 64 + lane;                                                                  \
-            const bool act = idx < QPW * pcs_;                                                               \
-            const int rr = act ? idx / pcs_ : 0, pc = act ? idx - rr * pcs_ : 0;                             \
-            const int64_t s_ = __shfl(src, rr, 64), r_ = __shfl(ri, rr, 64), t_ = __shfl(tru, rr, 64);       \
-            if (act) {                                                                                       \
-                pe[it] = *reinterpret_cast<const float4 *>(p.E + s_ * d + (K0) + pc * 4);                    \
-                pr[it] = *reinterpret_cast<const float4 *>(p.R + r_ * d + (K0) + pc * 4);                    \
-                pt[it] = *reinterpret_cast<const float4 *>(p.E + t_ * d + (K0) + pc * 4);                    \
-            }                                                                                                \
-        }                                                                                                    \
-    }
-        KGE_QP_FETCH(0)
-        for (int k0 = 0; k0 < kpad; k0 += KC) {
-            const int kc = max(0, min(KC, d - k0));              // data columns of this chunk
-            const int pieces = kc >> 2;
-#pragma unroll
-            for (int it = 0; it < ITS; ++it) {                   // uniform trip count (shuffles inside)
-                const int idx = it * 64 + lane;
-                const bool act = idx < QPW * pieces;
-                const int rr = act ? idx / pieces : 0, pc = act ? idx - rr * pieces : 0;
-                const bool tl_ = __shfl(tli, rr, 64) != 0;
-                if (!act) continue;
-                const float4 e4 = pe[it], r4 = pr[it], t4 = pt[it];
-                float4 q4;                                       // lp_prep_kernel, translation.py:105-125
-                q4.x = tl_ ? e4.x + r4.x : e4.x - r4.x;
-                q4.y = tl_ ? e4.y + r4.y : e4.y - r4.y;
-                q4.z = tl_ ? e4.z + r4.z : e4.z - r4.z;
-                q4.w = tl_ ? e4.w + r4.w : e4.w - r4.w;
-                const int64_t row = grp * QPW + rr;
-                if (row < p.B && !(p.dbg & 4)) *reinterpret_cast<float4 *>(p.Q + row * d + k0 + pc * 4) = q4;
-                *reinterpret_cast<float4 *>(qs + rr * LD + pc * 4) = q4;
-                *reinterpret_cast<float4 *>(ts + rr * LD + pc * 4) = t4;
-            }
-            if (k0 + KC < kpad && !(p.dbg & 8)) KGE_QP_FETCH(k0 + KC)
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (kc > 0 && lane < QPW && !(p.dbg & 1)) {
-                const float *x = qs + lane * LD;
-                // row_sqnorm_kernel's chain; its value at the end of every k16 cell is the prefix squared norm
-                // of the magnitude sum (split_thr_kernel adds up cell sums instead: equal up to rounding, and
-                // the band carries a 1.003 factor)
-                // Whole k16 cells: the cell's 16 query and 16 true-entity values come in with 8 b128 LDS reads, then the
-                // two dependent chains run side by side (||q||^2 in ascending k; the true score in the tile kernel's
-                // order, 8-blocks ascending and k = 0,4,1,5,2,6,3,7 inside) -- one LDS round trip per cell instead of
-                // one per element / per 8-block and chain.  Same operations in the same order: same bits.
-                const float *tt = ts + lane * LD;
-                int k = 0;
-                for (; k + 16 <= kc; k += 16) {
-                    float xv[16], tv[16];
-#pragma unroll
-                    for (int j4 = 0; j4 < 4; ++j4) {
-                        const float4 v = *reinterpret_cast<const float4 *>(x + k + 4 * j4);
-                        const float4 w = *reinterpret_cast<const float4 *>(tt + k + 4 * j4);
-                        xv[4 * j4] = v.x; xv[4 * j4 + 1] = v.y; xv[4 * j4 + 2] = v.z; xv[4 * j4 + 3] = v.w;
-                        tv[4 * j4] = w.x; tv[4 * j4 + 1] = w.y; tv[4 * j4 + 2] = w.z; tv[4 * j4 + 3] = w.w;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) qn = fmaf(xv[j], xv[j], qn);
-#pragma unroll
-                    for (int b8 = 0; b8 < 16; b8 += 8) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            acc = fmaf(xv[b8 + j], tv[b8 + j], acc);
-                            acc = fmaf(xv[b8 + 4 + j], tv[b8 + 4 + j], acc);
-                        }
-                    }
-                    if (p.e2pref) amag = amag + sqrtf(qn * p.e2pref[(k0 + k) >> 4]);
-                }
-                const int ktail = k;
-                for (; k < kc; ++k) {
-                    qn = fmaf(x[k], x[k], qn);
-                    if (p.e2pref && (((k0 + k) & 15) == 15 || k0 + k == d - 1))
-                        amag = amag + sqrtf(qn * p.e2pref[(k0 + k) >> 4]);
-                }
-                if (ktail < kc) acc = lp_chain_dot(x + ktail, tt + ktail, kc - ktail, acc);   // the pair kernel's chain
-            }
-            // split cells of this chunk: 8 consecutive k of one row per lane and pass
-            const int ngr = (p.dbg & 2) ? 0 : min(KC, kpad - k0) >> 3;
-            for (int idx = lane; idx < QPW * ngr; idx += 64) {
-                const int rr = idx / ngr, gq = idx - rr * ngr;
-                const int64_t row = grp * QPW + rr;
-                union { _Float16 h[8]; uint4 v; } hi, lo;
-                float dsum = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int k = k0 + gq * 8 + e;
-                    float xv = 0.f;
-                    if (row < p.B) xv = k < d ? qs[rr * LD + gq * 8 + e] : ((k == d || (p.level == 1 && k == d + 1)) ? 1.0f : 0.f);
-                    xv *= (float)(1 << SPLIT_SCALE_LOG2);
-                    const _Float16 hh = (_Float16)xv;
-                    hi.h[e] = hh;
-                    const float dd = xv - (float)hh;             // exact in fp32 (0 in the augmentation / padding columns)
-                    lo.h[e] = (_Float16)dd;
-                    dsum = fmaf(dd, dd, dsum);
-                }
-                // level 1: the residual ||q - hi(q)||^2 is a BOUND of the error band (any summation order, 1.0001 for it):
-                // summed here on all 64 lanes -- on the chain lanes its 5 operations per element were 70 % of their work
-                if (p.level == 1) dnp[rr * 8 + gq] = dsum;
-                const int kk = k0 + gq * 8, u = kk >> 4, hf = (kk >> 3) & 1;
-                const int64_t dst = p.qs_row ? (row < p.B ? (int64_t)p.qs_row[row] : -1) : row;
-                if (dst >= 0 && p.level == 1) {      // planar hi operand: 32 bytes per unit
-                    uint4 *cell = reinterpret_cast<uint4 *>(p.Qs) + (dst * p.units_p + u) * 2;
-                    cell[hf] = hi.v;
-                } else if (dst >= 0) {
-                    uint4 *cell = reinterpret_cast<uint4 *>(p.Qs) + (dst * p.units_p + u) * 4;
-                    cell[hf] = hi.v;
-                    cell[2 + hf] = lo.v;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (p.level == 1 && lane < QPW)
-                for (int gq = 0; gq < ngr; ++gq) dn += dnp[lane * 8 + gq];
-        }
-#undef KGE_QP_FETCH
-        if (lane < QPW && i < p.Bp) {
-            if (valid) {
-                const float st = lp_epilogue(KGE_LP_L2_EXPAND, acc, qn, p.en[tru]);
-                p.qn[i] = qn;
-                p.s_true[i] = st;
-                if (p.e2pref) {     // units past the data (the augmentation column alone in its unit)
-                    for (int u = (d + 15) >> 4; u < p.units; ++u) amag = amag + sqrtf(qn * p.e2pref[u]);
-                } else {
-                    amag = -1.0f;
-                }
-                if (p.level == 1) {
-                    const float inv2 = 1.0f / ((float)(1 << SPLIT_SCALE_LOG2) * (float)(1 << SPLIT_SCALE_LOG2));
-                    const float dq2 = dn * inv2 * 1.0001f;
-                    if (p.q_dn2) p.q_dn2[i] = dq2;
-                    p.thr[i] = split_thr_l2_hi(qn, st, em, d, p.units, p.c_acc, p.eps_scale, dq2, de2m);
-                } else {
-                    p.thr[i] = split_thr_l2(qn, st, em, d, p.units, p.c_acc, p.eps_scale, amag);
-                }
-                qbig = __uint_as_float(max(__float_as_uint(qbig), __float_as_uint(qn)));
-            } else {
-                p.thr[i] = make_float2(INFINITY, INFINITY);
-            }
-        }
-    }
-    if (p.qmax_io && !(p.dbg & 32)) {    // one atomic per block (same-address atomics serialise at ~12 ns each)
-        unsigned m = __float_as_uint(qbig);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if (lane == 0) wmax[wv] = m;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.qmax_io), max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
-    }
-}
-
-// ---- fused query side of one DistMult / ComplEx batch on the one-product level (r05) ------------------------------
-// What lp_prep + pair_scores + two any-order norm passes + their sum + kge_lp_hi_rows(is_query) + the threshold kernel
-// (+ two fills) do in nine launches.  The DOT modes' operands carry a power-of-two scale taken from a squared-norm
-// MAXIMUM (arbitrary magnitudes, unlike the unit-ball rows of the L2 modes) -- batch-wide in the separate kernels, which
-// is what kept this side at two sweeps over Q with a device-wide reduction between them.  Here every query row carries
-// ITS OWN scale S_i = split_scale(||q_i||^2): the count kernels never see a scale (the thresholds of query i are
-// multiplied by S_i * S_e like its accumulators), the band only gets tighter (its absolute term then holds ||q_i|| where
-// it held max ||q||), and the guard column of the padding candidates is built from ||q_i|| alone.
-// Per group of QPW queries of a wavefront: (1) ||q||^2 in any order (a bound: 16 lanes per row, the source rows read
-// once -- they are read again, from the L1 / L2, by) (2) the TransE pipeline's chunk loop: q = e (x) r written for the
-// later exact kernels and staged in LDS with the true entity's rows, the exact true score by the pair kernel's chain
-// (one lane per query; segment [Re | Im] after segment), the planar f16 hi operand and its measured residual on all lanes.
-struct DotPipeParams {
-    int tail;                       // as QueryPipeParams
-    int64_t Bh;
-    const float *E0, *E1, *R0, *R1; // entity / relation tables (ComplEx: Re, Im; DistMult: E1 = R1 = NULL)
-    int d;                          // columns per segment (K = d resp. 2 d), d % 8 == 0
-    const int64_t *h, *t, *r;
-    int64_t B, Bp;
-    const float *emax0, *emax1;     // device scalars: max ||row||^2 of the candidate table's segments
-    const float *de2max;            // device scalar >= max_c ||e_c - hi(e_c)||^2
-    float *qmax_io;                 // device scalar, max ||q||^2 folded in (may be NULL)
-    float c_acc, eps_scale;
-    int units, units_p;
-    float *Q0, *Q1, *qn, *s_true, *q_dn2;
-    float2 *thr;
-    _Float16 *Qh;
-    int32_t *list_count;
-    float *overflow;
-    int32_t *zero_i32;
-    int64_t zero_n;
-    const float *dn_bmax;           // optional [dn_blocks]: block maxima of the candidate table's residuals (kge_lp_dot_table_prep):
-    int dn_blocks;                  // folded into *de2max by every block on its way in, stored by block 0
-    const float *nm_bmax;           // optional [2][nm_blocks]: squared-norm maxima per block of kge_lp_dot_table_prep_fused -- folded
-    int nm_blocks;                  // into *emax0 / *emax1 the same way
-    float *prev_nmax;               // optional [2]: the maxima the NEXT one-pass table preparation takes its scale from (stored by
-                                    // block 0); with nm_bmax: the ones THIS table was scaled by -- another scale: *overflow = 1
-};
-
-// thresholds of one DOT query on the one-product level, operand scales s_q (its own) and s_e
-__device__ __forceinline__ float2 split_thr_dot_hi(float q, float st, float em, int K, int units, float c_acc, float eps_scale,
-                                                   float dq2, float de2m, float qm, float s_q, float s_e)
-{
-    const float two22 = 2.3841858e-7f;
-    const float enrm = sqrtf(em) * 1.000001f, qnrm = sqrtf(q) * 1.000001f;
-    const float out_scale = s_q * s_e;
-    const float sqk = sqrtf((float)K);
-    const float eps_abs = 1.4901161e-8f * sqk * (sqrtf(qm) * enrm + sqrtf(em) * qnrm) + 1e-30f;
-    const float eps_dot = (split_acc_err(-1.0f, 0.f, qnrm * enrm, units, c_acc, 16.0f) + split_chain_err(-1.0f, qnrm * enrm, K) +
-                           split_hi_resid(qnrm, enrm, 0.f, dq2, de2m) + eps_abs) * eps_scale;
-    const float hw = eps_dot + two22 * fabsf(st);
-    return make_float2(split_nonzero_lo((st - hw) * out_scale), (st + hw) * out_scale);
-}
-
-template <int QPW, bool CPLX>
-__global__ __launch_bounds__(256) void dot_query_pipeline_kernel(const DotPipeParams p)
-{
-    constexpr int KC = 48, LD = 52;
-    __shared__ __attribute__((aligned(16))) float qs_all[4 * QPW * LD];
-    __shared__ __attribute__((aligned(16))) float ts_all[4 * QPW * LD];
-    __shared__ float dnp_all[4 * QPW * 8];
-    __shared__ float qn_all[4 * QPW], sc_all[4 * QPW];
-    __shared__ unsigned wmax[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float *qs = qs_all + wv * QPW * LD, *ts = ts_all + wv * QPW * LD, *dnp = dnp_all + wv * QPW * 8;
-    float *qn_s = qn_all + wv * QPW, *sc_s = sc_all + wv * QPW;
-    const int d = p.d, nseg = CPLX ? 2 : 1, K = nseg * d, kpad = p.units_p * 16;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *p.list_count = 0;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.zero_n; j += (int64_t)gridDim.x * 256) p.zero_i32[j] = 0;
-    float em;
-    if (p.nm_bmax) {        // (as query_pipeline_kernel: block maxima -> the scalars, folded into what they hold)
-        __shared__ unsigned nred[8];
-        unsigned m0 = 0u, m1 = 0u;
-        for (int j = threadIdx.x; j < p.nm_blocks; j += 256) {
-            m0 = max(m0, __float_as_uint(p.nm_bmax[j]));
-            m1 = max(m1, __float_as_uint(p.nm_bmax[p.nm_blocks + j]));
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if (lane == 0) { nred[wv] = m0; nred[4 + wv] = m1; }
-        __syncthreads();
-        m0 = max(max(nred[0], nred[1]), max(nred[2], nred[3]));
-        m1 = max(max(nred[4], nred[5]), max(nred[6], nred[7]));
-        const float n0 = __uint_as_float(max(m0, __float_as_uint(*p.emax0)));
-        const float n1 = p.emax1 ? __uint_as_float(max(m1, __float_as_uint(*p.emax1))) : 0.f;
-        em = n0 + n1;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            *const_cast<float *>(p.emax0) = n0;
-            if (p.emax1) *const_cast<float *>(p.emax1) = n1;
-            if (p.prev_nmax) {
-                // the table was converted under split_scale(prev): thresholds and table agree only under the same scale
-                // (2: not the list -- the caller runs the same path again, now under the maxima stored below)
-                if (split_scale(p.prev_nmax[0] + p.prev_nmax[1]) != split_scale(em)) *p.overflow = 2.0f;
-                p.prev_nmax[0] = n0; p.prev_nmax[1] = n1;
-            }
-        }
-    } else {
-        em = *p.emax0 + (p.emax1 ? *p.emax1 : 0.f);
-        if (p.prev_nmax && blockIdx.x == 0 && threadIdx.x == 0) {
-            p.prev_nmax[0] = *p.emax0;
-            p.prev_nmax[1] = p.emax1 ? *p.emax1 : 0.f;
-        }
-    }
-    float de2m;
-    if (p.dn_bmax) {
-        __shared__ unsigned red[4];
-        unsigned m = 0u;
-        for (int j = threadIdx.x; j < p.dn_blocks; j += 256) m = max(m, __float_as_uint(p.dn_bmax[j]));
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if (lane == 0) red[wv] = m;
-        __syncthreads();
-        m = max(max(red[0], red[1]), max(red[2], red[3]));
-        de2m = __uint_as_float(max(m, __float_as_uint(*p.de2max)));
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0) *const_cast<float *>(p.de2max) = de2m;
-    } else {
-        de2m = *p.de2max;
-    }
-    const float s_e = split_scale(em);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && !(em < INFINITY)) *p.overflow = 1.0f;
-    float qbig = 0.f;
-    const int nch_seg = (d + KC - 1) / KC, nch = nseg * nch_seg;
-    const int64_t ngroups = (p.Bp + QPW - 1) / QPW;
-    for (int64_t grp = (int64_t)blockIdx.x * 4 + wv; grp < ngroups; grp += (int64_t)gridDim.x * 4) {
-        const int64_t i = grp * QPW + lane;
-        const bool valid = lane < QPW && i < p.B;
-        const int64_t ic = valid ? i : 0;
-        const bool tl = p.tail == 2 ? ic < p.Bh : p.tail == 1;
-        const int64_t fi = (p.tail == 2 && ic >= p.Bh) ? ic - p.Bh : ic;
-        const int64_t src = tl ? p.h[fi] : p.t[fi], tru = tl ? p.t[fi] : p.h[fi], ri = p.r[fi];
-        const int tli = tl ? 1 : 0;
-        // ---- (1) ||q||^2, any order: 16 lanes per row, four rows of the group at a time
-        {
-            const int sub = lane & 15;
-#pragma unroll 1
-            for (int rb = 0; rb < QPW; rb += 4) {
-                const int rr = rb + (lane >> 4);
-                const int64_t s_ = __shfl(src, rr, 64), r_ = __shfl(ri, rr, 64);
-                const bool tl_ = __shfl(tli, rr, 64) != 0;
-                float ss = 0.f;
-                for (int k = sub * 4; k < d; k += 64) {
-                    if (CPLX) {
-                        const float4 re = *reinterpret_cast<const float4 *>(p.E0 + s_ * d + k);
-                        const float4 im = *reinterpret_cast<const float4 *>(p.E1 + s_ * d + k);
-                        const float4 rr4 = *reinterpret_cast<const float4 *>(p.R0 + r_ * d + k);
-                        const float4 ir4 = *reinterpret_cast<const float4 *>(p.R1 + r_ * d + k);
-#define KGE_DP_SS(C)                                                                                         \
-    {                                                                                                        \
-        const float q0_ = tl_ ? re.C * rr4.C - im.C * ir4.C : rr4.C * re.C + ir4.C * im.C;                   \
-        const float q1_ = tl_ ? re.C * ir4.C + im.C * rr4.C : rr4.C * im.C - ir4.C * re.C;                   \
-        ss = fmaf(q0_, q0_, ss);                                                                             \
-        ss = fmaf(q1_, q1_, ss);                                                                             \
-    }
-                        KGE_DP_SS(x) KGE_DP_SS(y) KGE_DP_SS(z) KGE_DP_SS(w)
-#undef KGE_DP_SS
-                    } else {
-                        const float4 e4 = *reinterpret_cast<const float4 *>(p.E0 + s_ * d + k);
-                        const float4 r4 = *reinterpret_cast<const float4 *>(p.R0 + r_ * d + k);
-                        const float q0 = e4.x * r4.x, q1 = e4.y * r4.y, q2 = e4.z * r4.z, q3 = e4.w * r4.w;
-                        ss = fmaf(q0, q0, ss); ss = fmaf(q1, q1, ss); ss = fmaf(q2, q2, ss); ss = fmaf(q3, q3, ss);
-                    }
-                }
-                ss += __shfl_xor(ss, 8, 64); ss += __shfl_xor(ss, 4, 64); ss += __shfl_xor(ss, 2, 64); ss += __shfl_xor(ss, 1, 64);
-                if (sub == 0) qn_s[rr] = ss;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        const float qn = lane < QPW ? qn_s[lane] : 0.f;
-        const float s_q = split_scale(qn);
-        if (lane < QPW) sc_s[lane] = s_q;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        // ---- (2) the chunk loop
-        float acc = 0.f, dn = 0.f;
-        constexpr int NP = KC / 4, ITS = (QPW * NP + 63) / 64;
-        float4 pa[ITS], pb[ITS], pc_[ITS], pd[ITS], pt[ITS];
-#define KGE_DP_FETCH(C)                                                                                      \
-    {                                                                                                        \
-        const int sg_ = (C) / nch_seg, kk0_ = ((C) - sg_ * nch_seg) * KC;                                    \
-        const int pcs_ = max(0, min(KC, d - kk0_)) >> 2;                                                     \
-        const float *tt_ = (CPLX && sg_ != 0) ? p.E1 : p.E0;                                                 \
-        _Pragma("unroll") for (int it = 0; it < ITS; ++it) {                                                 \
-            const int idx = it * 64 + lane;                                                                  \
-            const bool act = idx < QPW * pcs_;                                                               \
-            const int rr = act ? idx / pcs_ : 0, pc = act ? idx - rr * pcs_ : 0;                             \
-            const int64_t s_ = __shfl(src, rr, 64), r_ = __shfl(ri, rr, 64), t_ = __shfl(tru, rr, 64);       \
-            if (act) {                                                                                       \
-                const int64_t ko_ = kk0_ + pc * 4;                                                           \
-                pa[it] = *reinterpret_cast<const float4 *>(p.E0 + s_ * d + ko_);                             \
-                pc_[it] = *reinterpret_cast<const float4 *>(p.R0 + r_ * d + ko_);                            \
-                if (CPLX) {                                                                                  \
-                    pb[it] = *reinterpret_cast<const float4 *>(p.E1 + s_ * d + ko_);                         \
-                    pd[it] = *reinterpret_cast<const float4 *>(p.R1 + r_ * d + ko_);                         \
-                }                                                                                            \
-                pt[it] = *reinterpret_cast<const float4 *>(tt_ + t_ * d + ko_);                              \
-            }                                                                                                \
-        }                                                                                                    \
-    }
-        KGE_DP_FETCH(0)
-#pragma unroll 1
-        for (int c = 0; c < nch; ++c) {
-            const int sg = c / nch_seg, k0 = (c - sg * nch_seg) * KC;
-            const int kc = min(KC, d - k0), pieces = kc >> 2;
-            float *Qg = sg == 0 ? p.Q0 : p.Q1;
-#pragma unroll
-            for (int it = 0; it < ITS; ++it) {
-                const int idx = it * 64 + lane;
-                const bool act = idx < QPW * pieces;
-                const int rr = act ? idx / pieces : 0, pc = act ? idx - rr * pieces : 0;
-                const bool tl_ = __shfl(tli, rr, 64) != 0;
-                if (!act) continue;
-                const float4 t4 = pt[it];
-                float4 q4;
-                if (CPLX) {      // lp_prep_kernel, bilinear.py:514-515 (tail) / :521-522 (head): the same operations
-                    const float4 re = pa[it], im = pb[it], rr4 = pc_[it], ir4 = pd[it];
-                    if (sg == 0) {
-                        q4.x = tl_ ? re.x * rr4.x - im.x * ir4.x : rr4.x * re.x + ir4.x * im.x;
-                        q4.y = tl_ ? re.y * rr4.y - im.y * ir4.y : rr4.y * re.y + ir4.y * im.y;
-                        q4.z = tl_ ? re.z * rr4.z - im.z * ir4.z : rr4.z * re.z + ir4.z * im.z;
-                        q4.w = tl_ ? re.w * rr4.w - im.w * ir4.w : rr4.w * re.w + ir4.w * im.w;
-                    } else {
-                        q4.x = tl_ ? re.x * ir4.x + im.x * rr4.x : rr4.x * im.x - ir4.x * re.x;
-                        q4.y = tl_ ? re.y * ir4.y + im.y * rr4.y : rr4.y * im.y - ir4.y * re.y;
-                        q4.z = tl_ ? re.z * ir4.z + im.z * rr4.z : rr4.z * im.z - ir4.z * re.z;
-                        q4.w = tl_ ? re.w * ir4.w + im.w * rr4.w : rr4.w * im.w - ir4.w * re.w;
-                    }
-                } else {         // bilinear.py:247-267
-                    const float4 e4 = pa[it], r4 = pc_[it];
-                    q4.x = e4.x * r4.x; q4.y = e4.y * r4.y; q4.z = e4.z * r4.z; q4.w = e4.w * r4.w;
-                }
-                const int64_t row = grp * QPW + rr;
-                if (row < p.B) *reinterpret_cast<float4 *>(Qg + row * d + k0 + pc * 4) = q4;
-                else q4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4 *>(qs + rr * LD + pc * 4) = q4;
-                *reinterpret_cast<float4 *>(ts + rr * LD + pc * 4) = t4;
-            }
-            if (c + 1 < nch) KGE_DP_FETCH(c + 1)
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (lane < QPW) {       // the exact true score: the pair kernel's chain (lp_chain_dot), continued over the segments
-                const float *x = qs + lane * LD, *tt = ts + lane * LD;
-                int k = 0;
-                for (; k + 16 <= kc; k += 16) {
-                    float xv[16], tv[16];
-#pragma unroll
-                    for (int j4 = 0; j4 < 4; ++j4) {
-                        const float4 v = *reinterpret_cast<const float4 *>(x + k + 4 * j4);
-                        const float4 w = *reinterpret_cast<const float4 *>(tt + k + 4 * j4);
-                        xv[4 * j4] = v.x; xv[4 * j4 + 1] = v.y; xv[4 * j4 + 2] = v.z; xv[4 * j4 + 3] = v.w;
-                        tv[4 * j4] = w.x; tv[4 * j4 + 1] = w.y; tv[4 * j4 + 2] = w.z; tv[4 * j4 + 3] = w.w;
-                    }
-#pragma unroll
-                    for (int b8 = 0; b8 < 16; b8 += 8) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            acc = fmaf(xv[b8 + j], tv[b8 + j], acc);
-                            acc = fmaf(xv[b8 + 4 + j], tv[b8 + 4 + j], acc);
-                        }
-                    }
-                }
-                if (k < kc) acc = lp_chain_dot(x + k, tt + k, kc - k, acc);     // (kc % 8 == 0: one more 8-block)
-            }
-            // the chunk's hi cells: 8 consecutive k of one row per lane and pass, the row's own scale
-            const int ngr = kc >> 3;
-            for (int idx = lane; idx < QPW * ngr; idx += 64) {
-                const int rr = idx / ngr, gq = idx - rr * ngr;
-                const int64_t row = grp * QPW + rr;
-                const float sc = sc_s[rr];
-                const float4 v0 = *reinterpret_cast<const float4 *>(qs + rr * LD + gq * 8);
-                const float4 v1 = *reinterpret_cast<const float4 *>(qs + rr * LD + gq * 8 + 4);
-                union { _Float16 h[8]; uint4 v; } hi;
-                float dsum = 0.f;
-#define KGE_DP_CV(E, X)                                                                                      \
-    {                                                                                                        \
-        const float xsj = (X) * sc;                                                                          \
-        const _Float16 hh = (_Float16)xsj;                                                                   \
-        const float dd = xsj - (float)hh;                                                                    \
-        dsum = fmaf(dd, dd, dsum);                                                                           \
-        hi.h[E] = hh;                                                                                        \
-    }
-                KGE_DP_CV(0, v0.x) KGE_DP_CV(1, v0.y) KGE_DP_CV(2, v0.z) KGE_DP_CV(3, v0.w)
-                KGE_DP_CV(4, v1.x) KGE_DP_CV(5, v1.y) KGE_DP_CV(6, v1.z) KGE_DP_CV(7, v1.w)
-#undef KGE_DP_CV
-                dnp[rr * 8 + gq] = dsum;
-                const int kk = sg * d + k0 + gq * 8, u = kk >> 4, hf = (kk >> 3) & 1;
-                if (row < p.Bp) reinterpret_cast<uint4 *>(p.Qh)[(row * p.units_p + u) * 2 + hf] = hi.v;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (lane < QPW)
-                for (int gq = 0; gq < ngr; ++gq) dn += dnp[lane * 8 + gq];
-        }
-#undef KGE_DP_FETCH
-        // the cells behind the data: the guard column at K (see hi_rows_kernel, aug_mode 3 -- with this row's own norm), zeros
-        const int ntail = (kpad - K) >> 3;
-        for (int idx = lane; idx < QPW * ntail; idx += 64) {
-            const int rr = idx / ntail, g = idx - rr * ntail;
-            const int64_t row = grp * QPW + rr;
-            union { _Float16 h[8]; uint4 v; } hi;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) hi.h[e] = (_Float16)0.f;
-            if (g == 0 && row < p.B) {
-                const float qr = sqrtf(qn_s[rr]);
-                hi.h[0] = (_Float16)fmaxf(0.25f * (qr + qr * 0.00390625f) * sc_s[rr], 1.0f);
-            }
-            const int kk = K + g * 8, u = kk >> 4, hf = (kk >> 3) & 1;
-            if (row < p.Bp) reinterpret_cast<uint4 *>(p.Qh)[(row * p.units_p + u) * 2 + hf] = hi.v;
-        }
-        if (lane < QPW && i < p.Bp) {
-            if (valid) {
-                p.qn[i] = qn;
-                p.s_true[i] = acc;
-                const float dq2 = dn * (1.0f / (s_q * s_q)) * 1.0001f;
-                if (p.q_dn2) p.q_dn2[i] = dq2;
-                p.thr[i] = split_thr_dot_hi(qn, acc, em, K, p.units, p.c_acc, p.eps_scale, dq2, de2m, qn, s_q, s_e);
-                if (!(qn < INFINITY)) *p.overflow = 1.0f;
-                qbig = __uint_as_float(max(__float_as_uint(qbig), __float_as_uint(qn)));
-            } else {
-                p.thr[i] = make_float2(INFINITY, INFINITY);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // (qn_s / sc_s are rewritten by the next group)
-    }
-    if (p.qmax_io) {
-        unsigned m = __float_as_uint(qbig);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if (lane == 0) wmax[wv] = m;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.qmax_io), max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
     }
 }
 
@@ -2204,187 +863,6 @@ __global__ __launch_bounds__(64 * NWAVES, 1) void lp_split_count_kernel(const Sp
     flush_counts(cur_q0);
 }
 
-// Exact re-scoring of the listed pairs: one lane per pair, rows staged cooperatively
-// (kge_common.h: lp_pair_score_staged).
-template <bool VEC4>
-__global__ __launch_bounds__(64, 2) void split_recheck_kernel(const kge_lp_desc d, const float *__restrict__ s_true,
-                                                           const int32_t *__restrict__ list, int32_t cap,
-                                                           const int32_t *__restrict__ list_count, int32_t *raw_count,
-                                                           float *list_stat)
-{
-    __shared__ __attribute__((aligned(16))) float qs[64 * KGE_PS_LD];
-    __shared__ __attribute__((aligned(16))) float es[64 * KGE_PS_LD];
-    const int lane = threadIdx.x;
-    const int n = (int)min((unsigned)*list_count, (unsigned)cap);   // (a count past the capacity means overflow: the caller redoes the count)
-    if (list_stat && blockIdx.x == 0 && lane == 0) atomicAdd(list_stat, (float)n);   // pairs re-scored per evaluation (level policy)
-    const int ngroups = (n + 63) >> 6;
-    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const int pi = grp * 64 + lane;
-        const bool valid = pi < n;
-        const int pj = valid ? pi : grp * 64;       // idle lanes shadow the group's first pair
-        const int qi = list[2 * pj], ci = list[2 * pj + 1];
-        const float sc = lp_pair_score_staged<VEC4>(d, qi, ci, qs, es);
-        if (valid && !(sc >= s_true[qi])) atomicSub(&raw_count[qi], 1);
-    }
-}
-
-// ---- exact re-scoring REGION BY REGION (r05) -------------------------------------------------------------------------
-// The free-running sweep can leave its uncertain pairs in regions of the list, one per (query panel, 32-query sub-tile)
-// (kge_split_args.region_count).  A block takes a region: the sub-tile's 32 query rows go to LDS ONCE (fp32, row stride an
-// odd number of 16-byte pieces: conflict-free b128 reads at per-lane rows), then every pair costs the candidate row
-// alone -- staged cooperatively like lp_staged_segment's -- instead of both rows: the recheck is bound by the L2's row
-// bandwidth (8.8 TB/s of 1.6 KB per pair at cfg2), so half the bytes is most of half the time.  Same chains (lp_chain_dot
-// on 32-column chunks, segment after segment), same epilogue: same bits as lp_pair_score.  Rows must be float4-readable
-// (kge_lp_vec4).
-__device__ __forceinline__ float recheck_e_segment(const float *__restrict__ T, int64_t ldt, int K, int ci,
-                                                   const float *__restrict__ qrow, float *es, float acc)
-{
-    const int lane = threadIdx.x & 63;
-    // (ONE 32-column chunk in flight per wavefront, as lp_staged_segment: with two -- 175 VGPRs -- the kernel took 83 us
-    // instead of 68, profiles/r05/region_recheck_ab.txt)
-    int k0 = 0;
-    if (K >= KGE_PS_KC) {
-        float4 e0, e1, e2, e3, e4, e5, e6, e7;
-#define KGE_RR_FETCH(IT, KK)                                                                                  \
-    {                                                                                                         \
-        const int idx_ = lane + 64 * IT, rr_ = idx_ >> 3, pc_ = idx_ & 7;                                     \
-        const int rc_ = __shfl(ci, rr_, 64);                                                                  \
-        e##IT = *reinterpret_cast<const float4 *>(T + (int64_t)rc_ * ldt + (KK) + pc_ * 4);                   \
-    }
-#define KGE_RR_STORE(IT)                                                                                      \
-    {                                                                                                         \
-        const int idx_ = lane + 64 * IT, rr_ = idx_ >> 3, pc_ = idx_ & 7;                                     \
-        *reinterpret_cast<float4 *>(es + rr_ * KGE_PS_LD + pc_ * 4) = e##IT;                                  \
-    }
-#define KGE_RR_ALL(M, ...) M(0, ##__VA_ARGS__) M(1, ##__VA_ARGS__) M(2, ##__VA_ARGS__) M(3, ##__VA_ARGS__) \
-                           M(4, ##__VA_ARGS__) M(5, ##__VA_ARGS__) M(6, ##__VA_ARGS__) M(7, ##__VA_ARGS__)
-        KGE_RR_ALL(KGE_RR_FETCH, 0)
-        for (; k0 + KGE_PS_KC <= K; k0 += KGE_PS_KC) {
-            KGE_RR_ALL(KGE_RR_STORE)
-            if (k0 + 2 * KGE_PS_KC <= K) { KGE_RR_ALL(KGE_RR_FETCH, k0 + KGE_PS_KC) }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            acc = lp_chain_dot(qrow + k0, es + lane * KGE_PS_LD, KGE_PS_KC, acc);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        }
-#undef KGE_RR_ALL
-#undef KGE_RR_STORE
-#undef KGE_RR_FETCH
-    }
-    for (; k0 < K; k0 += KGE_PS_KC) {      // the last, partial chunk (K % 4 == 0)
-        const int kc = min(KGE_PS_KC, K - k0);
-        const int pieces = kc >> 2;
-        for (int idx = lane; idx < 64 * pieces; idx += 64) {
-            const int rr = idx / pieces, pc = idx - rr * pieces;
-            const int rc = __shfl(ci, rr, 64);
-            *reinterpret_cast<float4 *>(es + rr * KGE_PS_LD + pc * 4) =
-                *reinterpret_cast<const float4 *>(T + (int64_t)rc * ldt + k0 + pc * 4);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        acc = lp_chain_dot(qrow + k0, es + lane * KGE_PS_LD, kc, acc);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    return acc;
-}
-
-constexpr int RR_ROWS = 32, RR_PANEL = 96;      // queries per region / per panel of the free-running sweep (lp_hi_stream.hip)
-
-// Rows longer than one LDS segment (r06; K > 256 or so -- DistMult / ComplEx d = 400: the recheck was 20 % of cfg4's step, all
-// of it row fetches): the region's query rows pass through LDS in SEGMENTS of seg_cols logical columns of [A0 | A1] while the
-// chains of up to RR_G pair groups per wave (a batch of NWV * 64 * RR_G pairs: a whole region, typically) rest in registers
-// between segments -- the sequential chain is cut, not reordered: same bits.  One segment (K <= seg_cols) is r05's form.
-constexpr int RR_G = 4;
-
-template <int NWV>
-__global__ __launch_bounds__(64 * NWV) void split_recheck_regions_kernel(const kge_lp_desc d, const float *__restrict__ s_true,
-                                                                        const int32_t *__restrict__ list, int32_t region_cap,
-                                                                        const int32_t *__restrict__ region_count, int n_regions,
-                                                                        int ldq, int seg_cols, int32_t *raw_count, float *list_stat,
-                                                                        int32_t *list_count)
-{
-    extern __shared__ __attribute__((aligned(16))) float rr_smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    float *qrows = rr_smem;
-    float *es = rr_smem + RR_ROWS * ldq + wv * 64 * KGE_PS_LD;
-    const int K = d.K0 + d.K1;
-    int n_block = 0;
-    // logical columns [c0, c1) of the region's 32 query rows -> LDS (row stride ldq)
-    auto stage = [&](int64_t q0, int c0, int c1) {
-        const int np = (c1 - c0) >> 2;
-        for (int idx = tid; idx < RR_ROWS * np; idx += 64 * NWV) {
-            const int rr = idx / np, pc = idx - rr * np;
-            const int64_t q = min(q0 + rr, d.B - 1);
-            const int col = c0 + pc * 4;        // (K0 % 4 == 0: a piece lies in one segment of the operand)
-            const float4 v = col < d.K0 ? *reinterpret_cast<const float4 *>(d.A0 + q * d.lda0 + col)
-                                        : *reinterpret_cast<const float4 *>(d.A1 + q * d.lda1 + (col - d.K0));
-            *reinterpret_cast<float4 *>(qrows + rr * ldq + pc * 4) = v;
-        }
-    };
-    // the chain of one pair over the staged columns [c0, c1): operand segment 0, then 1
-    auto chain = [&](float acc, int ci, const float *qrow, int c0, int c1) -> float {
-        if (c0 < d.K0) acc = recheck_e_segment(d.T0 + c0, d.ldt0, min(c1, d.K0) - c0, ci, qrow, es, acc);
-        if (c1 > d.K0 && d.K1 > 0) {
-            const int s0 = max(c0, d.K0);
-            acc = recheck_e_segment(d.T1 + (s0 - d.K0), d.ldt1, c1 - s0, ci, qrow + (s0 - c0), es, acc);
-        }
-        return acc;
-    };
-    for (int reg = blockIdx.x; reg < n_regions; reg += gridDim.x) {
-        const int n = (int)min((unsigned)region_count[reg], (unsigned)region_cap);   // (past the capacity: overflow flagged by the sweep)
-        if (n == 0) continue;                   // (block-uniform)
-        n_block += n;
-        const int64_t q0 = (int64_t)(reg / 3) * RR_PANEL + (reg % 3) * RR_ROWS;
-        const int2 *ent = reinterpret_cast<const int2 *>(list) + (int64_t)reg * region_cap;
-        if (K <= seg_cols) {
-            __syncthreads();                    // the previous region's readers are done
-            stage(q0, 0, K);
-            __syncthreads();
-            for (int c0 = wv * 64; c0 < n; c0 += NWV * 64) {
-                const int pi = c0 + lane;
-                const bool valid = pi < n;
-                const int2 e = ent[valid ? pi : c0];       // idle lanes shadow the group's first pair
-                const int qi = e.x, ci = e.y;
-                const float acc = chain(0.0f, ci, qrows + (int)(qi - q0) * ldq, 0, K);
-                const float sc = lp_epilogue_any(d, acc, qi, ci);
-                if (valid && !(sc >= s_true[qi])) atomicSub(&raw_count[qi], 1);
-            }
-            continue;
-        }
-        for (int b0 = 0; b0 < n; b0 += NWV * 64 * RR_G) {       // (block-uniform trip counts: barriers inside)
-            float acc[RR_G];
-            int qi[RR_G], ci[RR_G];
-#pragma unroll
-            for (int g = 0; g < RR_G; ++g) {
-                const int c0 = b0 + (g * NWV + wv) * 64;
-                const int pi = c0 + lane;
-                const int2 e = ent[min(pi < n ? pi : c0, n - 1)];   // idle lanes shadow the group's first pair (idle groups: the last pair)
-                qi[g] = e.x; ci[g] = e.y; acc[g] = 0.0f;
-            }
-            for (int c0 = 0; c0 < K; c0 += seg_cols) {
-                const int c1 = min(K, c0 + seg_cols);
-                __syncthreads();                // the previous segment's / region's readers are done
-                stage(q0, c0, c1);
-                __syncthreads();
-#pragma unroll
-                for (int g = 0; g < RR_G; ++g)
-                    if (b0 + (g * NWV + wv) * 64 < n)       // (wave-uniform)
-                        acc[g] = chain(acc[g], ci[g], qrows + (int)(qi[g] - q0) * ldq, c0, c1);
-            }
-#pragma unroll
-            for (int g = 0; g < RR_G; ++g) {
-                const int pi = b0 + (g * NWV + wv) * 64 + lane;
-                if (pi < n) {
-                    const float sc = lp_epilogue_any(d, acc[g], qi[g], ci[g]);
-                    if (!(sc >= s_true[qi[g]])) atomicSub(&raw_count[qi[g]], 1);
-                }
-            }
-        }
-    }
-    if (tid == 0 && n_block > 0) {              // pairs re-scored per evaluation (level policy) / the list's length
-        if (list_stat) atomicAdd(list_stat, (float)n_block);
-        if (list_count) atomicAdd(list_count, n_block);
-    }
-}
-
 template <int NWAVES, bool DBG, int PM, int GS = 0, int LV = 0>
 int launch_split(const SplitParams &p, int grid, hipStream_t s)
 {
@@ -2396,209 +874,29 @@ int launch_split(const SplitParams &p, int grid, hipStream_t s)
     return 0;
 }
 
-int split_num_cus()
+// The 14 instantiations: level x threshold form (pm: 0 plain, 1 TransH, 2 TransD) x plain / grouped columns (gs: 0 or
+// GSETS), and the probe kernel (dbg) of the plain per-query sweep at both levels.
+int launch_split_for(int pm, int gs, bool lv1, bool dbg, const SplitParams &p, int grid, hipStream_t s)
 {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
+    if (dbg && pm == 0 && gs == 0) return lv1 ? launch_split<8, true, 0, 0, 1>(p, grid, s) : launch_split<8, true, 0, 0, 0>(p, grid, s);
+    switch (pm + (gs ? 3 : 0) + (lv1 ? 6 : 0)) {
+    case 0: return launch_split<8, false, 0, 0, 0>(p, grid, s);
+    case 1: return launch_split<8, false, 1, 0, 0>(p, grid, s);
+    case 2: return launch_split<8, false, 2, 0, 0>(p, grid, s);
+    case 3: return launch_split<8, false, 0, GSETS, 0>(p, grid, s);
+    case 4: return launch_split<8, false, 1, GSETS, 0>(p, grid, s);
+    case 5: return launch_split<8, false, 2, GSETS, 0>(p, grid, s);
+    case 6: return launch_split<8, false, 0, 0, 1>(p, grid, s);
+    case 7: return launch_split<8, false, 1, 0, 1>(p, grid, s);
+    case 8: return launch_split<8, false, 2, 0, 1>(p, grid, s);
+    case 9: return launch_split<8, false, 0, GSETS, 1>(p, grid, s);
+    case 10: return launch_split<8, false, 1, GSETS, 1>(p, grid, s);
+    case 11: return launch_split<8, false, 2, GSETS, 1>(p, grid, s);
     }
-    return n;
+    return KGE_EINVAL;
 }
-
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 } // namespace
-
-extern "C" int kge_lp_split_units(int K, int with_aug)
-{
-    return (int)round_up((K + (with_aug ? 1 : 0) + 15) / 16, 2);
-}
-
-extern "C" int64_t kge_lp_split_rows_padded(int64_t rows, int is_query) { return round_up(rows, is_query ? TQ : TC); }
-
-extern "C" int kge_lp_split_rows(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1,
-                                 int64_t rows, int is_query, int aug_mode, const float *aug, float aug_mul,
-                                 const float *norm2max0, const float *norm2max1, void *out, float *cell_ss,
-                                 const int64_t *row_index, kge_stream_t stream)
-{
-    if (rows < 0 || K0 <= 0 || K1 < 0 || ld0 < K0 || (K1 > 0 && ld1 < K1) || aug_mode < 0 || aug_mode > 4)
-        return KGE_EINVAL;
-    if (rows == 0 && is_query) return 0;
-    if ((rows > 0 && !X0) || (rows > 0 && K1 > 0 && !X1) || !out || ((aug_mode == 1 || aug_mode == 3) && rows > 0 && !aug))
-        return KGE_EINVAL;
-    SplitRowsParams p;
-    p.X0 = X0; p.X1 = X1; p.ld0 = ld0; p.ld1 = ld1; p.K0 = K0; p.K1 = K1;
-    p.rows = rows;
-    p.rows_p = kge_lp_split_rows_padded(rows, is_query);
-    p.aug_mode = aug_mode; p.aug = aug; p.aug_mul = aug_mul;
-    p.nmax0 = norm2max0; p.nmax1 = norm2max1;
-    p.units_p = kge_lp_split_units(K0 + K1, aug_mode != 0);
-    p.out = reinterpret_cast<uint4 *>(out);
-    p.cell_ss = cell_ss;
-    p.row_index = row_index;
-    const int64_t total = (p.rows_p / 16) * ((p.units_p + 15) / 16);     // tiles of 16 rows x 16 cells
-    if (total == 0) return 0;
-    const int grid = (int)(total < 65536 ? total : 65536);
-    hipLaunchKernelGGL(split_rows_kernel, dim3(grid), dim3(256), 0, kge_s(stream), p);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-/* units of a PLANAR hi operand (one-product level): k16 units of K + 2 columns, rounded up to 4 (one 128-byte stage) */
-extern "C" int kge_lp_hi_units(int K) { return (int)round_up((K + 2 + 15) / 16, 4); }
-
-static int hi_rows_impl(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1, int64_t rows,
-                        int is_query, int aug_mode, const float *aug, float aug_mul, const float *norm2max0,
-                        const float *norm2max1, void *out, float *dn2, float *dn2max, const int64_t *row_index,
-                        int frag, kge_stream_t stream)
-{
-    if (rows < 0 || K0 <= 0 || K1 < 0 || ld0 < K0 || (K1 > 0 && ld1 < K1) || aug_mode < 1 || aug_mode > 4) return KGE_EINVAL;
-    if (rows == 0 && is_query) return 0;
-    if ((rows > 0 && !X0) || (rows > 0 && K1 > 0 && !X1) || !out || ((aug_mode == 1 || aug_mode == 3) && rows > 0 && !aug))
-        return KGE_EINVAL;
-    HiRowsParams p;
-    p.X0 = X0; p.X1 = X1; p.ld0 = ld0; p.ld1 = ld1; p.K0 = K0; p.K1 = K1;
-    p.rows = rows;
-    p.rows_p = kge_lp_split_rows_padded(rows, is_query);
-    p.aug_mode = aug_mode; p.aug = aug; p.aug_mul = aug_mul;
-    p.nmax0 = norm2max0; p.nmax1 = norm2max1;
-    p.units_p = kge_lp_hi_units(K0 + K1);
-    p.out = reinterpret_cast<uint4 *>(out);
-    p.dn2 = dn2; p.dn2max = dn2max; p.row_index = row_index;
-    p.frag = frag;
-    p.nm_bmax = nullptr; p.nm_blocks = 0; p.dn_bmax = nullptr; p.prev_nmax = nullptr; p.nm_out = nullptr;
-    const int64_t blocks = p.rows_p / 16;
-    if (blocks == 0) return 0;
-    // every block ends with ONE same-address atomic (dn2max), and those serialise at ~20-30 ns each (measured r05 on the
-    // fused table preparation: 1,824 of them cost 50 us): with a maximum to fold, two blocks per CU walk the rows
-    const int64_t cap = dn2max ? 2 * (int64_t)split_num_cus() : 65536;
-    hipLaunchKernelGGL(hi_rows_kernel, dim3((int)(blocks < cap ? blocks : cap)), dim3(256), 0, kge_s(stream), p);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int kge_lp_hi_rows(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1, int64_t rows,
-                              int is_query, int aug_mode, const float *aug, float aug_mul, const float *norm2max0,
-                              const float *norm2max1, void *out, float *dn2, float *dn2max, const int64_t *row_index,
-                              kge_stream_t stream)
-{
-    return hi_rows_impl(X0, ld0, K0, X1, ld1, K1, rows, is_query, aug_mode, aug, aug_mul, norm2max0, norm2max1, out, dn2,
-                        dn2max, row_index, 0, stream);
-}
-
-/* the CANDIDATE operand of the free-running one-product kernel: same values, fragment-major layout (kge_split_args.es_frag) */
-extern "C" int kge_lp_hi_rows_frag(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1, int64_t rows,
-                                   int aug_mode, const float *aug, float aug_mul, const float *norm2max0,
-                                   const float *norm2max1, void *out, float *dn2, float *dn2max, kge_stream_t stream)
-{
-    return hi_rows_impl(X0, ld0, K0, X1, ld1, K1, rows, 0, aug_mode, aug, aug_mul, norm2max0, norm2max1, out, dn2, dn2max,
-                        nullptr, 1, stream);
-}
-
-/* Candidate side of a DOT problem on the one-product level in TWO launches (r05): the squared-norm maxima of the table's one
- * or two segments in one sweep (block maxima, no atomics, no zero-fill), then the hi table (planar or fragment-major), whose
- * blocks fold those maxima into *norm2max0_io / *norm2max1_io (block 0 stores the scalars) and leave their residual maxima
- * per block in dn_block_max[kge_lp_dot_table_prep_blocks(rows, 1)] for kge_lp_dot_query_pipeline to fold into *de2max.
- * ws: 2 * kge_lp_dot_table_prep_blocks(rows, 0) floats of scratch. */
-extern "C" int kge_lp_dot_table_prep_blocks(int64_t rows, int which)
-{
-    if (which == 0) { const int64_t b = (rows + 63) / 64; return (int)(b < 2048 ? (b > 0 ? b : 1) : 2048); }
-    const int64_t b = kge_lp_split_rows_padded(rows, 0) / 16;
-    return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
-
-extern "C" int kge_lp_dot_table_prep(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1, int64_t rows,
-                                     int frag, float *norm2max0_io, float *norm2max1_io, void *out, float *dn_block_max,
-                                     float *ws, kge_stream_t stream)
-{
-    if (rows <= 0 || K0 <= 0 || K1 < 0 || ld0 < K0 || (K1 > 0 && ld1 < K1)) return KGE_EINVAL;
-    if (!X0 || (K1 > 0 && (!X1 || !norm2max1_io)) || !norm2max0_io || !out || !dn_block_max || !ws) return KGE_EINVAL;
-    const int nb = kge_lp_dot_table_prep_blocks(rows, 0);
-    hipLaunchKernelGGL(dot_table_norm_max_kernel, dim3(nb), dim3(256), 0, kge_s(stream), X0, ld0, K0,
-                       K1 > 0 ? X1 : nullptr, ld1, K1, rows, ws);
-    KGE_CHECK_LAUNCH();
-    HiRowsParams p;
-    p.X0 = X0; p.X1 = K1 > 0 ? X1 : nullptr; p.ld0 = ld0; p.ld1 = ld1; p.K0 = K0; p.K1 = K1;
-    p.rows = rows;
-    p.rows_p = kge_lp_split_rows_padded(rows, 0);
-    p.aug_mode = 4; p.aug = nullptr; p.aug_mul = 0.f;
-    p.nmax0 = norm2max0_io; p.nmax1 = K1 > 0 ? norm2max1_io : nullptr;
-    p.units_p = kge_lp_hi_units(K0 + K1);
-    p.out = reinterpret_cast<uint4 *>(out);
-    p.dn2 = nullptr; p.dn2max = nullptr; p.row_index = nullptr;
-    p.frag = frag ? 1 : 0;
-    p.nm_bmax = ws; p.nm_blocks = nb; p.dn_bmax = dn_block_max; p.prev_nmax = nullptr; p.nm_out = nullptr;
-    // fragment-major tables of float4-readable rows: the coalesced kernel; unaligned or planar ones: the general one
-    const bool vec = K0 % 4 == 0 && K1 % 4 == 0 && ld0 % 4 == 0 && ((size_t)X0 & 15) == 0 &&
-                     (K1 == 0 || (ld1 % 4 == 0 && ((size_t)X1 & 15) == 0));
-    if (frag && vec)
-        hipLaunchKernelGGL(hi_rows_frag_kernel<false>, dim3(kge_lp_dot_table_prep_blocks(rows, 1)), dim3(256), 0, kge_s(stream), p);
-    else
-        hipLaunchKernelGGL(hi_rows_kernel, dim3(kge_lp_dot_table_prep_blocks(rows, 1)), dim3(256), 0, kge_s(stream), p);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-/* 1 if kge_lp_split_count takes a fragment-major candidate table (es_frag = 1) for K columns on the one-product level */
-extern "C" int kge_lp_hi_stream_supported(int K)
-{
-    const int units = (K + 2 + 15) / 16;
-    return (units <= kge_hi_stream_max_units() || kge_hi_chunk_supported(units)) ? 1 : 0;
-}
-
-/* Candidate-table preparation of the L2 one-product sweep in one pass: en[row] = ||X[row]||^2 by kge_row_sqnorm's
- * sequential chain (same bits), *en_max_io = max(., max en), the fragment-major hi table of kge_lp_hi_rows_frag(aug_mode 1,
- * aug = en, aug_mul = -0.5) and *dn2max_io = max(., max_row ||x - hi(x)||^2) -- one launch, the table read once.
- * K % 4 == 0, ld % 4 == 0, X 16-byte aligned (else KGE_EUNSUPPORTED: use the separate entry points). */
-extern "C" int kge_lp_table_prep_blocks(int64_t rows)
-{
-    const int64_t blocks = kge_lp_split_rows_padded(rows, 0) / 16;
-    return (int)(blocks < 65536 ? blocks : 65536);
-}
-
-extern "C" int kge_lp_table_prep_l2(const float *X, int64_t ld, int64_t rows, int K, float *en, float *en_max_io,
-                                    void *out, float *dn2max_io, float *block_max, kge_stream_t stream)
-{
-    if (rows < 0 || K <= 0 || ld < K) return KGE_EINVAL;
-    if (rows == 0) return 0;
-    if (!X || !en || !out) return KGE_EINVAL;
-    if (K % 4 != 0 || ld % 4 != 0 || !kge_aligned16(X) || K > 8192) return KGE_EUNSUPPORTED;
-    TablePrepParams p;
-    p.X = X; p.ld = ld; p.rows = rows; p.rows_p = kge_lp_split_rows_padded(rows, 0);
-    p.K = K; p.units_p = kge_lp_hi_units(K);
-    p.en = en; p.en_max = en_max_io; p.out = reinterpret_cast<uint4 *>(out); p.dn2max = dn2max_io;
-    p.block_max = block_max;
-    p.dbg = kge_env_int("KGE_TP_DBG", 0);
-    const int lds_ld = ((K + 3) & ~3) + 4;
-    const int smem = (16 * lds_ld + 16 * 17 + 16) * 4;
-    const int64_t blocks = p.rows_p / 16;
-    auto k = table_prep_l2_kernel;
-    static int attr_dev[16];
-    if (smem > 48 * 1024)
-        if (int e = kge_ensure_dyn_smem(reinterpret_cast<const void *>(k), smem, attr_dev)) return e;
-    hipLaunchKernelGGL(k, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), smem, kge_s(stream), p);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int kge_lp_split_prefix_max(const float *cell_ss, int64_t rows, int is_query, int units_p, float *e2pref,
-                                       kge_stream_t stream)
-{
-    if (rows < 0 || units_p <= 0) return KGE_EINVAL;
-    if (rows == 0) return 0;
-    if (!cell_ss || !e2pref) return KGE_EINVAL;
-    const int64_t rows_p = kge_lp_split_rows_padded(rows, is_query);
-    if (units_p > 128) return KGE_EINVAL;       // (K <= 2031)
-    const int64_t want = (rows + 1023) / 1024;
-    hipLaunchKernelGGL(prefix_max_kernel, dim3((int)(want < 512 ? want : 512)), dim3(1024), 0, kge_s(stream), cell_ss,
-                       rows_p, rows, units_p, e2pref);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
 
 extern "C" int kge_lp_split_count(const kge_lp_desc *d, const kge_split_args *a, const float *s_true,
                                   int32_t *raw_count, kge_stream_t stream)
@@ -2690,6 +988,7 @@ extern "C" int kge_lp_split_count(const kge_lp_desc *d, const kge_split_args *a,
     // are within noise with 4 ahead -> 16 while 16 panels stay below ~3 MiB, else 4.
     p.qg = kge_env_int("KGE_SPLIT_QG", (int64_t)TQ * p.row_bytes * 16 <= (3 << 20) ? 16 : 4);
     const int slots = split_num_cus();
+    const int pm = d->mode == KGE_LP_L2_PROJH ? 1 : (d->mode == KGE_LP_L2_PROJD ? 2 : 0);      // threshold form of the epilogue
     if (a->es_frag) {
         // the free-running one-product kernel (lp_hi_stream.hip): fragment-major candidate table, resident query panel
         // long rows: the panel streamed in chunks (lp_hi_chunk.hip)
@@ -2722,7 +1021,6 @@ extern "C" int kge_lp_split_count(const kge_lp_desc *d, const kge_split_args *a,
             if (h.region_cap <= 0) return KGE_EINVAL;
         }
         h.true_idx = a->true_idx; h.c_base = d->c_base;
-        const int pm = d->mode == KGE_LP_L2_PROJH ? 1 : (d->mode == KGE_LP_L2_PROJD ? 2 : 0);
         if (chunked) {
             if (pm != 0 || h.region_count) return KGE_EUNSUPPORTED;
             return kge_hi_chunk_launch(h, slots, s);
@@ -2745,16 +1043,12 @@ extern "C" int kge_lp_split_count(const kge_lp_desc *d, const kge_split_args *a,
         if (a->n_single_p < 0 || a->n_multi_p < 0 || a->n_single_p % TQ || a->n_multi_p % TQ ||
             (a->n_single_p > 0 && !a->col_q) || (a->n_multi_p > 0 && !a->members))
             return KGE_EINVAL;
-        const int pm = d->mode == KGE_LP_L2_PROJH ? 1 : (d->mode == KGE_LP_L2_PROJD ? 2 : 0);
         if (a->n_single_p > 0) {
             p.col_q = a->col_q;
             p.q_panels = (int)(a->n_single_p / TQ);
             p.n_items = (int64_t)p.q_panels * p.c_tiles;
             const int grid = (int)(p.n_items < slots ? p.n_items : slots);
-            rc = lv1 ? (pm == 1 ? launch_split<8, false, 1, 0, 1>(p, grid, s)
-                                : (pm == 2 ? launch_split<8, false, 2, 0, 1>(p, grid, s) : launch_split<8, false, 0, 0, 1>(p, grid, s)))
-                     : (pm == 1 ? launch_split<8, false, 1>(p, grid, s)
-                                : (pm == 2 ? launch_split<8, false, 2>(p, grid, s) : launch_split<8, false, 0>(p, grid, s)));
+            rc = launch_split_for(pm, 0, lv1, false, p, grid, s);
             if (rc) return rc;
         }
         if (a->n_multi_p > 0) {
@@ -2764,130 +1058,18 @@ extern "C" int kge_lp_split_count(const kge_lp_desc *d, const kge_split_args *a,
             p.q_panels = (int)(a->n_multi_p / TQ);
             p.n_items = (int64_t)p.q_panels * p.c_tiles;
             const int grid = (int)(p.n_items < slots ? p.n_items : slots);
-            rc = lv1 ? (pm == 1 ? launch_split<8, false, 1, GSETS, 1>(p, grid, s)
-                                : (pm == 2 ? launch_split<8, false, 2, GSETS, 1>(p, grid, s) : launch_split<8, false, 0, GSETS, 1>(p, grid, s)))
-                     : (pm == 1 ? launch_split<8, false, 1, GSETS>(p, grid, s)
-                                : (pm == 2 ? launch_split<8, false, 2, GSETS>(p, grid, s) : launch_split<8, false, 0, GSETS>(p, grid, s)));
+            rc = launch_split_for(pm, GSETS, lv1, false, p, grid, s);
         }
         return rc;
     }
     p.q_panels = (int)((d->B + TQ - 1) / TQ);
     p.n_items = (int64_t)p.q_panels * p.c_tiles;
     const int grid = (int)(p.n_items < slots ? p.n_items : slots);
-    if (lv1 && d->mode == KGE_LP_L2_PROJH) return launch_split<8, false, 1, 0, 1>(p, grid, s);
-    if (lv1 && d->mode == KGE_LP_L2_PROJD) return launch_split<8, false, 2, 0, 1>(p, grid, s);
-    if (lv1) return p.dbg ? launch_split<8, true, 0, 0, 1>(p, grid, s) : launch_split<8, false, 0, 0, 1>(p, grid, s);
-    if (d->mode == KGE_LP_L2_PROJH) return launch_split<8, false, 1>(p, grid, s);
-    if (d->mode == KGE_LP_L2_PROJD) return launch_split<8, false, 2>(p, grid, s);
-    return p.dbg ? launch_split<8, true, 0>(p, grid, s) : launch_split<8, false, 0>(p, grid, s);
+    return launch_split_for(pm, 0, lv1, p.dbg != 0, p, grid, s);      // (the probes: this path only)
 }
 
 /* threshold sets per grouped column (kge_split_args.members) */
 extern "C" int kge_lp_split_group_sets(void) { return GSETS; }
-
-extern "C" int kge_lp_split_recheck(const kge_lp_desc *d, const float *s_true, const int32_t *list, int32_t cap,
-                                    const int32_t *list_count, int32_t *raw_count, float *list_stat, kge_stream_t stream)
-{
-    int rc = kge_lp_desc_check(d);
-    if (rc) return rc;
-    if (d->B == 0 || d->N == 0) return 0;
-    if (!s_true || !list || cap <= 0 || !list_count || !raw_count) return KGE_EINVAL;
-    if (!KGE_LP_IS_MFMA(d->mode)) return KGE_EINVAL;
-    const bool vec4 = kge_lp_vec4(*d);
-    const int grid = split_num_cus() * kge_env_int("KGE_SPLIT_RECHECK_WAVES", 160 * 1024 / (2 * 64 * KGE_PS_LD * 4));
-    if (vec4)
-        hipLaunchKernelGGL(split_recheck_kernel<true>, dim3(grid), dim3(64), 0, kge_s(stream), *d, s_true, list, cap,
-                           list_count, raw_count, list_stat);
-    else
-        hipLaunchKernelGGL(split_recheck_kernel<false>, dim3(grid), dim3(64), 0, kge_s(stream), *d, s_true, list,
-                           cap, list_count, raw_count, list_stat);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-/* regions of the list of n queries' sweep: 3 per panel of 96 queries (kge_split_args.region_count) */
-extern "C" int kge_lp_split_regions(int64_t B)
-{
-    return (int)(kge_lp_split_rows_padded(B, 1) / RR_PANEL) * 3;
-}
-
-// LDS segment of the region recheck: logical columns of the query rows resident at a time (a multiple of 32, the chunk of the
-// candidate-row staging), from the byte budget of the 32 rows (KGE_REGION_MAX_BYTES, default 36 KiB: at K = 200 the region's
-// 26 KB of query rows leave six wavefronts per CU; measured r05 -- profiles/r05/region_recheck_ab.txt -- a WHOLE 52 KB row
-// block at K = 400 left four and was slower than no regions; r06 passes longer rows through in segments instead)
-static int region_seg_cols(int K)
-{
-    const int max_ld = kge_env_int("KGE_REGION_MAX_BYTES", 36 * 1024) / (RR_ROWS * 4);
-    const int ld_full = K + (((K >> 2) & 1) ? 0 : 4);
-    if (ld_full <= max_ld) return K;
-    // longer rows: SMALLER segments than the budget of a whole row block -- more wavefronts per CU is what the kernel lives on
-    // (cfg4, DistMult d = 400, same box: no regions 2.107 ms per evaluate, 36 KiB segments 2.083, 20 KiB 2.031, 12 KiB 2.036;
-    // profiles/r06/region_segments_ab.txt)
-    const int seg_ld = min(max_ld, kge_env_int("KGE_REGION_SEG_BYTES", 20 * 1024) / (RR_ROWS * 4));
-    int seg = ((seg_ld - 4) / 32) * 32;
-    return seg < 32 ? 32 : seg;
-}
-
-/* 1 if kge_lp_split_count / kge_lp_split_recheck_regions take a list cut into regions for this problem */
-extern "C" int kge_lp_split_regions_supported(const kge_lp_desc *d)
-{
-    if (kge_lp_desc_check(d) || !KGE_LP_IS_MFMA(d->mode) || !kge_lp_vec4(*d)) return 0;
-    const int K = d->K0 + d->K1;
-    // (rows of the free-running kernel's range: the chunked-panel kernel of longer rows keeps one global list; segments of the
-    // operand must not cut a 16-byte piece: K0 % 4 == 0 is part of kge_lp_vec4)
-    if ((K + 2 + 15) / 16 > 32) return 0;
-    if (region_seg_cols(K) < K && kge_env_int("KGE_REGION_SEGMENTS", 1) == 0) return 0;
-    return 1;
-}
-
-extern "C" int kge_lp_split_recheck_regions(const kge_lp_desc *d, const float *s_true, const int32_t *list, int32_t cap,
-                                            const int32_t *region_count, int32_t *raw_count, float *list_stat,
-                                            int32_t *list_count, kge_stream_t stream)
-{
-    int rc = kge_lp_desc_check(d);
-    if (rc) return rc;
-    if (d->B == 0 || d->N == 0) return 0;
-    if (!s_true || !list || cap <= 0 || !region_count || !raw_count) return KGE_EINVAL;
-    if (!kge_lp_split_regions_supported(d)) return KGE_EINVAL;
-    const int n_regions = kge_lp_split_regions(d->B);
-    const int32_t region_cap = cap / n_regions;
-    if (region_cap <= 0) return KGE_EINVAL;
-    const int K = d->K0 + d->K1;
-    const int seg = region_seg_cols(K);
-    const int ldq = seg + (((seg >> 2) & 1) ? 0 : 4);   // floats: a multiple of 4, an odd number of 16-byte pieces
-    const int nwv = kge_env_int("KGE_RECHECK_REGION_WAVES", 2);
-    const int smem = (RR_ROWS * ldq + (nwv == 4 ? 4 : 2) * 64 * KGE_PS_LD) * 4;
-    const int want = split_num_cus() * 6;
-    const int grid = n_regions < want ? n_regions : want;
-    static int attr2[16], attr4[16];     // per device
-    if (nwv == 4) {
-        auto k = split_recheck_regions_kernel<4>;
-        if (int e = kge_ensure_dyn_smem(reinterpret_cast<const void *>(k), smem, attr4)) return e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(256), smem, kge_s(stream), *d, s_true, list, region_cap, region_count, n_regions,
-                           ldq, seg, raw_count, list_stat, list_count);
-    } else {
-        auto k = split_recheck_regions_kernel<2>;
-        if (int e = kge_ensure_dyn_smem(reinterpret_cast<const void *>(k), smem, attr2)) return e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(128), smem, kge_s(stream), *d, s_true, list, region_cap, region_count, n_regions,
-                           ldq, seg, raw_count, list_stat, list_count);
-    }
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-/* *max_io = max(*max_io, max_i |x[i]|)  (device scalar, non-negative; the bound on the projection gather term) */
-extern "C" int kge_absmax(const float *x, int64_t n, float *max_io, kge_stream_t stream)
-{
-    if (n < 0 || !max_io) return KGE_EINVAL;
-    if (n == 0) return 0;
-    if (!x) return KGE_EINVAL;
-    const int64_t want = (n + 1023) / 1024;
-    const int grid = (int)(want < 1024 ? want : 1024);
-    hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(256), 0, kge_s(stream), x, n, max_io);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
 
 /* 1 if this device's v_mfma_f32_32x32x16_f16 accumulates as modelled (see mfma_selftest_kernel), 0 if
  * not, negative / positive error codes as usual.  Synchronises; call it once, outside any capture. */
@@ -2932,142 +1114,4 @@ extern "C" int kge_mfma_f16_selftest(void)
     for (int t = 0; t < NT_; ++t)
         if (got[t] != expect[t]) return 0;
     return 1;
-}
-
-/* The same candidate side in ONE launch and ONE pass over the table (r06): the operand scale is the one the squared-norm
- * maxima of a PREVIOUS evaluation ask for (prev_nmax[2], device; kge_lp_dot_query_pipeline keeps them), the fragment-major
- * hi table, its residual maxima per block (dn_block_max) and THIS pass's squared-norm maxima per block
- * (nm_block_max[2][kge_lp_dot_table_prep_blocks(rows, 1)]) come out; hand both arrays and prev_nmax to
- * kge_lp_dot_query_pipeline, which folds them, raises *overflow when the table has outgrown (or fallen below) the scale
- * that was used -- the caller redoes that evaluation on another path -- and stores the new maxima for the next call.
- * KGE_EINVAL unless the rows are float4-readable (K0, K1, ld % 4 == 0, 16-byte aligned): then kge_lp_dot_table_prep. */
-extern "C" int kge_lp_dot_table_prep_fused(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1,
-                                           int64_t rows, const float *prev_nmax, void *out, float *dn_block_max,
-                                           float *nm_block_max, kge_stream_t stream)
-{
-    if (rows <= 0 || K0 <= 0 || K1 < 0 || ld0 < K0 || (K1 > 0 && ld1 < K1)) return KGE_EINVAL;
-    if (!X0 || (K1 > 0 && !X1) || !prev_nmax || !out || !dn_block_max || !nm_block_max) return KGE_EINVAL;
-    const bool vec = K0 % 4 == 0 && K1 % 4 == 0 && ld0 % 4 == 0 && ((size_t)X0 & 15) == 0 &&
-                     (K1 == 0 || (ld1 % 4 == 0 && ((size_t)X1 & 15) == 0));
-    if (!vec) return KGE_EINVAL;
-    HiRowsParams p;
-    p.X0 = X0; p.X1 = K1 > 0 ? X1 : nullptr; p.ld0 = ld0; p.ld1 = ld1; p.K0 = K0; p.K1 = K1;
-    p.rows = rows;
-    p.rows_p = kge_lp_split_rows_padded(rows, 0);
-    p.aug_mode = 4; p.aug = nullptr; p.aug_mul = 0.f;
-    p.nmax0 = nullptr; p.nmax1 = nullptr;
-    p.units_p = kge_lp_hi_units(K0 + K1);
-    p.out = reinterpret_cast<uint4 *>(out);
-    p.dn2 = nullptr; p.dn2max = nullptr; p.row_index = nullptr;
-    p.frag = 1;
-    p.nm_bmax = nullptr; p.nm_blocks = 0; p.dn_bmax = dn_block_max; p.prev_nmax = prev_nmax; p.nm_out = nm_block_max;
-    hipLaunchKernelGGL(hi_rows_frag_kernel<true>, dim3(kge_lp_dot_table_prep_blocks(rows, 1)), dim3(256), 0, kge_s(stream), p);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-/* TransE-L2 query side of one batch in ONE launch (what kge_lp_prep + kge_row_sqnorm + kge_lp_pair_scores
- * (true scores) + kge_lp_split_rows(queries) + the threshold kernel of kge_lp_split_count do separately),
- * bit-identical outputs.  Q (B,d), qn (B), s_true (B), Qs (split operand), thr (2*Bp floats), *list_count = 0.
- * The candidate table must be the whole entity table (no shard).  Then call kge_lp_split_count with
- * thr_ready = 1. */
-// The query side of one DistMult (E1 = R1 = NULL) / ComplEx batch on the one-product level in one launch, per-query operand
-// scales (dot_query_pipeline_kernel).  emax0 / emax1 / de2max must hold their final values when the launch runs.
-extern "C" int kge_lp_dot_query_pipeline(int side, const float *E0, const float *E1, const float *R0, const float *R1, int d,
-                                         const int64_t *h, const int64_t *t, const int64_t *r, int64_t B,
-                                         const float *emax0, const float *emax1, const float *de2max, float *qmax_io,
-                                         int accum_model, float eps_scale, float *Q0, float *Q1, float *qn, float *s_true,
-                                         void *Qh, float *thr, float *q_dn2, int32_t *list_count, float *overflow,
-                                         int32_t *zero_i32, int64_t zero_n, const float *dn_block_max, int dn_blocks,
-                                         const float *nm_block_max, int nm_blocks, float *prev_nmax, kge_stream_t stream)
-{
-    if (dn_block_max && dn_blocks <= 0) return KGE_EINVAL;
-    if (nm_block_max && nm_blocks <= 0) return KGE_EINVAL;
-    const bool both = side == KGE_SIDE_BOTH, cplx = E1 != nullptr;
-    if ((side != KGE_SIDE_TAIL && side != KGE_SIDE_HEAD && !both) || d <= 0 || d > 4096 || B < 0) return KGE_EINVAL;
-    if (B == 0) return 0;
-    if (!E0 || !R0 || !h || !t || !r || !emax0 || !de2max || !Q0 || !qn || !s_true || !Qh || !thr || !list_count || !overflow)
-        return KGE_EINVAL;
-    if (cplx && (!R1 || !Q1 || !emax1)) return KGE_EINVAL;
-    if (!cplx && (R1 || Q1)) return KGE_EINVAL;
-    if (d % 8 != 0 || !kge_aligned16(E0) || !kge_aligned16(R0) || (cplx && (!kge_aligned16(E1) || !kge_aligned16(R1))))
-        return KGE_EINVAL;      // float4 staging, hi cells of 8 columns inside one segment
-    if (zero_n < 0 || (zero_n > 0 && !zero_i32)) return KGE_EINVAL;
-    DotPipeParams p;
-    p.tail = both ? 2 : (side == KGE_SIDE_TAIL ? 1 : 0);
-    p.Bh = B;
-    p.E0 = E0; p.E1 = E1; p.R0 = R0; p.R1 = R1; p.d = d; p.h = h; p.t = t; p.r = r;
-    p.B = both ? 2 * B : B; p.Bp = kge_lp_split_rows_padded(p.B, 1);
-    p.emax0 = emax0; p.emax1 = cplx ? emax1 : nullptr; p.de2max = de2max; p.qmax_io = qmax_io;
-    p.c_acc = accum_model == 1 ? 1.25f : 2.0f; p.eps_scale = eps_scale;
-    const int K = cplx ? 2 * d : d;
-    p.units = (K + 2 + 15) / 16; p.units_p = kge_lp_hi_units(K);
-    p.Q0 = Q0; p.Q1 = Q1; p.qn = qn; p.s_true = s_true; p.q_dn2 = q_dn2;
-    p.thr = reinterpret_cast<float2 *>(thr);
-    p.Qh = reinterpret_cast<_Float16 *>(Qh);
-    p.list_count = list_count; p.overflow = overflow;
-    p.zero_i32 = zero_i32; p.zero_n = zero_n;
-    p.dn_bmax = dn_block_max; p.dn_blocks = dn_blocks;
-    p.nm_bmax = nm_block_max; p.nm_blocks = nm_blocks; p.prev_nmax = prev_nmax;
-    // queries per wavefront: 16 -- or 4 for a small batch (the kernel is a latency chain per group: fewer than two groups of
-    // 16 per SIMD leave most of the chip idle while ~400 wavefronts walk 10 chunks each)
-    const int qpw = kge_env_int("KGE_DQPIPE_QPW", p.Bp / 16 < 2048 ? 4 : 16);
-    const int64_t groups = (p.Bp + qpw - 1) / qpw, blocks = (groups + 3) / 4;
-    const int grid = (int)(blocks < 256 * 16 ? blocks : 256 * 16);
-    if (qpw == 4) {
-        if (cplx) hipLaunchKernelGGL((dot_query_pipeline_kernel<4, true>), dim3(grid), dim3(256), 0, kge_s(stream), p);
-        else hipLaunchKernelGGL((dot_query_pipeline_kernel<4, false>), dim3(grid), dim3(256), 0, kge_s(stream), p);
-    } else {
-        if (cplx) hipLaunchKernelGGL((dot_query_pipeline_kernel<16, true>), dim3(grid), dim3(256), 0, kge_s(stream), p);
-        else hipLaunchKernelGGL((dot_query_pipeline_kernel<16, false>), dim3(grid), dim3(256), 0, kge_s(stream), p);
-    }
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int kge_lp_query_pipeline(int side, const float *E, const float *R, int d, const int64_t *h,
-                                     const int64_t *t, const int64_t *r, int64_t B, const float *en,
-                                     const float *emax, float *qmax_io, int accum_model, float eps_scale, float *Q,
-                                     float *qn, float *s_true, void *Qs, float *thr, int32_t *list_count,
-                                     const float *e2pref, const int32_t *qs_row, int level, const float *de2max,
-                                     float *q_dn2, const float *tp_block_max, int tp_blocks, int32_t *zero_i32,
-                                     int64_t zero_n, kge_stream_t stream)
-{
-    if (level != 0 && level != 1) return KGE_EINVAL;
-    if (level == 1 && !de2max) return KGE_EINVAL;
-    const bool both = side == KGE_SIDE_BOTH;
-    if ((side != KGE_SIDE_TAIL && side != KGE_SIDE_HEAD && !both) || d <= 0 || d > 4096 || B < 0) return KGE_EINVAL;
-    if (B == 0) return 0;
-    if (!E || !R || !h || !t || !r || !en || !emax || !Q || !qn || !s_true || !Qs || !thr || !list_count) return KGE_EINVAL;
-    QueryPipeParams p;
-    p.tail = both ? 2 : (side == KGE_SIDE_TAIL ? 1 : 0);
-    p.Bh = B;
-    p.E = E; p.R = R; p.d = d; p.h = h; p.t = t; p.r = r;
-    p.B = both ? 2 * B : B; p.Bp = kge_lp_split_rows_padded(p.B, 1);
-    p.en = en; p.emax = emax; p.qmax_io = qmax_io;
-    p.c_acc = accum_model == 1 ? 1.25f : 2.0f; p.eps_scale = eps_scale;
-    p.units = (d + 1 + 15) / 16; p.units_p = kge_lp_split_units(d, 1);
-    p.level = level; p.de2max = de2max; p.q_dn2 = q_dn2;
-    p.tp_bmax = tp_block_max; p.tp_blocks = tp_blocks;
-    p.emax_out = const_cast<float *>(emax); p.de2max_out = const_cast<float *>(de2max);
-    if (tp_block_max && tp_blocks <= 0) return KGE_EINVAL;
-    if (zero_n < 0 || (zero_n > 0 && !zero_i32)) return KGE_EINVAL;
-    p.zero_i32 = zero_i32; p.zero_n = zero_n;
-    p.dbg = kge_env_int("KGE_QP_DBG", 0);
-    if (level == 1) { p.units = (d + 2 + 15) / 16; p.units_p = kge_lp_hi_units(d); }
-    p.Q = Q; p.qn = qn; p.s_true = s_true;
-    p.thr = reinterpret_cast<float2 *>(thr);
-    p.Qs = reinterpret_cast<_Float16 *>(Qs);
-    p.list_count = list_count;
-    p.e2pref = e2pref;
-    p.qs_row = qs_row;
-    if (d % 4 != 0 || !kge_aligned16(E) || !kge_aligned16(R)) return KGE_EINVAL;   // float4 staging
-    const int qpw = kge_env_int("KGE_QPIPE_QPW", 16);
-    const int64_t groups = (p.Bp + qpw - 1) / qpw, blocks = (groups + 3) / 4;
-    const int grid = (int)(blocks < 256 * 16 ? blocks : 256 * 16);
-    if (qpw == 8) hipLaunchKernelGGL(query_pipeline_kernel<8>, dim3(grid), dim3(256), 0, kge_s(stream), p);
-    else if (qpw == 32) hipLaunchKernelGGL(query_pipeline_kernel<32>, dim3(grid), dim3(256), 0, kge_s(stream), p);
-    else hipLaunchKernelGGL(query_pipeline_kernel<16>, dim3(grid), dim3(256), 0, kge_s(stream), p);
-    KGE_CHECK_LAUNCH();
-    return 0;
 }
