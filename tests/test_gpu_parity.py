@@ -1634,7 +1634,9 @@ def test_device_built_index_and_plans_equal_the_torch_builds(hip, n_ent, n_rel, 
 @pytest.mark.parametrize('frag', [False, True])
 @pytest.mark.parametrize('B,N,K,cols_on', [(64, 300, 32, False), (1000, 3000, 200, False), (193, 257, 17, False), (5, 2, 1, False),
                                            (700, 1500, 203, False), (1000, 3000, 200, True), (400, 5000, 64, True),
-                                           (3000, 20000, 200, False), (2500, 9000, 400, False), (300, 1100, 500, False)])
+                                           (3000, 20000, 200, False), (2500, 9000, 400, False), (300, 1100, 500, False),
+                                           # grouped columns behind ONE 8-wave workgroup per CU: 26 units, and the runtime-unit loop
+                                           (129, 257, 400, True), (193, 700, 500, True)])
 def test_split_one_product_level_counts_equal_exact_counts(hip, B, N, K, cols_on, frag):
     """The ONE-PRODUCT level of the split prefilter (kge_split_args.level = 1: planar hi operands, one MFMA product per
     k16 unit, thresholds from the operands' measured f16 residuals) + exact recheck leave exactly the counts of the
@@ -1994,15 +1996,19 @@ def test_evaluator_one_pass_table_follows_growing_tables(hip, kind):
         assert redone[4] and redone[7] and not redone[2] and not redone[3] and not redone[6]
 
 
-@pytest.mark.parametrize('kind', ['transe', 'distmult', 'complex', 'transh', 'transd'])
-def test_evaluator_level_policy_and_identical_ranks(hip, kind):
+# (d = 64: the runtime-unit loop of the free-running kernel.  The projection epilogues of its other instantiations: 13 units on two
+# 4-wave workgroups per CU, 26 units and the runtime loop on one 8-wave workgroup)
+@pytest.mark.parametrize('kind,d', [pytest.param(k, 64, id=k) for k in ('transe', 'distmult', 'complex', 'transh', 'transd')] +
+                         [pytest.param(k, d, id='%s-d%d' % (k, d)) for d in (200, 400, 352) for k in ('transh', 'transd')])
+def test_evaluator_level_policy_and_identical_ranks(hip, kind, d):
     """LinkPredictionEvaluator with the one-product level forced on (model.split_level = 1), forced off (0) and on
     'auto' (first evaluation three products, the next ones follow the re-scored pair count): identical rank vectors,
     eager and as hipGraph replays; an evaluation whose one-product list overflows is redone on three products."""
     import torchkge_amd as tk
     import torchkge_amd.evaluation as evm
-    n_ent, n_rel, d = 4000, 9, 64
-    tables = orc.init_tables(kind, n_ent, n_rel, d, seed=5, d_rel=(48 if kind == 'transd' else None))
+    n_ent, n_rel = 4000, 9
+    # (TransD sweeps rows of the RELATION dimension: 48 beside d = 64, d itself for the wider cases)
+    tables = orc.init_tables(kind, n_ent, n_rel, d, seed=5, d_rel=((48 if d == 64 else d) if kind == 'transd' else None))
     m = build_model(kind, 2, tables, n_ent, n_rel)
     h, t, r = orc.synthetic_triples_zipf(n_ent, n_rel, 30000, 31, hubs=((1500, 'head'), (600, 'tail')))
     kg = tk.KnowledgeGraph(kg={'heads': h, 'tails': t, 'relations': r}, ent2ix={i: i for i in range(n_ent)},

@@ -40,10 +40,10 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVE_CYCLES
   tag=$(echo $pass | cut -d' ' -f1)
   timeout 300 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $OUT/pmc_level1_$tag -o bench -- python $R/bench.py --only-timed --steps 3 --warmup 1 --weights xavier --settle-ms 0 --no-graph --split-level 1 > $OUT/pmc_level1_$tag.log 2>&1
 done
-# power / clock of the free-running kernel back to back, and of its probes
+# power / clock of the free-running kernel back to back (its KGE_HS_PROBE timing probes are gone: the numbers stay in profiles/r05/)
 cd $R
-{ for pr in 0 16; do echo "== KGE_HS_PROBE=$pr"; LEVEL=1 TAIL=1 FRAG=1 KGE_HS_PROBE=$pr bash tools/power_probe.sh 0 2>&1 | grep -E "Power|sclk|launches"; done; } > $OUT/power_probe_hi_stream.txt
-{ for pr in 0 1 2 4 8 12 16; do LEVEL=1 TAIL=1 FRAG=1 K=200 KGE_HS_PROBE=$pr timeout 120 python tools/split_time.py 2>&1 | grep count | sed "s/^/probe=$pr /"; done
+{ LEVEL=1 TAIL=1 FRAG=1 bash tools/power_probe.sh 0 2>&1 | grep -E "Power|sclk|launches"; } > $OUT/power_probe_hi_stream.txt
+{ LEVEL=1 TAIL=1 FRAG=1 K=200 timeout 120 python tools/split_time.py 2>&1 | grep count
   LEVEL=1 TAIL=1 FRAG=0 K=200 timeout 120 python tools/split_time.py 2>&1 | grep count | sed "s/^/r04 kernel /"
   for K in 400; do for f in 0 1; do LEVEL=1 TAIL=1 FRAG=$f K=$K timeout 120 python tools/split_time.py 2>&1 | grep count; done; done; } > $OUT/hi_stream_probes.txt
 timeout 300 python tools/first_call.py 2>/dev/null | tail -1 > $OUT/first_call.json
