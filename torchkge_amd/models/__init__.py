@@ -1,4 +1,4 @@
 # -*- coding: utf-8 -*-
 from .interfaces import Model, TranslationModel, BilinearModel, EntityCandidates
 from .translation import TransEModel, TransHModel, TransDModel, TorusEModel, TransRModel
-from .bilinear import DistMultModel, ComplExModel, RESCALModel, HolEModel
+from .bilinear import DistMultModel, ComplExModel, RESCALModel, HolEModel, AnalogyModel

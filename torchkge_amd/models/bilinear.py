@@ -1,12 +1,14 @@
 # -*- coding: utf-8 -*-
-"""DistMult / ComplEx / RESCAL / HolE with the reference's constructors, attributes
+"""DistMult / ComplEx / RESCAL / HolE / ANALOGY with the reference's constructors, attributes
 and state_dict keys (torchkge/models/bilinear.py:14-143, :146-267, :270-411,
-:414-556) on the HIP engine: the all-candidates score matrix is one fp32 MFMA
+:414-556, :559-763) on the HIP engine: the all-candidates score matrix is one fp32 MFMA
 GEMM S = Q . E^T (ComplEx: K = 2d over the [Re | Im] tables, no concatenation;
-RESCAL / HolE: Q = the relation-transformed query rows, kge_bilinear_query)."""
+RESCAL / HolE: Q = the relation-transformed query rows, kge_bilinear_query;
+ANALOGY: K = scalar_dim + 2 complex_dim over the packed [sc | re | im] rows, kge_analogy_query)."""
 import torch
 
 from .. import _hip
+from .. import _hip_analogy
 from ..utils.modeling import init_embedding
 from .interfaces import BilinearModel, _table_of
 from .translation import _ent_range
@@ -362,3 +364,161 @@ class HolEModel(_OperatorModel):
         """(ent_emb, rel_emb) (bilinear.py:351-363)."""
         self.normalize_parameters()
         return self.ent_emb.weight.data, self.rel_emb.weight.data
+
+
+class _AnalogyScore(torch.autograd.Function):
+    """ANALOGY's scoring_function as one fused HIP kernel, differentiable wrt the six tables
+    (kge_analogy_score_triples / _bwd + the sorted row reduction)."""
+
+    @staticmethod
+    def forward(ctx, h, t, r, *tables):
+        tabs = [x.detach() for x in tables]
+        ctx.save_for_backward(h, t, r, *tabs)
+        return _hip_analogy.score_triples(tabs[:3], tabs[3:], h, t, r)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        h, t, r = ctx.saved_tensors[:3]
+        tabs = list(ctx.saved_tensors[3:])
+        grads = _hip_analogy.score_triples_bwd(tabs[:3], tabs[3:], h, t, r, grad_out, ctx.needs_input_grad[3:])
+        return (None,) * 3 + tuple(grads)
+
+
+class AnalogyModel(BilinearModel):
+    """ANALOGY (bilinear.py:559-763): ``AnalogyModel(emb_dim, n_entities, n_relations, scalar_share=0.5)``; DistMult on
+    ``scalar_dim = int(emb_dim * scalar_share)`` coordinates plus ComplEx on ``complex_dim = emb_dim - scalar_dim``;
+    parameters ``sc_ent_emb``, ``re_ent_emb``, ``im_ent_emb``, ``sc_rel_emb``, ``re_rel_emb``, ``im_rel_emb``; never
+    normalised (:652-656).
+
+    The score against a candidate is ONE dot product of width K = scalar_dim + 2 complex_dim between a query row
+    (kge_analogy_query) and the candidate's packed row [sc | re | im] (kge_analogy_pack_rows, once per evaluation): from
+    there on every path is DistMult's one-segment KGE_LP_DOT.  The documented score is served for EVERY split; the
+    reference's own inference_scoring_function adds (b, N, scalar_dim) to (b, N, complex_dim) tensors and so raises
+    (or broadcasts) unless the two are equal."""
+
+    _kind = None            # no kind of include/kge_hip.h: the entry points are those of include/kge_hip_analogy.h
+    _ENT_TABLES = ('sc_ent_emb', 're_ent_emb', 'im_ent_emb')
+    _ENT_POS = (0, 1, 2)
+
+    def __init__(self, emb_dim, n_entities, n_relations, scalar_share=0.5):
+        super().__init__(emb_dim, n_entities, n_relations)
+        self.scalar_dim = int(self.emb_dim * scalar_share)
+        self.complex_dim = int(self.emb_dim - self.scalar_dim)
+        if self.scalar_dim > _hip_analogy.MAX_DIM or self.complex_dim > _hip_analogy.MAX_DIM:
+            raise RuntimeError('torchkge_amd: AnalogyModel handles scalar_dim, complex_dim <= %d' % _hip_analogy.MAX_DIM)
+        self.sc_ent_emb = init_embedding(self.n_ent, self.scalar_dim)
+        self.re_ent_emb = init_embedding(self.n_ent, self.complex_dim)
+        self.im_ent_emb = init_embedding(self.n_ent, self.complex_dim)
+        self.sc_rel_emb = init_embedding(self.n_rel, self.scalar_dim)
+        self.re_rel_emb = init_embedding(self.n_rel, self.complex_dim)
+        self.im_rel_emb = init_embedding(self.n_rel, self.complex_dim)
+
+    def _tables(self):
+        return [self.sc_ent_emb.weight, self.re_ent_emb.weight, self.im_ent_emb.weight,
+                self.sc_rel_emb.weight, self.re_rel_emb.weight, self.im_rel_emb.weight]
+
+    def _lp_width(self):
+        return self.scalar_dim + 2 * self.complex_dim
+
+    def normalize_parameters(self):
+        """No normalisation for ANALOGY (bilinear.py:652-656)."""
+        pass
+
+    def get_embeddings(self):
+        return tuple(x.data for x in self._tables())
+
+    def scoring_function(self, h_idx, t_idx, r_idx):
+        """sc_h . diag(sc_r) . sc_t + Re(<h, r, conj(t)>) of each triplet (bilinear.py:634-650), one fused HIP kernel,
+        differentiable."""
+        self._check_unsharded('scoring_function')
+        tables = self._tables()
+        _hip.require_cuda(h_idx, t_idx, r_idx, *tables)
+        return _AnalogyScore.apply(h_idx, t_idx, r_idx, *tables)
+
+    # ---- the packed candidate rows ----------------------------------------
+    def _packed(self, name, tabs):
+        """(rows, K rounded up to 4) packed [sc | re | im] rows of the three tables ``tabs``, pads zero: built once per
+        lp_session (never kept across sessions: the tables may change between them); inside a captured evaluation the
+        pack launch is part of the graph and reads the parameters at their addresses."""
+        tabs = [_hip.f32c(x) for x in tabs]
+        return self._cache.get(name, tabs, lambda: _hip_analogy.pack_rows(tabs))
+
+    def _dot(self, q, P):
+        return _hip.LpProblem(_hip.LP_DOT, q, P, K0=self._lp_width())
+
+    def inference_scoring_function(self, h, t, r):
+        """h, t, r are (sc, re, im) tuples; the one holding 3-D tensors is the candidate set (bilinear.py:682-711)."""
+        A = _hip_analogy
+        if t[1].dim() == 3:
+            assert h[1].dim() == 2 and r[1].dim() == 2      # tail completion
+            q, cand = A.query(_hip.SIDE_TAIL, h, r, None, None, None, B=h[1].shape[0]), t
+        elif h[1].dim() == 3:
+            assert t[1].dim() == 2 and r[1].dim() == 2      # head completion
+            q, cand = A.query(_hip.SIDE_HEAD, t, r, None, None, None, B=t[1].shape[0]), h
+        else:
+            assert r[1].dim() == 3 and h[1].dim() == 2 and t[1].dim() == 2      # relation prediction
+            q, cand = A.query(A.SIDE_REL, h, t, None, None, None, B=h[1].shape[0]), r
+        tabs = [_table_of(c) for c in cand]
+        if all(x is not None for x in tabs):
+            return self._dot(q, self._packed('apk_cand', tabs)).scores()
+        # real materialised candidates: one batched product per segment, summed
+        d_sc, d_c = self.scalar_dim, self.complex_dim
+        s = None
+        for c0, w, c in ((0, d_sc, cand[0]), (d_sc, d_c, cand[1]), (d_sc + d_c, d_c, cand[2])):
+            if w:
+                part = _hip.lp_scores_batched(_hip.LP_DOT, q[:, c0:c0 + w], c)
+                s = part if s is None else _hip.ewise(_hip.EW_ADD, s, part)
+        return s
+
+    def inference_prepare_candidates(self, h_idx, t_idx, r_idx, entities=True):
+        """((sc_h, re_h, im_h), (sc_t, re_t, im_t), (sc_r, re_r, im_r), (sc_cand, re_cand, im_cand)) with stride-0
+        candidate views (bilinear.py:713-763)."""
+        self._check_unsharded('inference_prepare_candidates')
+        b_size = max(h_idx.shape[0], t_idx.shape[0], r_idx.shape[0])   # inference passes one empty index
+        tabs = [x.data for x in self._tables()]
+        ent, rel = tabs[:3], tabs[3:]
+        K = self._lp_width()
+        d_sc, d_c = self.scalar_dim, self.complex_dim
+
+        def rows(tt, idx):      # the three gathers as one pack launch, handed out as column slices
+            P = _hip_analogy.pack_rows(tt, idx)
+            return P[:, :d_sc], P[:, d_sc:d_sc + d_c], P[:, d_sc + d_c:K]
+        h, t, r = rows(ent, h_idx), rows(ent, t_idx), rows(rel, r_idx)
+        src, n = (ent, self.n_ent) if entities else (rel, self.n_rel)
+        cand = tuple(x.view(1, n, x.shape[1]).expand(b_size, n, x.shape[1]) for x in src)
+        return h, t, r, cand
+
+    # ---- evaluation ---------------------------------------------------------
+    def _lp_prep(self, side, h_idx, t_idx, r_idx, exchange=None, qtabs=None, **want):
+        """The query rows of a batch (kge_analogy_query).  Row-sharded tables: rows of entities another rank owns come
+        back as zeros and ``exchange`` sums them over the shards; ``qtabs``: the three query-entity replicas replace the
+        entity tables (h_idx / t_idx index them)."""
+        tabs = [x.data for x in self._tables()]
+        ent, rel = tabs[:3], tabs[3:]
+        if qtabs is not None:
+            return (_hip_analogy.query(side, list(qtabs), rel, h_idx, t_idx, r_idx),)
+        lo, n = (self._row_shard[0], self._row_shard[1] - self._row_shard[0]) if self._row_shard is not None else (0, -1)
+        Q = _hip_analogy.query(side, ent, rel, h_idx, t_idx, r_idx, ent_lo=lo, ent_n=n)
+        if self._row_shard is not None:
+            if exchange is None:
+                raise RuntimeError('torchkge_amd: a row-sharded model needs the evaluator\'s query exchange')
+            exchange([Q])
+        return (Q,)
+
+    def lp_problem(self, h_idx, t_idx, r_idx, side, ent_lo=0, ent_hi=None, exchange=None, qtabs=None, cols=None):
+        ent_lo, ent_hi = _ent_range(self, ent_lo, ent_hi)
+        sd = _hip.side_code(side)
+        K = self._lp_width()
+        Q = self._lp_prep(sd, h_idx, t_idx, r_idx, exchange, qtabs=qtabs)[0]
+        ent = [self._cand_rows(x.data, ent_lo, ent_hi) for x in self._tables()[:3]]
+        P = self._packed('apk_%d_%d' % (ent_lo, ent_hi), ent)
+        prob = self._attach_dot_split(_hip.LpProblem(_hip.LP_DOT, Q, P, c_base=ent_lo, K0=K), P, c_base=ent_lo, K=K)
+        prob.cols = cols if (sd == _hip.SIDE_BOTH and prob.split is not None) else None
+        return prob
+
+    def lp_true_scores_replica(self, prob, qctx):
+        """The (2B) true scores from the query-entity replicas, on every rank: the replicas packed (once per evaluation)
+        and the one-segment DOT problem's pair chain -- the rows and the chain the owner shard runs: identical bits."""
+        qt, hq, tq = qctx
+        P = self._packed('apk_replica', list(qt))
+        return self._dot(prob.keep[0], P).pair_scores(torch.cat([tq, hq]))

@@ -422,12 +422,12 @@ class Model(Module):
             sp['list_stat'] = guard_slot(g, G_RESCORED)
         if dot and prep is None:
             def norms():
-                _hip.row_sqnorm(T0, max_io=emax, bound_only=True)       # (only the maxima are used: the operands' scale)
+                _hip.row_sqnorm(T0, K=K, max_io=emax, bound_only=True)  # (only the maxima are used: the operands' scale)
                 if T1 is not None:
                     _hip.row_sqnorm(T1, max_io=emax1, bound_only=True)
                 return True
             self._cache.get('esn_' + tag, srcs, norms)      # the norm maxima fix the operands' scale: before either table
-        how = {'X1': T1, 'dot': True, 'nmax0': emax, 'nmax1': emax1} if dot else {'K': K, 'aug': aug}
+        how = {'K': K, 'X1': T1, 'dot': True, 'nmax0': emax, 'nmax1': emax1} if dot else {'K': K, 'aug': aug}
         lvl1, frag = self._level_and_frag() if level is None else level
         if not lvl1:
             Es, e2 = self._cache.get(('esd_' if dot else 'es_') + tag, srcs, lambda: _hip.split_table(T0, **how))
@@ -443,11 +443,12 @@ class Model(Module):
         sp.update({'Es': Eh, 'e2pref': None, 'level': 1, 'de2max': de2, 'es_frag': frag})
         return sp
 
-    def _attach_dot_split(self, prob, T0, T1=None, c_base=0):
+    def _attach_dot_split(self, prob, T0, T1=None, c_base=0, K=None):
         """Rank counts of a KGE_LP_DOT problem through the certified f16-split
-        prefilter (only inside an evaluation, where the guard vector exists)."""
+        prefilter (only inside an evaluation, where the guard vector exists).  ``K``: the columns of T0 that count
+        (a padded leading dimension: ANALOGY's packed rows); None: all of them."""
         if self._guard_on and self.split_filter and self._split_ok:
-            prob.split = self._split_operand((c_base, T0.shape[0]), T0, T1, dot=True)
+            prob.split = self._split_operand((c_base, T0.shape[0]), T0, T1, K=K, dot=True)
         return prob
 
     def _dot_fused_problem(self, sd, h_idx, t_idx, r_idx, ent, rel):
