@@ -9,7 +9,7 @@ from .utils import l1_dissimilarity, l2_dissimilarity
 from .data_structures import KnowledgeGraph, SmallKG
 from .evaluation import LinkPredictionEvaluator, RelationPredictionEvaluator, clear_eval_state
 from .inference import EntityInference
-from .models import TransEModel, TransHModel, TransDModel, TorusEModel, TransRModel, DistMultModel, ComplExModel, RESCALModel, HolEModel, AnalogyModel
+from .models import TransEModel, TransHModel, TransDModel, TorusEModel, TransRModel, DistMultModel, ComplExModel, RESCALModel, HolEModel, AnalogyModel, ConvKBModel
 from .sampling import BernoulliNegativeSampler, UniformNegativeSampler
 
 

@@ -17,9 +17,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfma.hip', 'lp_split_operands.hip', 'lp_split_query.hip',
            'lp_split_recheck.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip', 'lp_l1_sad.hip', 'rank_filter.hip',
-           'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip', 'transr_xform.hip', 'analogy.hip']
+           'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip', 'transr_xform.hip', 'analogy.hip', 'convkb.hip']
 HEADERS = ['kge_common.h', 'lp_split_common.h', 'lp_hi_sweep.h', os.path.join('..', '..', 'include', 'kge_hip.h'),
-           os.path.join('..', '..', 'include', 'kge_hip_analogy.h')]
+           os.path.join('..', '..', 'include', 'kge_hip_analogy.h'), os.path.join('..', '..', 'include', 'kge_hip_convkb.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
 # libkge_hip.so does not depend on librccl
@@ -52,7 +52,10 @@ EXTRA_FLAGS = {'lp_direct.hip': ['-fno-slp-vectorize'], 'lp_hi_stream.hip': _NO_
                # transr_xform.hip (TransR: MFMA squared norms with a VALU epilogue beside other waves' MFMAs, fmaf chains): the same
                'transr_xform.hip': ['-fno-slp-vectorize'],
                # analogy.hip (ANALOGY query rows: mul, mul, add / sub on pairs of neighbouring outputs): the same
-               'analogy.hip': ['-fno-slp-vectorize']}
+               'analogy.hip': ['-fno-slp-vectorize'],
+               # convkb.hip (ConvKB: per filter fma, max, fma on a register tile of pairs -- plain VALU at 63 T lane-ops/s; the
+               # vectoriser would pack the per-filter FMAs into v_pk_fma_f32 at half rate): the same
+               'convkb.hip': ['-fno-slp-vectorize']}
 
 
 def _hipcc():

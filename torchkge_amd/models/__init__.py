@@ -2,3 +2,4 @@
 from .interfaces import Model, TranslationModel, BilinearModel, EntityCandidates
 from .translation import TransEModel, TransHModel, TransDModel, TorusEModel, TransRModel
 from .bilinear import DistMultModel, ComplExModel, RESCALModel, HolEModel, AnalogyModel
+from .deep import ConvKBModel
