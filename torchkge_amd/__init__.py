@@ -13,11 +13,13 @@ from .models import TransEModel, TransHModel, TransDModel, TorusEModel, TransRMo
 from .sampling import BernoulliNegativeSampler, UniformNegativeSampler
 
 
-# Names of the reference that are OUT OF SCOPE of this engine: a clear
-# error instead of an AttributeError, so a ported script says what to do.
+# Names of the reference that this package does not provide at its top level: a clear error
+# instead of an AttributeError, so a ported script says what to do.  RelationInference is out of scope (SURVEY.md
+# section 8); the triplet-classification pair is provided by its submodules.
 _NOT_PROVIDED = {
-    'TripletClassificationEvaluator': 'triplet classification is outside the link-prediction hot path',
-    'PositionalNegativeSampler': 'use BernoulliNegativeSampler / UniformNegativeSampler (the samplers on the hot path)',
+    'TripletClassificationEvaluator': 'not at the top level yet -- import it from torchkge_amd.evaluation, the path the reference\'s '
+                                      'tutorial uses',
+    'PositionalNegativeSampler': 'not at the top level yet -- import it from torchkge_amd.sampling, the path the reference\'s tests use',
     'RelationInference': 'use RelationPredictionEvaluator, or EntityInference for missing entities',
 }
 

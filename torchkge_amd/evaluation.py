@@ -40,11 +40,12 @@ import weakref
 import torch
 from tqdm.autonotebook import tqdm
 
-from . import _hip
+from . import _hip, _hip_triplet
 from . import distributed as kdist
 from .exceptions import NotYetEvaluatedError
 from .filter_index import ColumnPlan, filter_index_for, KEY2_SPAN, FilterPlan
 from .models.interfaces import Model as _BaseModel, guard_slot, G_QMAX, G_EMAX, G_OVERFLOW, G_RESCORED
+from .sampling import PositionalNegativeSampler
 from .utils.data import get_n_batches
 from .utils.modeling import filter_scores
 from .utils.operations import get_rank
@@ -1553,3 +1554,68 @@ class RelationPredictionEvaluator(object):
                 i, round(self.hit_at_k(k=i)[0], n_digits), i, round(self.hit_at_k(k=i)[1], n_digits)))
         print('Mean Rank : {} \t Filt. Mean Rank : {}'.format(int(self.mean_rank()[0]), int(self.mean_rank()[1])))
         print('MRR : {} \t\t Filt. MRR : {}'.format(round(self.mrr()[0], n_digits), round(self.mrr()[1], n_digits)))
+
+
+class TripletClassificationEvaluator(object):
+    """Triplet classification of Socher et al. 2013 with the reference's interface (torchkge/evaluation.py:428-580):
+    ``TripletClassificationEvaluator(model, kg_val, kg_test)``, ``.evaluated``, ``.thresholds``, ``.sampler``,
+    ``.get_scores(heads, tails, relations, batch_size)``, ``.evaluate(b_size)``, ``.accuracy(b_size)``.
+
+    ``evaluate`` scores one positional negative per validation fact and takes, per relation, the largest of those
+    scores as the threshold above which a fact counts as true (a relation without validation facts: the largest score
+    of all); ``accuracy`` is the share of test facts above and of their negatives below their relation's threshold.
+
+    The reference builds one boolean mask over all facts per relation and moves every negative through host memory.
+    Here negatives (kge_positional_corrupt), scores (Model.scoring_function), thresholds (kge_relation_max) and the two
+    decision counts (kge_threshold_count) stay on the device under no_grad; the one host read of a whole evaluation is
+    the final pair of counts.  For that the sampler runs with ``sync_free = True`` (see PositionalNegativeSampler: a
+    different but equally distributed random stream; set ``evaluator.sampler.sync_free = False`` for the reference's
+    order of draws at one host read per batch).  ``b_size`` is taken literally: that many facts per corrupt_batch /
+    scoring_function call.  ``thresholds`` is an fp32 (n_rel) tensor on the model's device."""
+
+    def __init__(self, model, kg_val, kg_test):
+        self.model = model
+        self.kg_val = kg_val
+        self.kg_test = kg_test
+        self.is_cuda = next(self.model.parameters()).is_cuda
+        self.evaluated = False
+        self.thresholds = None
+        self.sampler = PositionalNegativeSampler(self.kg_val, kg_test=self.kg_test)
+        self.sampler.sync_free = True
+
+    def _device(self):
+        return next(self.model.parameters()).device
+
+    def get_scores(self, heads, tails, relations, batch_size):
+        """scoring_function of the model over the triples, ``batch_size`` at a time; fp32 (n) on the model's device."""
+        dev = self._device()
+        heads, tails, relations = heads.to(dev), tails.to(dev), relations.to(dev)
+        _hip.require_cuda(heads, tails, relations)
+        scores = []
+        with torch.no_grad():
+            for lo in range(0, heads.shape[0], batch_size):
+                sl = slice(lo, lo + batch_size)
+                scores.append(self.model.scoring_function(heads[sl], tails[sl], relations[sl]))
+        if not scores:
+            return torch.zeros(0, dtype=torch.float32, device=dev)
+        return torch.cat(scores, dim=0)
+
+    def evaluate(self, b_size):
+        """Thresholds from the validation graph (evaluation.py:513-541)."""
+        r_idx = self.kg_val.relations.to(self._device())
+        neg_heads, neg_tails = self.sampler.corrupt_kg(b_size, self.is_cuda, which='main', on_device=True)
+        neg_scores = self.get_scores(neg_heads, neg_tails, r_idx, b_size)
+        self.thresholds = _hip_triplet.relation_max(neg_scores, r_idx, self.kg_val.n_rel)
+        self.evaluated = True
+
+    def accuracy(self, b_size):
+        """Share of the 2 * n_facts decisions on the test graph that are right (evaluation.py:543-580)."""
+        if not self.evaluated:
+            self.evaluate(b_size)
+        r_idx = self.kg_test.relations.to(self._device())
+        neg_heads, neg_tails = self.sampler.corrupt_kg(b_size, self.is_cuda, which='test', on_device=True)
+        scores = self.get_scores(self.kg_test.head_idx, self.kg_test.tail_idx, r_idx, b_size)
+        neg_scores = self.get_scores(neg_heads, neg_tails, r_idx, b_size)
+        counts = _hip_triplet.threshold_count(scores, neg_scores, r_idx, self.thresholds)
+        n_pos, n_neg = counts.tolist()          # the one host read
+        return (n_pos + n_neg) / (2 * self.kg_test.n_facts)

@@ -1,8 +1,10 @@
 # -*- coding: utf-8 -*-
-"""Negative samplers with the reference's interface (torchkge/sampling.py:16-327):
+"""Negative samplers with the reference's interface (torchkge/sampling.py:16-504, :556-592):
 ``NegativeSampler``, ``UniformNegativeSampler``, ``BernoulliNegativeSampler``
 (``.bern_probs``, ``.corrupt_batch(heads, tails, relations, n_neg=None)``,
-``.corrupt_kg(batch_size, use_cuda, which)``).
+``.corrupt_kg(batch_size, use_cuda, which)``), ``PositionalNegativeSampler``
+(``.possible_heads / .possible_tails / .n_poss_heads / .n_poss_tails``) and
+``get_possible_heads_tails``.
 
 The random draws are issued with the same torch RNG calls, in the same order
 and with the same sizes as the reference (bernoulli, randint(k),
@@ -11,12 +13,19 @@ reference's; the masked index-puts (the integer part) run in one HIP scatter
 (kge_corrupt_scatter).  ``sync_free=True`` draws B*n_neg replacements for both
 sides instead, removing the device->host sync of ``mask.sum().item()`` at the
 price of a different (equally distributed) random stream.
-"""
-import torch
-from torch import bernoulli, cat, ones, randint, tensor
 
-from . import _hip
+The positional sampler keeps its two possibility indices as dense per-relation
+CSRs on the device and corrupts a batch in one gather (kge_positional_corrupt):
+no Python loop over the facts of the graph or the elements of a batch.
+"""
+from collections import defaultdict
+
+import torch
+from torch import bernoulli, cat, ones, rand, randint, tensor
+
+from . import _hip, _hip_triplet
 from .exceptions import NotYetImplementedError
+from .filter_index import FilterIndex, KEY2_SPAN
 from .utils.data import DataLoader
 from .utils.operations import get_bernoulli_probs
 
@@ -113,3 +122,157 @@ class BernoulliNegativeSampler(NegativeSampler):
             n_neg = self.n_neg
         self.bern_probs = self.bern_probs.to(heads.device)
         return self._corrupt(heads, tails, self.bern_probs[relations].repeat(n_neg), n_neg)
+
+
+class _PossibilityIndex(object):
+    """Dense per-relation CSR of one side: the distinct entities seen at that place of relation r are
+    ``values[offsets[r]:offsets[r + 1]]`` (int32, ascending); ``offsets`` is int64 (n_rel + 1)."""
+
+    def __init__(self, relations, entities, n_rel, n_ent, device):
+        # sort / unique by the engine's index builder (key1 = relation, key2 = 0, value = entity): rocPRIM on the GPU,
+        # ATen elsewhere; its sorted-key CSR lists only the relations that occur, the counts scatter makes it dense
+        zeros = torch.zeros_like(relations)
+        idx = FilterIndex.from_triples_torch(relations, zeros, entities, device, n_rel, 1, n_ent)
+        counts = torch.zeros(n_rel, dtype=torch.int64, device=idx.offsets.device)
+        if idx.n_keys:
+            counts[idx.keys // KEY2_SPAN] = idx.offsets[1:] - idx.offsets[:-1]
+        self.offsets = torch.zeros(n_rel + 1, dtype=torch.int64, device=counts.device)
+        self.offsets[1:] = torch.cumsum(counts, 0)
+        self.values = idx.targets       # (one zero when the graph is empty: a valid pointer, never inside a segment)
+        self.counts = counts
+
+    def to(self, device):
+        out = object.__new__(_PossibilityIndex)
+        out.offsets, out.values, out.counts = self.offsets.to(device), self.values.to(device), self.counts.to(device)
+        return out
+
+    def lists(self):
+        """{r: ascending list of entities}, every relation a key."""
+        off, val = self.offsets.cpu().tolist(), self.values.cpu().numpy()
+        return {r: val[off[r]:off[r + 1]].tolist() for r in range(len(off) - 1)}
+
+
+def _graph_triples(*kgs):
+    """(heads, tails, relations) of the graphs laid end to end."""
+    kgs = [g for g in kgs if g is not None and g.n_facts > 0]
+    if not kgs:
+        e = torch.zeros(0, dtype=torch.int64)
+        return e, e, e
+    dev = kgs[0].head_idx.device
+    return tuple(cat([getattr(g, nm).to(dev) for g in kgs]) for nm in ('head_idx', 'tail_idx', 'relations'))
+
+
+def get_possible_heads_tails(kg, possible_heads=None, possible_tails=None):
+    """{relation: set of entities seen as its head}, {relation: set seen as its tail} of ``kg``, merged into the two
+    dicts of an earlier call when they are given (sampling.py:556-592).  Only relations that occur are keys.  One
+    sort / unique over the facts instead of three ``.item()`` calls per fact."""
+    out = []
+    for given, ents in ((possible_heads, kg.head_idx), (possible_tails, kg.tail_idx)):
+        if given is None:
+            d = defaultdict(set)
+        else:
+            assert type(given) == dict
+            d = defaultdict(set, given)
+        if kg.n_facts > 0:
+            idx = _PossibilityIndex(kg.relations, ents, kg.n_rel, kg.n_ent, kg.relations.device)
+            for r, vals in idx.lists().items():
+                if vals:
+                    d[r].update(vals)
+        out.append(dict(d))
+    return out[0], out[1]
+
+
+class PositionalNegativeSampler(BernoulliNegativeSampler):
+    """Head or tail (Bernoulli choice of Wang et al. 2014) replaced by an entity that occupies the same place in
+    another fact of the same relation (Socher et al. 2013; sampling.py:330-504).  The possibilities come from ``kg``
+    and ``kg_val``, never from ``kg_test``; a relation without any gets a uniform entity of [0, n_ent).
+
+    ``possible_heads`` / ``possible_tails``: {relation: list}, every relation of range(n_rel) a key, built on first
+    access; ``n_poss_heads`` / ``n_poss_tails``: int64 (n_rel).
+
+    Difference from the reference: within a relation the entities are in ASCENDING id order, where the reference has
+    ``list(set)`` order (an artefact of CPython's hash table).  The draw is uniform over the same set either way, but
+    the same seed picks a different member.
+
+    Random calls, on the batch's device and in the reference's order: ``bernoulli(bern_probs[relations])``, one host
+    read of the number k of heads to replace, ``rand((k,))``, ``rand((B - k,))``; then ``randint(0, n_ent, (k,))`` and
+    ``randint(0, n_ent, (B - k,))`` only when the sampler holds a relation without possibilities.  With
+    ``sync_free = True`` all four arrays are B long and nothing is read back: the same kernel, a different but equally
+    distributed stream."""
+
+    def __init__(self, kg, kg_val=None, kg_test=None):
+        super().__init__(kg, kg_val, kg_test, 1)
+        h, t, r = _graph_triples(kg, kg_val if self.n_facts_val > 0 else None)
+        self.n_rel = kg.n_rel
+        self._index = {}        # device -> (heads index, tails index)
+        self._index[h.device] = (_PossibilityIndex(r, h, self.n_rel, self.n_ent, h.device),
+                                 _PossibilityIndex(r, t, self.n_rel, self.n_ent, h.device))
+        ih, it = self._index[h.device]
+        self.n_poss_heads, self.n_poss_tails = ih.counts.cpu(), it.counts.cpu()
+        # (head and tail of a relation are empty together: both come from the same facts)
+        self._has_empty = bool((self.n_poss_heads == 0).any()) if self.n_rel > 0 else False
+        self._lists = None
+
+    def _indices(self, device):
+        if device not in self._index:
+            ih, it = next(iter(self._index.values()))
+            self._index[device] = (ih.to(device), it.to(device))
+        return self._index[device]
+
+    def _possible(self):
+        if self._lists is None:
+            ih, it = next(iter(self._index.values()))
+            self._lists = (ih.lists(), it.lists())
+        return self._lists
+
+    @property
+    def possible_heads(self):
+        return self._possible()[0]
+
+    @property
+    def possible_tails(self):
+        return self._possible()[1]
+
+    def find_possibilities(self):
+        """(possible_heads, possible_tails, n_poss_heads, n_poss_tails), as the reference returns them."""
+        return self.possible_heads, self.possible_tails, self.n_poss_heads, self.n_poss_tails
+
+    def corrupt_batch(self, heads, tails, relations, n_neg=None):
+        """One negative per fact (``n_neg`` is part of the samplers' interface only, as in the reference)."""
+        device = heads.device
+        assert device == tails.device
+        _hip.require_cuda(heads, tails, relations)
+        B = heads.shape[0]
+        self.bern_probs = self.bern_probs.to(device)
+        mask = bernoulli(self.bern_probs[relations])                # RNG draw #1
+        if self.sync_free:
+            k_h = k_t = B
+        else:
+            k_h = int(mask.sum().item())                            # the reference's sync (:463)
+            k_t = B - k_h
+        u_h = rand((k_h,), device=device)                           # draw #2
+        u_t = rand((k_t,), device=device)                           # draw #3
+        fb_h = fb_t = None
+        if self._has_empty:
+            fb_h = randint(0, self.n_ent, (k_h,), device=device)
+            fb_t = randint(0, self.n_ent, (k_t,), device=device)
+        ih, it = self._indices(device)
+        return _hip_triplet.positional_corrupt(heads, tails, relations, mask.to(torch.uint8), u_h, u_t, fb_h, fb_t,
+                                               ih.offsets, ih.values, it.offsets, it.values, self.n_rel)
+
+    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False):
+        """The reference's driver (host tensors out); ``on_device=True`` keeps the graph's vectors and the negatives
+        on the GPU from end to end (what TripletClassificationEvaluator uses)."""
+        if not on_device:
+            return super().corrupt_kg(batch_size, use_cuda, which)
+        assert which in ['main', 'train', 'test', 'val']
+        kg = self.kg_val if which == 'val' else (self.kg_test if which == 'test' else self.kg)
+        assert kg is not None and kg.n_facts > 0
+        h, t, r = kg.head_idx.cuda(), kg.tail_idx.cuda(), kg.relations.cuda()
+        corr_heads, corr_tails = [], []
+        for lo in range(0, h.shape[0], batch_size):
+            sl = slice(lo, lo + batch_size)
+            neg_heads, neg_tails = self.corrupt_batch(h[sl], t[sl], r[sl], n_neg=1)
+            corr_heads.append(neg_heads)
+            corr_tails.append(neg_tails)
+        return cat(corr_heads), cat(corr_tails)
