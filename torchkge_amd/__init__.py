@@ -11,6 +11,7 @@ from .evaluation import LinkPredictionEvaluator, RelationPredictionEvaluator, cl
 from .inference import EntityInference
 from .models import TransEModel, TransHModel, TransDModel, TorusEModel, TransRModel, DistMultModel, ComplExModel, RESCALModel, HolEModel, AnalogyModel, ConvKBModel
 from .sampling import BernoulliNegativeSampler, UniformNegativeSampler
+from .determinism import set_deterministic, is_deterministic, deterministic
 
 
 # Names of the reference that this package does not provide at its top level: a clear error

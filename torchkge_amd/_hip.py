@@ -324,8 +324,11 @@ def sort_perm(keys, n_keys):
 def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
     """Returns a list of gradient tensors (or None) matching ``tables``.  Large
     batches take the sorted reduction (per-triple gradient rows, then one atomic
-    row-add per run of equal target rows) instead of one atomic per element."""
+    row-add per run of equal target rows) instead of one atomic per element.
+    In deterministic mode (torchkge_amd.determinism) EVERY batch takes the row mode
+    and the rows are summed by kge_segment_sum_ordered: no float atomic, a fixed order."""
     lib = load_library()
+    det = _hip_det.is_deterministic()
     tabs = [f32c(x) for x in tables] + [None] * (4 - len(tables))
     grads = [torch.zeros_like(x) for x in tabs[:len(tables)]] + [None] * (4 - len(tables))
     go = f32c(grad_out)
@@ -335,9 +338,9 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
         return _rescal_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
     if kind == TRANSR:
         return _transr_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
-    # (TorusE: always the row mode -- no per-element float atomics; a batch whose rows fit one 32-entry chunk per stream
-    # of kge_segment_sum_rows gets the same bits on every run)
-    if B < BWD_SORTED_MIN_BATCH and kind < TORUSE_L1:
+    # (TorusE: always the row mode -- no per-element float atomics; the same bits on every run need the deterministic
+    # mode, torchkge_amd.set_deterministic(True), which sums the rows through kge_segment_sum_ordered)
+    if B < BWD_SORTED_MIN_BATCH and kind < TORUSE_L1 and (not det or B == 0):
         with _on(dev):
             _check(lib.kge_score_triples_bwd(kind, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
                                              d_ent, d_rel, _p(h), _p(t), _p(r), B, _p(go),
@@ -358,7 +361,8 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
             g = grads[ti]
             k0, n0, k1, n1 = (h, B, t, B) if key == 'ht' else (r, B, None, 0)
             if key not in perms:    # the ids (they index g's rows) in sorted order: runs of equal target rows
-                if BWD_PERM == 'sort':
+                # (deterministic mode: never the counting sort, whose order inside a run is the arrival order of its atomics)
+                if BWD_PERM == 'sort' or (det and BWD_PERM == 'count'):
                     # device radix sort of (id, position) over the id's bits (kge_key_sort): ~4x cheaper than the counting
                     # sort below at B = 32768, whose wave-aggregated atomics walk up to 64 distinct ids per wavefront
                     bits = max(1, int(g.shape[0] - 1).bit_length())
@@ -369,7 +373,7 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
                     perm = torch.empty(n0 + n1, dtype=torch.int64, device=dev)
                     _check(lib.kge_key_sort(_p(k0), n0, _p(k1), n1, bits, _p(perm), _p(ws), nb, _stream()), 'kge_key_sort')
                 elif BWD_PERM == 'torch':
-                    perm = torch.sort(k0 if k1 is None else torch.cat([k0, k1])).indices
+                    perm = torch.sort(k0 if k1 is None else torch.cat([k0, k1]), stable=det).indices
                 else:               # counting sort: hist, cumsum, scatter
                     cnt = torch.zeros(2, g.shape[0], dtype=torch.int32, device=dev)
                     _check(lib.kge_key_hist(_p(k0), n0, _p(k1), n1, _p(cnt[0]), _stream()), 'kge_key_hist')
@@ -378,9 +382,8 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
                     _check(lib.kge_key_scatter(_p(k0), n0, _p(k1), n1, _p(off), _p(cnt[1]), _p(perm), _stream()),
                            'kge_key_scatter')
                 perms[key] = perm
-            _check(lib.kge_segment_sum_rows(rows.data_ptr() + s0 * B * d_ent * 4, d_ent, g.shape[1], _p(k0), n0,
-                                            _p(k1), n1, _p(perms[key]), _p(g), g.stride(0), _stream()),
-                   'kge_segment_sum_rows')
+            _hip_det.segment_sum(rows.data_ptr() + s0 * B * d_ent * 4, d_ent, g.shape[1], k0, n0, k1, n1, perms[key], g,
+                                 g.stride(0), det)
     return [g if n else None for g, n in zip(grads[:len(tables)], needs)]
 
 
@@ -402,7 +405,7 @@ def _key_perm(k0, k1, n_keys):
 
 
 def _rescal_bwd(tabs, d, d_rel, h, t, r, go, grads, needs):
-    """RESCAL's backward: entity gradients through the row mode + kge_segment_sum_rows, rel_mat's by the relation-grouped
+    """RESCAL's backward: entity gradients through the row mode + _hip_det.segment_sum, rel_mat's by the relation-grouped
     reduction kge_rescal_rel_grad (sorted by relation: no atomics on rel_mat, the same bits on every run)."""
     lib = load_library()
     B, dev = h.shape[0], h.device
@@ -413,8 +416,7 @@ def _rescal_bwd(tabs, d, d_rel, h, t, r, go, grads, needs):
         if needs[0]:
             g = grads[0]
             perm = _key_perm(h, t, g.shape[0])
-            _check(lib.kge_segment_sum_rows(_p(rows), d, d, _p(h), B, _p(t), B, _p(perm), _p(g), g.stride(0), _stream()),
-                   'kge_segment_sum_rows')
+            _hip_det.segment_sum(rows, d, d, h, B, t, B, perm, g, g.stride(0))
         if needs[1]:
             g = grads[1]
             perm = _key_perm(r, None, g.shape[0])
@@ -424,7 +426,7 @@ def _rescal_bwd(tabs, d, d_rel, h, t, r, go, grads, needs):
 
 
 def _transr_bwd(tabs, d_e, d_r, h, t, r, go, grads, needs):
-    """TransR's backward: entity and rel_emb gradients through the row mode + kge_segment_sum_rows, proj_mat's by the
+    """TransR's backward: entity and rel_emb gradients through the row mode + _hip_det.segment_sum, proj_mat's by the
     relation-grouped reduction kge_transr_rel_grad (sorted by relation: no atomics on proj_mat, the same bits on every
     run)."""
     lib = load_library()
@@ -437,15 +439,13 @@ def _transr_bwd(tabs, d_e, d_r, h, t, r, go, grads, needs):
         if needs[0]:
             g = grads[0]
             perm = _key_perm(h, t, g.shape[0])
-            _check(lib.kge_segment_sum_rows(_p(rows), ld, d_e, _p(h), B, _p(t), B, _p(perm), _p(g), g.stride(0), _stream()),
-                   'kge_segment_sum_rows')
+            _hip_det.segment_sum(rows, ld, d_e, h, B, t, B, perm, g, g.stride(0))
         if needs[1] or needs[2]:
             perm = _key_perm(r, None, grads[1].shape[0])
             gp, vp = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
             if needs[1]:
                 g = grads[1]
-                _check(lib.kge_segment_sum_rows(gp, ld, d_r, _p(r), B, None, 0, _p(perm), _p(g), g.stride(0), _stream()),
-                       'kge_segment_sum_rows')
+                _hip_det.segment_sum(gp, ld, d_r, r, B, None, 0, perm, g, g.stride(0))
             if needs[2]:
                 g = grads[2]
                 _check(lib.kge_transr_rel_grad(gp, ld, vp, ld, d_r, d_e, _p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
@@ -1673,3 +1673,8 @@ def corrupt_scatter(heads, tails, mask_u8, draws_h, draws_t, n_neg):
                                        B, n_neg, _p(nh), _p(nt), _p(ws), _stream()),
                'kge_corrupt_scatter')
     return nh, nt
+
+
+# the deterministic reduction's binding (include/kge_hip_det.h): it takes its ctypes helpers from this module, so it
+# is imported once everything above exists
+from . import _hip_det  # noqa: E402

@@ -4,7 +4,7 @@ wrappers.  The symbols live in the library _hip.load_library() returns; their pr
 table of their own because include/kge_hip.h, kge_lp_desc and its ABI version do not change for this model."""
 import torch
 
-from . import _hip
+from . import _hip, _hip_det
 from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, i64c, require_cuda
 
 SIDE_REL = 5        # KGE_ANALOGY_SIDE_REL
@@ -123,8 +123,8 @@ _SEG_MAX = 1024     # widest row kge_segment_sum_rows reduces in one call
 
 def score_triples_bwd(ent, rel, h, t, r, grad_out, needs):
     """Gradients of the six tables (None where ``needs`` says so): per-triple gradient rows in packed layout, reduced
-    per entity / relation by kge_key_sort + kge_segment_sum_rows into packed gradients whose column slices are the
-    tables' -- no per-element atomics."""
+    per entity / relation by kge_key_sort + _hip_det.segment_sum (kge_segment_sum_rows, or kge_segment_sum_ordered in
+    deterministic mode) into packed gradients whose column slices are the tables' -- no per-element atomics."""
     lib = load_library()
     ent, rel = _prep(ent), _prep(rel)
     d_sc, d_c = _dims(ent)
@@ -146,8 +146,8 @@ def score_triples_bwd(ent, rel, h, t, r, grad_out, needs):
                 perm = _hip._key_perm(k0, k1, max(n_rows, 1))
                 for c0 in range(0, K, _SEG_MAX):
                     w = min(_SEG_MAX, K - c0)
-                    _check(lib.kge_segment_sum_rows(src.data_ptr() + 4 * c0, K, w, _p(k0), B, _p(k1), 0 if k1 is None else B,
-                                                    _p(perm), g.data_ptr() + 4 * c0, K, _stream()), 'kge_segment_sum_rows')
+                    _hip_det.segment_sum(src.data_ptr() + 4 * c0, K, w, k0, B, k1, 0 if k1 is None else B, perm,
+                                         g.data_ptr() + 4 * c0, K)
             parts = (g[:, :d_sc], g[:, d_sc:d_sc + d_c], g[:, d_sc + d_c:])
             for j in range(3):
                 out[first + j] = parts[j] if needs[first + j] else None

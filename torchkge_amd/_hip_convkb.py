@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from . import _hip
+from . import _hip, _hip_det
 from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, i64c, require_cuda
 
 MAX_DIM = 512       # KGE_CONVKB_MAX_DIM: of each of d (emb_dim) and F (n_filters)
@@ -204,7 +204,8 @@ def score_triples(E, R, ws, d, F, h, t, r):
 def score_triples_bwd(E, R, ws, d, F, h, t, r, s, grad_out, needs):
     """Gradients of (ent_emb, rel_emb, conv weight (F, 3, 1), conv bias, linear weight (2, F d), linear bias), None
     where ``needs`` says so.  Entity / relation gradients: per-triple rows reduced by kge_key_sort +
-    kge_segment_sum_rows (no per-element atomics); the four layer gradients: one reduction kernel over the batch."""
+    _hip_det.segment_sum (kge_segment_sum_rows, or kge_segment_sum_ordered in deterministic mode; no per-element
+    atomics); the four layer gradients: one reduction kernel over the batch (fixed-shape trees: the same bits on every run)."""
     lib = load_library()
     E, R = _rows(E), _rows(R)
     h, t, r = i64c(h), i64c(t), i64c(r)
@@ -231,8 +232,7 @@ def score_triples_bwd(E, R, ws, d, F, h, t, r, s, grad_out, needs):
             if B:
                 src = rows if pos == 0 else rows[2 * B:]
                 perm = _hip._key_perm(k0, k1, max(n_rows, 1))
-                _check(lib.kge_segment_sum_rows(_p(src), d, d, _p(k0), B, _p(k1), 0 if k1 is None else B, _p(perm),
-                                                _p(grad), d, _stream()), 'kge_segment_sum_rows')
+                _hip_det.segment_sum(src, d, d, k0, B, k1, 0 if k1 is None else B, perm, grad, d)
             out[pos] = grad
     if want_par:
         for pos, val in ((2, dw), (3, dcb), (4, dL), (5, dlb)):
