@@ -15,13 +15,13 @@ from .determinism import set_deterministic, is_deterministic, deterministic
 
 
 # Names of the reference that this package does not provide at its top level: a clear error
-# instead of an AttributeError, so a ported script says what to do.  RelationInference is out of scope (SURVEY.md
-# section 8); the triplet-classification pair is provided by its submodules.
+# instead of an AttributeError, so a ported script says what to do.  RelationInference and the
+# triplet-classification pair are provided by their submodules.
 _NOT_PROVIDED = {
     'TripletClassificationEvaluator': 'not at the top level yet -- import it from torchkge_amd.evaluation, the path the reference\'s '
                                       'tutorial uses',
     'PositionalNegativeSampler': 'not at the top level yet -- import it from torchkge_amd.sampling, the path the reference\'s tests use',
-    'RelationInference': 'use RelationPredictionEvaluator, or EntityInference for missing entities',
+    'RelationInference': 'not at the top level yet -- import it from torchkge_amd.inference, the module the reference keeps it in',
 }
 
 

@@ -1,4 +1,4 @@
-// Exclusive prefix count of a byte mask, the scheme the two corruption kernels share (corrupt.hip, triplet.hip): every
+// Exclusive prefix count of a byte mask, the scheme the corruption kernels share (corrupt.hip, triplet.hip, relation_corrupt.hip): every
 // position of a batch learns how many non-zero mask bytes lie before it, which is its index into the draw arrays.
 //
 //   mask_count_kernel    one int32 count per block of MS_CB positions

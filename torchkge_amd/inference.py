@@ -1,7 +1,8 @@
 # -*- coding: utf-8 -*-
-"""Top-k inference of missing entities with the reference's
-interface (torchkge/inference.py:156-250): ``EntityInference(model,
-known_entities, known_relations, top_k=1, missing='tails', dictionary=None)``,
+"""Top-k inference of missing entities and missing relations with the reference's
+interface (torchkge/inference.py:78-250): ``EntityInference(model,
+known_entities, known_relations, top_k=1, missing='tails', dictionary=None)`` and
+``RelationInference(model, entities1, entities2, top_k=1, dictionary=None)``,
 ``.evaluate(b_size, verbose)`` filling ``.predictions`` (n, top_k) long and
 ``.scores`` (n, top_k) float on the CPU.
 
@@ -11,6 +12,8 @@ Same score kernels as link prediction; the reference's full
 not reproduced: scores are stored by slice (the reference indexes
 ``self.scores[i*b, (i+1)*b]`` with a tuple), and ``missing='heads'`` works (the
 reference derives the batch size from the empty head index).
+``RelationInference`` ranks the (b, n_rel) relation scores every model already
+computes on the HIP path with one kge_topk_chunk call per batch.
 """
 import torch
 from tqdm.autonotebook import tqdm
@@ -180,6 +183,85 @@ class EntityInference(object):
                 vals.append(v)
         self.predictions = torch.cat(preds).cpu() if preds else self.predictions
         self.scores = torch.cat(vals).cpu() if vals else self.scores
+
+
+class RelationInference(object):
+    """Infer the top_k most plausible relations between two known entities (inference.py:78-154).
+
+    Per batch: ``model.inference_prepare_candidates(e1, e2, empty, entities=False)`` and
+    ``model.inference_scoring_function(h, t, candidates)`` give the (b, n_rel) scores of every relation -- each model's
+    own HIP relation-score path, the one ``RelationPredictionEvaluator`` ranks on; then ONE ``kge_topk_chunk`` call
+    masks the pair's known relations (``dictionary``: a ``{(e1, e2): [relations]}`` mapping such as
+    ``kg.dict_of_rels``, or a prebuilt index with ``.lookup``) and keeps the k = min(top_k, n_rel) best, where the
+    reference filters, sorts the whole matrix and slices (:145-151).  Order: score descending, relation id ascending
+    (the reference's sort leaves ties unspecified); a masked relation scores -inf and comes last.
+
+    ``topk`` is the reference's attribute name, ``top_k`` an alias.  One reference bug is not reproduced: the reference
+    stores ``self.scores[i * b_size, (i + 1) * b_size]`` with a tuple and raises IndexError on the first batch; here
+    scores are stored by slice.  The model must be on ``cuda``; a row-sharded model is refused by the models' own
+    check inside ``inference_prepare_candidates``."""
+
+    def __init__(self, model, entities1, entities2, top_k=1, dictionary=None):
+        self.model = model
+        self.entities1 = entities1
+        self.entities2 = entities2
+        self.topk = top_k
+        self.dictionary = dictionary
+        self.predictions = torch.empty(size=(len(entities1), top_k)).long()
+        self.scores = torch.empty(size=(len(entities2), top_k))
+
+    @property
+    def top_k(self):
+        return self.topk
+
+    @top_k.setter
+    def top_k(self, value):
+        self.topk = value
+
+    def evaluate(self, b_size, verbose=True):
+        from .filter_index import filter_index_for
+        dev = _device_of(self.model)
+        model = self.model
+        prepare = getattr(model, 'lp_eval_prepare', None)
+        if prepare is not None:
+            prepare()
+        ents1, ents2 = self.entities1.to(dev), self.entities2.to(dev)
+        none = torch.zeros(0, dtype=torch.long, device=dev)
+        k = min(self.topk, model.n_rel)
+        index = None
+        if self.dictionary is not None:
+            index = self.dictionary if hasattr(self.dictionary, 'lookup') else filter_index_for(self.dictionary, dev)
+        preds, vals = [], []
+        n_batches = get_n_batches(len(ents1), b_size)
+        session = model.lp_session() if hasattr(model, 'lp_session') else None
+        with torch.no_grad():
+            if session is not None:
+                session.__enter__()
+            try:
+                for i in tqdm(range(n_batches), total=n_batches, unit='batch', disable=(not verbose), desc='Inference'):
+                    sl = slice(i * b_size, (i + 1) * b_size)
+                    e1, e2 = ents1[sl], ents2[sl]
+                    b = e1.shape[0]
+                    h_emb, t_emb, _, candidates = model.inference_prepare_candidates(e1, e2, none, entities=False)
+                    scores = model.inference_scoring_function(h_emb, t_emb, candidates)
+                    scores = _hip.f32c(scores)          # (b, n_rel), this batch's own tensor: the mask is written in place
+                    seg_lo = seg_hi = targets = None
+                    if index is not None:
+                        seg_lo, seg_hi = index.lookup(e1, e2)
+                        targets = index.targets
+                    v = torch.empty(b, k, dtype=torch.float32, device=dev)
+                    ix = torch.empty(b, k, dtype=torch.int64, device=dev)
+                    _hip.topk_chunk(scores, 0, k, v, ix, 0, seg_lo, seg_hi, targets)
+                    preds.append(ix)
+                    vals.append(v)
+            finally:
+                if session is not None:
+                    session.__exit__(None, None, None)
+        if preds:
+            self.predictions, self.scores = torch.cat(preds).cpu(), torch.cat(vals).cpu()
+        else:
+            self.predictions = torch.empty(size=(0, k)).long()
+            self.scores = torch.empty(size=(0, k))
 
 
 def _gather_partials(pv, pi, k, n_local, n_ent, world, group):

@@ -1,10 +1,11 @@
 # -*- coding: utf-8 -*-
-"""Negative samplers with the reference's interface (torchkge/sampling.py:16-504, :556-592):
+"""Negative samplers with the reference's interface (torchkge/sampling.py:16-592):
 ``NegativeSampler``, ``UniformNegativeSampler``, ``BernoulliNegativeSampler``
 (``.bern_probs``, ``.corrupt_batch(heads, tails, relations, n_neg=None)``,
 ``.corrupt_kg(batch_size, use_cuda, which)``), ``PositionalNegativeSampler``
-(``.possible_heads / .possible_tails / .n_poss_heads / .n_poss_tails``) and
-``get_possible_heads_tails``.
+(``.possible_heads / .possible_tails / .n_poss_heads / .n_poss_tails``),
+``BernoulliRelationNegativeSampler`` (``.bern_probs``, ``.rel_share``; three
+vectors out) and ``get_possible_heads_tails``.
 
 The random draws are issued with the same torch RNG calls, in the same order
 and with the same sizes as the reference (bernoulli, randint(k),
@@ -17,13 +18,17 @@ price of a different (equally distributed) random stream.
 The positional sampler keeps its two possibility indices as dense per-relation
 CSRs on the device and corrupts a batch in one gather (kge_positional_corrupt):
 no Python loop over the facts of the graph or the elements of a batch.
+
+The relation-corrupting sampler's three masked index-puts are one HIP entry
+point as well (kge_relation_corrupt, include/kge_hip_relation.h): two dependent
+prefix counts and one scatter.
 """
 from collections import defaultdict
 
 import torch
 from torch import bernoulli, cat, ones, rand, randint, tensor
 
-from . import _hip, _hip_triplet
+from . import _hip, _hip_relation, _hip_triplet
 from .exceptions import NotYetImplementedError
 from .filter_index import FilterIndex, KEY2_SPAN
 from .utils.data import DataLoader
@@ -276,3 +281,94 @@ class PositionalNegativeSampler(BernoulliNegativeSampler):
             corr_heads.append(neg_heads)
             corr_tails.append(neg_tails)
         return cat(corr_heads), cat(corr_tails)
+
+
+class BernoulliRelationNegativeSampler(NegativeSampler):
+    """Corrupts either the relation of a fact or, with the Bernoulli choice of Wang et al. 2014, its head or its tail
+    (sampling.py:507-553).  ``corrupt_batch`` returns ``(neg_heads, neg_tails, neg_rels)``, int64 on the batch's device.
+
+    The reference's quirks are kept:
+      * ``rel_share`` is the probability that an ENTITY is corrupted (the reference's own comment: "if 1 then entities
+        are corrupted"), so the relation is corrupted with probability ``1 - rel_share``;
+      * every draw is ``randint(1, .)``: neither entity 0 nor relation 0 is ever drawn;
+      * the drawn relation may equal the true one;
+      * a graph of one relation raises torch's own error from ``randint(1, 1)``.
+
+    Two deliberate differences:
+      * ``n_neg`` is honoured: the batch is repeated ``n_neg`` times as in ``BernoulliNegativeSampler`` and 3 x
+        (B * n_neg) ids come back (the reference ignores it and returns B negatives);
+      * ``corrupt_kg`` returns three vectors (the reference inherits a ``corrupt_kg`` that unpacks two and raises);
+        ``on_device=True`` keeps the graph's vectors and the negatives on the GPU, as in ``PositionalNegativeSampler``.
+
+    Random calls, on the batch's device, in the reference's order and with its sizes (n = B * n_neg):
+    ``bernoulli(rel_share * ones(n))``, one host read of its sum k, ``randint(1, n_rel, (n - k,))``,
+    ``bernoulli(bern_probs[relations.repeat(n_neg)[mask == 1]])``, one host read of its sum q,
+    ``randint(1, n_ent, (q,))``, ``randint(1, n_ent, (k - q,))``; then one kge_relation_corrupt.  With
+    ``sync_free = True`` all five arrays are n long and nothing is read back: the head mask is drawn for every position
+    from ``bern_probs[relations.repeat(n_neg)]`` and the entity positions' entries are moved to the front on the device
+    (the kernel consumes it compactly), so every position still uses the probability of its own relation.  The same
+    kernel, a different but equally distributed stream."""
+
+    def __init__(self, kg, kg_val=None, kg_test=None, n_neg=1, rel_share=.33):
+        super().__init__(kg, kg_val, kg_test, n_neg)
+        self.n_rel = kg.n_rel
+        self.bern_probs = self.evaluate_probabilities()
+        self.rel_share = rel_share
+
+    evaluate_probabilities = BernoulliNegativeSampler.evaluate_probabilities
+
+    def corrupt_batch(self, heads, tails, relations, n_neg=None):
+        if n_neg is None:
+            n_neg = self.n_neg
+        device = heads.device
+        assert device == tails.device
+        _hip.require_cuda(heads, tails, relations)
+        n = heads.shape[0] * n_neg
+        self.bern_probs = self.bern_probs.to(device)
+        rels_rep = relations.repeat(n_neg)
+        mask_ent = bernoulli(self.rel_share * ones(n, device=device))            # RNG draw #1: 1 = an entity is corrupted
+        if self.sync_free:
+            draws_r = randint(1, self.n_rel, (n,), device=device)
+            side = bernoulli(self.bern_probs[rels_rep])         # the head / tail choice of position j, were it an entity's
+            # the kernel reads the choice of the p-th ENTITY position at mask_head[p]: move every position's own choice
+            # there (the other positions' behind them, a permutation) -- a position keeps the probability of ITS relation
+            ones_upto = torch.cumsum(mask_ent, 0).long()
+            at = torch.arange(n, device=device)
+            slot = torch.where(mask_ent != 0, ones_upto - 1, ones_upto[-1:] + at - ones_upto) if n else at
+            mask_head = torch.empty_like(side).scatter_(0, slot, side)
+            draws_h = randint(1, self.n_ent, (n,), device=device)
+            draws_t = randint(1, self.n_ent, (n,), device=device)
+            # (the draws are i.i.d.: position j consumes the entries its two prefix counts name, any fixed assignment is
+            # equally distributed)
+        else:
+            k = int(mask_ent.sum().item())                                       # the reference's sync (:538)
+            draws_r = randint(1, self.n_rel, (n - k,), device=device)            # draw #2
+            mask_head = bernoulli(self.bern_probs[rels_rep[mask_ent == 1]])      # draw #3
+            q = int(mask_head.sum().item())                                      # the reference's sync (:548)
+            draws_h = randint(1, self.n_ent, (q,), device=device)                # draw #4
+            draws_t = randint(1, self.n_ent, (k - q,), device=device)            # draw #5
+        return _hip_relation.relation_corrupt(heads, tails, relations, mask_ent.to(torch.uint8), mask_head.to(torch.uint8),
+                                              draws_r, draws_h, draws_t, n_neg)
+
+    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False):
+        """(neg_heads, neg_tails, neg_rels) of a whole graph, batch by batch with n_neg = 1: host tensors, or with
+        ``on_device=True`` device tensors from vectors that never leave the GPU."""
+        assert which in ['main', 'train', 'test', 'val']
+        if which == 'val':
+            assert self.n_facts_val > 0
+        if which == 'test':
+            assert self.n_facts_test > 0
+        kg = self.kg_val if which == 'val' else (self.kg_test if which == 'test' else self.kg)
+        out = ([], [], [])
+        if on_device:
+            h, t, r = kg.head_idx.cuda(), kg.tail_idx.cuda(), kg.relations.cuda()
+            batches = ((h[lo:lo + batch_size], t[lo:lo + batch_size], r[lo:lo + batch_size])
+                       for lo in range(0, h.shape[0], batch_size))
+        else:
+            batches = DataLoader(kg, batch_size=batch_size, use_cuda='batch' if use_cuda else None)
+        for batch in batches:
+            for lst, neg in zip(out, self.corrupt_batch(batch[0], batch[1], batch[2], n_neg=1)):
+                lst.append(neg)
+        empty = torch.zeros(0, dtype=torch.int64)
+        out = tuple(cat(lst).long() if lst else empty for lst in out)
+        return out if on_device or not use_cuda else tuple(x.cpu() for x in out)
