@@ -209,6 +209,25 @@ def load_library():
     return lib
 
 
+_BOUND = {}     # id(signature table of a satellite header) -> the library handle it was bound to
+
+
+def bind(signatures, sizes=(), size_argtypes=(_i64,), size_restype=_i64):
+    """load_library() with the prototypes of one more header bound, once per library handle: ``signatures`` (name ->
+    argtypes; they return int) and the size queries ``sizes`` (names; one prototype for all).  The headers beside
+    include/kge_hip.h declare symbols of the same library; this is the load_library() of their modules."""
+    lib = load_library()
+    if _BOUND.get(id(signatures)) is not lib:
+        for name, args in signatures.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = args, _int
+        for name in sizes:
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = list(size_argtypes), size_restype
+        _BOUND[id(signatures)] = lib
+    return lib
+
+
 def _check(rc, name):
     if rc != 0:
         if rc < 0:
@@ -258,6 +277,15 @@ def f32c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def f32rows(x):
+    """A float32 matrix whose rows are contiguous; the row stride is free (the kernels take a leading dimension)."""
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise RuntimeError('torchkge_amd: expected a float32 matrix, got %s of %d dimensions' % (x.dtype, x.dim()))
+    if x.shape[1] == 0 or (x.stride(1) == 1 and x.stride(0) >= x.shape[1]):
+        return x
+    return x.contiguous()
+
+
 def i64c(t):
     if t.dtype != torch.int64:
         t = t.long()
@@ -292,105 +320,30 @@ _BWD_STREAMS = {
     HOLE: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
     TORUSE_L1: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')], TORUSE_TORUS_L1: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
     TORUSE_TORUS_L2: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')], TORUSE_TORUS_EL2: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
-    # rel_mat's gradient (d^2 per triple) is reduced per relation from streams 2 / 3 (kge_rescal_rel_grad)
     RESCAL: [(0, 0, 2, 'ht')],
+    TRANSR: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],      # (rel_emb's rows are the U rows of proj_mat's reduction)
 }
+# the kinds whose last table holds a matrix per relation: (table, entry point, its arguments between the row streams and
+# the ids).  The matrix gradient is reduced per relation from the rows U, V of streams 2 / 3 (sorted by relation: no
+# atomics, the same bits on every run); these kinds write four streams and have no atomic mode.
+_BWD_REL_TAIL = {
+    RESCAL: (1, 'kge_rescal_rel_grad', lambda U, V, ld, d_ent, d_rel: (U, V, ld, d_ent)),
+    TRANSR: (2, 'kge_transr_rel_grad', lambda U, V, ld, d_ent, d_rel: (U, ld, V, ld, d_rel, d_ent)),
+}
+# the kinds whose backward kernel can add element by element into the tables (no rows): the small-batch mode.  Not
+# TorusE: no per-element float atomics there at any batch size
+_BWD_ATOMIC = frozenset(k for k in range(TORUSE_L1) if k not in _BWD_REL_TAIL)
 BWD_SORTED_MIN_BATCH = 2048     # below this the plain atomic scatter is as fast
 
 
 _KEY_SORT_WS = {}
-BWD_PERM = os.environ.get('KGE_BWD_PERM', 'sort')      # 'sort' (kge_key_sort) | 'torch' (torch.sort) | 'count' (kge_key_hist / _scatter): how score_triples_bwd orders the ids of a large batch
-
-
-def sort_perm(keys, n_keys):
-    """Stable ascending order of small non-negative int64 keys (< n_keys <= 2**32): perm[j] = position of the j-th
-    key (kge_key_sort: one device radix sort of (key, position) pairs)."""
-    lib = load_library()
-    require_cuda(keys)
-    keys = i64c(keys)
-    n, dev = keys.shape[0], keys.device
-    bits = max(1, int(n_keys - 1).bit_length())
-    if bits > 32:
-        raise RuntimeError('sort_perm: keys need more than 32 bits')
-    nb = int(lib.kge_key_sort_ws_bytes(n, bits))
-    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
-    perm = torch.empty(n, dtype=torch.int64, device=dev)
-    if n > 0:
-        with _on(dev):
-            _check(lib.kge_key_sort(_p(keys), n, None, 0, bits, _p(perm), _p(ws), nb, _stream()), 'kge_key_sort')
-    return perm
-
-
-def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
-    """Returns a list of gradient tensors (or None) matching ``tables``.  Large
-    batches take the sorted reduction (per-triple gradient rows, then one atomic
-    row-add per run of equal target rows) instead of one atomic per element.
-    In deterministic mode (torchkge_amd.determinism) EVERY batch takes the row mode
-    and the rows are summed by kge_segment_sum_ordered: no float atomic, a fixed order."""
-    lib = load_library()
-    det = _hip_det.is_deterministic()
-    tabs = [f32c(x) for x in tables] + [None] * (4 - len(tables))
-    grads = [torch.zeros_like(x) for x in tabs[:len(tables)]] + [None] * (4 - len(tables))
-    go = f32c(grad_out)
-    B = h.shape[0]
-    dev = h.device
-    if kind == RESCAL:
-        return _rescal_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
-    if kind == TRANSR:
-        return _transr_bwd(tabs, d_ent, d_rel, h, t, r, go, grads, needs)
-    # (TorusE: always the row mode -- no per-element float atomics; the same bits on every run need the deterministic
-    # mode, torchkge_amd.set_deterministic(True), which sums the rows through kge_segment_sum_ordered)
-    if B < BWD_SORTED_MIN_BATCH and kind < TORUSE_L1 and (not det or B == 0):
-        with _on(dev):
-            _check(lib.kge_score_triples_bwd(kind, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
-                                             d_ent, d_rel, _p(h), _p(t), _p(r), B, _p(go),
-                                             _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(grads[3]),
-                                             None, 0, _stream()), 'kge_score_triples_bwd')
-        return [g if n else None for g, n in zip(grads[:len(tables)], needs)]
-    streams = _BWD_STREAMS[kind]
-    n_streams = max(s0 + ns for _, s0, ns, _ in streams)
-    rows = torch.empty(n_streams * B * d_ent, dtype=torch.float32, device=dev)
-    with _on(dev):
-        _check(lib.kge_score_triples_bwd(kind, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
-                                         d_ent, d_rel, _p(h), _p(t), _p(r), B, _p(go), None, None, None, None,
-                                         _p(rows), d_ent, _stream()), 'kge_score_triples_bwd')
-        perms = {}
-        for ti, s0, ns, key in streams:
-            if not needs[ti]:
-                continue
-            g = grads[ti]
-            k0, n0, k1, n1 = (h, B, t, B) if key == 'ht' else (r, B, None, 0)
-            if key not in perms:    # the ids (they index g's rows) in sorted order: runs of equal target rows
-                # (deterministic mode: never the counting sort, whose order inside a run is the arrival order of its atomics)
-                if BWD_PERM == 'sort' or (det and BWD_PERM == 'count'):
-                    # device radix sort of (id, position) over the id's bits (kge_key_sort): ~4x cheaper than the counting
-                    # sort below at B = 32768, whose wave-aggregated atomics walk up to 64 distinct ids per wavefront
-                    bits = max(1, int(g.shape[0] - 1).bit_length())
-                    nb = _KEY_SORT_WS.get((n0 + n1, bits))
-                    if nb is None:      # (the size query walks rocPRIM's host-side configuration: once per shape)
-                        nb = _KEY_SORT_WS[(n0 + n1, bits)] = int(lib.kge_key_sort_ws_bytes(n0 + n1, bits))
-                    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-                    perm = torch.empty(n0 + n1, dtype=torch.int64, device=dev)
-                    _check(lib.kge_key_sort(_p(k0), n0, _p(k1), n1, bits, _p(perm), _p(ws), nb, _stream()), 'kge_key_sort')
-                elif BWD_PERM == 'torch':
-                    perm = torch.sort(k0 if k1 is None else torch.cat([k0, k1]), stable=det).indices
-                else:               # counting sort: hist, cumsum, scatter
-                    cnt = torch.zeros(2, g.shape[0], dtype=torch.int32, device=dev)
-                    _check(lib.kge_key_hist(_p(k0), n0, _p(k1), n1, _p(cnt[0]), _stream()), 'kge_key_hist')
-                    off = torch.cumsum(cnt[0], 0, dtype=torch.int64) - cnt[0]
-                    perm = torch.empty(n0 + n1, dtype=torch.int64, device=dev)
-                    _check(lib.kge_key_scatter(_p(k0), n0, _p(k1), n1, _p(off), _p(cnt[1]), _p(perm), _stream()),
-                           'kge_key_scatter')
-                perms[key] = perm
-            _hip_det.segment_sum(rows.data_ptr() + s0 * B * d_ent * 4, d_ent, g.shape[1], k0, n0, k1, n1, perms[key], g,
-                                 g.stride(0), det)
-    return [g if n else None for g, n in zip(grads[:len(tables)], needs)]
 
 
 def _key_perm(k0, k1, n_keys):
-    """kge_key_sort of [k0 | k1] (k1 may be None): stable ascending order of the ids < n_keys.  Workspace sizes are
-    cached per shape (the size query walks rocPRIM's host-side configuration); nothing here synchronises the host, so it
-    runs inside a graph capture."""
+    """kge_key_sort of [k0 | k1] (k1 may be None): stable ascending order of the ids < n_keys -- a device radix sort of
+    (id, position) pairs over the ids' bits.  Workspace sizes are cached per shape (the size query walks rocPRIM's
+    host-side configuration); nothing here synchronises the host, so it runs inside a graph capture.  The caller has made
+    the keys' device current."""
     lib = load_library()
     n0, n1 = k0.shape[0], (0 if k1 is None else k1.shape[0])
     bits = max(1, int(n_keys - 1).bit_length())
@@ -404,53 +357,61 @@ def _key_perm(k0, k1, n_keys):
     return perm
 
 
-def _rescal_bwd(tabs, d, d_rel, h, t, r, go, grads, needs):
-    """RESCAL's backward: entity gradients through the row mode + _hip_det.segment_sum, rel_mat's by the relation-grouped
-    reduction kge_rescal_rel_grad (sorted by relation: no atomics on rel_mat, the same bits on every run)."""
-    lib = load_library()
-    B, dev = h.shape[0], h.device
-    rows = torch.empty(4 * B * d, dtype=torch.float32, device=dev)
-    with _on(dev):
-        _check(lib.kge_score_triples_bwd(RESCAL, _p(tabs[0]), _p(tabs[1]), None, None, d, d_rel, _p(h), _p(t), _p(r), B,
-                                         _p(go), None, None, None, None, _p(rows), d, _stream()), 'kge_score_triples_bwd')
-        if needs[0]:
-            g = grads[0]
-            perm = _key_perm(h, t, g.shape[0])
-            _hip_det.segment_sum(rows, d, d, h, B, t, B, perm, g, g.stride(0))
-        if needs[1]:
-            g = grads[1]
-            perm = _key_perm(r, None, g.shape[0])
-            _check(lib.kge_rescal_rel_grad(rows.data_ptr() + 2 * B * d * 4, rows.data_ptr() + 3 * B * d * 4, d, d, _p(r),
-                                           _p(perm), B, g.shape[0], _p(g), g.stride(0), _stream()), 'kge_rescal_rel_grad')
-    return [g if n else None for g, n in zip(grads[:2], needs)]
+def sort_perm(keys, n_keys):
+    """Stable ascending order of small non-negative int64 keys (< n_keys <= 2**32): perm[j] = position of the j-th
+    key (_key_perm with its argument checks)."""
+    require_cuda(keys)
+    if int(n_keys - 1).bit_length() > 32:
+        raise RuntimeError('sort_perm: keys need more than 32 bits')
+    keys = i64c(keys)
+    with _on(keys.device):
+        return _key_perm(keys, None, n_keys)
 
 
-def _transr_bwd(tabs, d_e, d_r, h, t, r, go, grads, needs):
-    """TransR's backward: entity and rel_emb gradients through the row mode + _hip_det.segment_sum, proj_mat's by the
-    relation-grouped reduction kge_transr_rel_grad (sorted by relation: no atomics on proj_mat, the same bits on every
-    run)."""
+def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
+    """Returns a list of gradient tensors (or None) matching ``tables``.  Large
+    batches take the sorted reduction (per-triple gradient rows, then one atomic
+    row-add per run of equal target rows) instead of one atomic per element.
+    In deterministic mode (torchkge_amd.determinism) EVERY batch takes the row mode
+    and the rows are summed by kge_segment_sum_ordered: no float atomic, a fixed order.
+    A table whose ``needs`` flag is False costs no sort and no sum."""
     lib = load_library()
-    B, dev = h.shape[0], h.device
-    ld = max(d_e, d_r)
-    rows = torch.empty(4 * B * ld, dtype=torch.float32, device=dev)
+    det = _hip_det.is_deterministic()
+    tabs = [f32c(x) for x in tables] + [None] * (4 - len(tables))
+    grads = [torch.zeros_like(x) for x in tabs[:len(tables)]] + [None] * (4 - len(tables))
+    go = f32c(grad_out)
+    B = h.shape[0]
+    dev = h.device
+    streams, tail = _BWD_STREAMS[kind], _BWD_REL_TAIL.get(kind)
+    # the atomic mode: the kernel adds element by element into the zeroed gradient tables, no rows.  (TorusE: always the
+    # row mode -- no per-element float atomics; the same bits on every run need the deterministic mode, which sums the
+    # rows through kge_segment_sum_ordered)
+    atomic = B < BWD_SORTED_MIN_BATCH and kind in _BWD_ATOMIC and (not det or B == 0)
+    ld = max(d_ent, d_rel) if kind == TRANSR else d_ent
+    n_streams = 4 if tail else max(s0 + ns for _, s0, ns, _ in streams)
+    rows = None if atomic else torch.empty(n_streams * B * ld, dtype=torch.float32, device=dev)
+    gp = grads if atomic else [None] * 4
     with _on(dev):
-        _check(lib.kge_score_triples_bwd(TRANSR, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), None, d_e, d_r, _p(h), _p(t), _p(r), B,
-                                         _p(go), None, None, None, None, _p(rows), ld, _stream()), 'kge_score_triples_bwd')
-        if needs[0]:
-            g = grads[0]
-            perm = _key_perm(h, t, g.shape[0])
-            _hip_det.segment_sum(rows, ld, d_e, h, B, t, B, perm, g, g.stride(0))
-        if needs[1] or needs[2]:
-            perm = _key_perm(r, None, grads[1].shape[0])
-            gp, vp = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
-            if needs[1]:
-                g = grads[1]
-                _hip_det.segment_sum(gp, ld, d_r, r, B, None, 0, perm, g, g.stride(0))
-            if needs[2]:
-                g = grads[2]
-                _check(lib.kge_transr_rel_grad(gp, ld, vp, ld, d_r, d_e, _p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
-                                               _stream()), 'kge_transr_rel_grad')
-    return [g if n else None for g, n in zip(grads[:3], needs)]
+        _check(lib.kge_score_triples_bwd(kind, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
+                                         d_ent, d_rel, _p(h), _p(t), _p(r), B, _p(go),
+                                         _p(gp[0]), _p(gp[1]), _p(gp[2]), _p(gp[3]),
+                                         _p(rows), 0 if atomic else ld, _stream()), 'kge_score_triples_bwd')
+        if not atomic:
+            perms = {'ht': None, 'r': None}     # one sort per id set; the ids index the gradient table's rows
+            for ti, s0, ns, key in streams:
+                if needs[ti]:
+                    g = grads[ti]
+                    k0, k1 = (h, t) if key == 'ht' else (r, None)
+                    perms[key] = _hip_det.reduce_rows(rows.data_ptr() + s0 * B * ld * 4, ld, g.shape[1], k0, k1, g,
+                                                      perm=perms[key], det=det)
+            if tail and needs[tail[0]]:
+                ti, name, args = tail
+                g = grads[ti]
+                perm = perms['r'] if perms['r'] is not None else _key_perm(r, None, g.shape[0])
+                U, V = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
+                _check(getattr(lib, name)(*(args(U, V, ld, d_ent, d_rel) + (_p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
+                                                                             _stream()))), name)
+    return [g if n else None for g, n in zip(grads[:len(tables)], needs)]
 
 
 def transr_proj_sqnorm(M, X, d_e, d_r, b=None, out=None, by_row=False, rels=None):

@@ -5,7 +5,7 @@ table of their own because include/kge_hip.h, kge_lp_desc and its ABI version do
 import torch
 
 from . import _hip, _hip_det
-from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, i64c, require_cuda
+from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, f32rows, i64c, require_cuda
 
 SIDE_REL = 5        # KGE_ANALOGY_SIDE_REL
 MAX_DIM = 512       # of each of d_sc, d_c
@@ -17,19 +17,11 @@ _SIGNATURES = {
     'kge_analogy_score_triples': _T3 + _T3 + [_int, _int, _vp, _vp, _vp, _i64, _vp, _vp],
     'kge_analogy_score_triples_bwd': _T3 + _T3 + [_int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
 }
-_bound = None
 
 
 def load_library():
     """The handle of _hip.load_library() with the argtypes of this header bound."""
-    global _bound
-    lib = _hip.load_library()
-    if _bound is not lib:
-        for name, args in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, _int
-        _bound = lib
-    return lib
+    return _hip.bind(_SIGNATURES)
 
 
 def _t3(tabs):
@@ -43,17 +35,8 @@ def _t3(tabs):
     return out
 
 
-def _rows(x):
-    """A float32 matrix whose rows are contiguous; the row stride is free (the kernels take a leading dimension)."""
-    if x.dtype != torch.float32 or x.dim() != 2:
-        raise RuntimeError('torchkge_amd: expected a float32 matrix, got %s of %d dimensions' % (x.dtype, x.dim()))
-    if x.shape[1] == 0 or (x.stride(1) == 1 and x.stride(0) >= x.shape[1]):
-        return x
-    return x.contiguous()
-
-
 def _prep(tabs):
-    tabs = [None if x is None else _rows(x) for x in tabs]
+    tabs = [None if x is None else f32rows(x) for x in tabs]
     require_cuda(*tabs)
     return tabs
 
@@ -118,12 +101,9 @@ def score_triples(ent, rel, h, t, r):
     return out
 
 
-_SEG_MAX = 1024     # widest row kge_segment_sum_rows reduces in one call
-
-
 def score_triples_bwd(ent, rel, h, t, r, grad_out, needs):
     """Gradients of the six tables (None where ``needs`` says so): per-triple gradient rows in packed layout, reduced
-    per entity / relation by kge_key_sort + _hip_det.segment_sum (kge_segment_sum_rows, or kge_segment_sum_ordered in
+    per entity / relation by _hip_det.reduce_rows (kge_key_sort, then kge_segment_sum_rows, or kge_segment_sum_ordered in
     deterministic mode) into packed gradients whose column slices are the tables' -- no per-element atomics."""
     lib = load_library()
     ent, rel = _prep(ent), _prep(rel)
@@ -135,6 +115,7 @@ def score_triples_bwd(ent, rel, h, t, r, grad_out, needs):
     n_ent, n_rel = ent[0].shape[0], rel[0].shape[0]
     rows = torch.empty(3 * B, K, dtype=torch.float32, device=dev)
     out = [None] * 6
+    det = _hip_det.is_deterministic()
     with _on(dev):
         _check(lib.kge_analogy_score_triples_bwd(*(_t3(ent) + _t3(rel) + [d_sc, d_c, _p(h), _p(t), _p(r), B, _p(go), _p(rows),
                                                                            K, _stream()])), 'kge_analogy_score_triples_bwd')
@@ -143,11 +124,7 @@ def score_triples_bwd(ent, rel, h, t, r, grad_out, needs):
                 continue
             g = torch.zeros(n_rows, K, dtype=torch.float32, device=dev)
             if B:
-                perm = _hip._key_perm(k0, k1, max(n_rows, 1))
-                for c0 in range(0, K, _SEG_MAX):
-                    w = min(_SEG_MAX, K - c0)
-                    _hip_det.segment_sum(src.data_ptr() + 4 * c0, K, w, k0, B, k1, 0 if k1 is None else B, perm,
-                                         g.data_ptr() + 4 * c0, K)
+                _hip_det.reduce_rows(src, K, K, k0, k1, g, det=det)
             parts = (g[:, :d_sc], g[:, d_sc:d_sc + d_c], g[:, d_sc + d_c:])
             for j in range(3):
                 out[first + j] = parts[j] if needs[first + j] else None

@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from . import _hip, _hip_det
-from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, i64c, require_cuda
+from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, f32rows, i64c, require_cuda
 
 MAX_DIM = 512       # KGE_CONVKB_MAX_DIM: of each of d (emb_dim) and F (n_filters)
 SLOT_HEAD, SLOT_REL, SLOT_TAIL, SLOT_BOTH = 0, 1, 2, 3      # the slot the candidates fill; KGE_CONVKB_SLOT_BOTH
@@ -37,34 +37,17 @@ _SIGNATURES = {
     'kge_convkb_score_triples_bwd': [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64,
                                      _vp, _vp, _vp, _vp, _vp],
 }
-_bound = None
 
 
 def load_library():
     """The handle of _hip.load_library() with the argtypes of this header bound."""
-    global _bound
-    lib = _hip.load_library()
-    if _bound is not lib:
-        for name, args in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, _int
-        _bound = lib
-    return lib
+    return _hip.bind(_SIGNATURES)
 
 
 def check_dims(d, F):
     if not (1 <= d <= MAX_DIM and 1 <= F <= MAX_DIM):
         raise RuntimeError('torchkge_amd: ConvKBModel handles 1 <= emb_dim <= %d and 1 <= n_filters <= %d, got emb_dim = %d, '
                            'n_filters = %d' % (MAX_DIM, MAX_DIM, d, F))
-
-
-def _rows(x):
-    """A float32 matrix whose rows are contiguous; the row stride is free (the kernels take a leading dimension)."""
-    if x.dtype != torch.float32 or x.dim() != 2:
-        raise RuntimeError('torchkge_amd: expected a float32 matrix, got %s of %d dimensions' % (x.dtype, x.dim()))
-    if x.stride(1) == 1 and x.stride(0) >= x.shape[1]:
-        return x
-    return x.contiguous()
 
 
 def ws_floats(d, F):
@@ -77,7 +60,7 @@ def prepare(conv_w, conv_b, lin_w, lin_b, d):
     lib = load_library()
     F = conv_w.shape[0]
     check_dims(d, F)
-    w, cb, L, lb = f32c(conv_w), f32c(conv_b), _rows(lin_w), f32c(lin_b)
+    w, cb, L, lb = f32c(conv_w), f32c(conv_b), f32rows(lin_w), f32c(lin_b)
     require_cuda(w, cb, L, lb)
     if tuple(L.shape) != (2, F * d) or w.numel() != 3 * F or cb.numel() != F or lb.numel() != 2:
         raise RuntimeError('torchkge_amd: ConvKB layer shapes do not fit emb_dim = %d, n_filters = %d' % (d, F))
@@ -94,7 +77,7 @@ class ConvKBProblem(object):
     header); ``T``: the candidate rows, local candidate c = global id c_base + c; ``ws``: prepare()'s workspace."""
 
     def __init__(self, slot, QE, qe_idx, QR, qr_idx, T, ws, d, F, B, c_base=0, B_tail=0):
-        QE, QR, T = _rows(QE), _rows(QR), _rows(T)
+        QE, QR, T = f32rows(QE), f32rows(QR), f32rows(T)
         qe_idx = None if qe_idx is None else i64c(qe_idx)
         qr_idx = None if qr_idx is None else i64c(qr_idx)
         require_cuda(QE, QR, T, ws, qe_idx, qr_idx)
@@ -190,7 +173,7 @@ class ConvKBProblem(object):
 
 def score_triples(E, R, ws, d, F, h, t, r):
     lib = load_library()
-    E, R = _rows(E), _rows(R)
+    E, R = f32rows(E), f32rows(R)
     h, t, r = i64c(h), i64c(t), i64c(r)
     require_cuda(E, R, ws, h, t, r)
     B = h.shape[0]
@@ -203,11 +186,11 @@ def score_triples(E, R, ws, d, F, h, t, r):
 
 def score_triples_bwd(E, R, ws, d, F, h, t, r, s, grad_out, needs):
     """Gradients of (ent_emb, rel_emb, conv weight (F, 3, 1), conv bias, linear weight (2, F d), linear bias), None
-    where ``needs`` says so.  Entity / relation gradients: per-triple rows reduced by kge_key_sort +
-    _hip_det.segment_sum (kge_segment_sum_rows, or kge_segment_sum_ordered in deterministic mode; no per-element
+    where ``needs`` says so.  Entity / relation gradients: per-triple rows reduced by _hip_det.reduce_rows
+    (kge_key_sort, then kge_segment_sum_rows, or kge_segment_sum_ordered in deterministic mode; no per-element
     atomics); the four layer gradients: one reduction kernel over the batch (fixed-shape trees: the same bits on every run)."""
     lib = load_library()
-    E, R = _rows(E), _rows(R)
+    E, R = f32rows(E), f32rows(R)
     h, t, r = i64c(h), i64c(t), i64c(r)
     s, go = f32c(s), f32c(grad_out)
     B, dev = h.shape[0], h.device
@@ -221,18 +204,17 @@ def score_triples_bwd(E, R, ws, d, F, h, t, r, s, grad_out, needs):
         dw = torch.empty(F, 3, 1, dtype=torch.float32, device=dev)
         dcb = torch.empty(F, dtype=torch.float32, device=dev)
     out = [None] * 6
+    det = _hip_det.is_deterministic()
     with _on(dev):
         _check(lib.kge_convkb_score_triples_bwd(_p(E), E.stride(0), _p(R), R.stride(0), d, F, _p(ws), _p(h), _p(t), _p(r), B,
                                                 _p(s), _p(go), _p(g), _p(rows), d, _p(dL), _p(dlb), _p(dw), _p(dcb),
                                                 _stream()), 'kge_convkb_score_triples_bwd')
-        for pos, n_rows, k0, k1, src in ((0, E.shape[0], h, t, rows), (1, R.shape[0], r, None, None)):
+        for pos, n_rows, k0, k1, first in ((0, E.shape[0], h, t, 0), (1, R.shape[0], r, None, 2 * B)):
             if not needs[pos]:
                 continue
             grad = torch.zeros(n_rows, d, dtype=torch.float32, device=dev)
             if B:
-                src = rows if pos == 0 else rows[2 * B:]
-                perm = _hip._key_perm(k0, k1, max(n_rows, 1))
-                _hip_det.segment_sum(src, d, d, k0, B, k1, 0 if k1 is None else B, perm, grad, d)
+                _hip_det.reduce_rows(rows[first:], d, d, k0, k1, grad, det=det)
             out[pos] = grad
     if want_par:
         for pos, val in ((2, dw), (3, dcb), (4, dL), (5, dlb)):

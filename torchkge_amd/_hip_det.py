@@ -19,25 +19,15 @@ _SIGNATURES = {
     'kge_segment_sum_ordered': [_vp, _i64, _int, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _size, _vp],
 }
 _WS_SIZES = ('kge_segment_sum_ordered_ws_bytes',)       # size_t f(int64_t M, int d)
-_bound = None
 _WS_BYTES = {}      # (M, d) -> workspace bytes
+SEG_MAX = 1024      # widest row one kge_segment_sum_rows / kge_segment_sum_ordered call reduces
 # how often each reduction was launched by segment_sum / segment_sum_ordered (tests read it: which path a backward took)
 CALLS = {'ordered': 0, 'atomic': 0}
 
 
 def load_library():
     """The handle of _hip.load_library() with the argtypes of this header bound."""
-    global _bound
-    lib = _hip.load_library()
-    if _bound is not lib:
-        for name, args in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, _int
-        for name in _WS_SIZES:
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = [_i64, _int], _size
-        _bound = lib
-    return lib
+    return _hip.bind(_SIGNATURES, _WS_SIZES, (_i64, _int), _size)
 
 
 def ws_bytes(M, d):
@@ -78,3 +68,24 @@ def segment_sum(rows, ld, d, k0, n0, k1, n1, perm, out, out_ld, det=None):
     rc = (_hip._lib or _hip.load_library()).kge_segment_sum_rows(_ptr(rows), ld, d, _ptr(k0), n0, _ptr(k1), n1, _ptr(perm), _ptr(out), out_ld, _stream())
     if rc:
         _check(rc, 'kge_segment_sum_rows')
+
+
+def reduce_rows(rows, ld, d, k0, k1, out, out_ld=None, perm=None, det=None):
+    """The end of every backward: out[id, :d] += the rows (leading dimension ``ld``) of each id of [k0 | k1] (``k1`` may be
+    None), through segment_sum.  ``rows`` / ``out``: tensors or device addresses; ``out_ld``: None takes out.stride(0).
+    ``perm``: the ids' sorted order; None sorts them here (_hip._key_perm: the ids index the out.shape[0] rows of the
+    tensor ``out``).  Returns the order, for the caller to pass back in when it reduces another table by the same ids: one
+    sort per id set and backward.  Rows wider than SEG_MAX go in column chunks.  ``det``: the mode as the backward has
+    read it, once.  An empty id list launches nothing (the library returns before any launch); the caller has made the
+    ids' device current."""
+    n0, n1 = k0.shape[0], (0 if k1 is None else k1.shape[0])
+    if perm is None:
+        perm = _hip._key_perm(k0, k1, max(out.shape[0], 1))
+    if out_ld is None:
+        out_ld = out.stride(0)
+    if det is None:
+        det = is_deterministic()
+    rows, out = _ptr(rows), _ptr(out)
+    for c0 in range(0, d, SEG_MAX):
+        segment_sum(rows + 4 * c0, ld, min(SEG_MAX, d - c0), k0, n0, k1, n1, perm, out + 4 * c0, out_ld, det)
+    return perm

@@ -7,28 +7,17 @@ Nothing here synchronises or reads back."""
 import torch
 
 from . import _hip
-from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, i64c, require_cuda
+from ._hip import _vp, _i64, _p, _check, _on, _stream, i64c, require_cuda
 
 _SIGNATURES = {
     'kge_relation_corrupt': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
 }
 _WS_SIZES = ('kge_relation_corrupt_ws_elems',)        # int64_t f(int64_t)
-_bound = None
 
 
 def load_library():
     """The handle of _hip.load_library() with the argtypes of this header bound."""
-    global _bound
-    lib = _hip.load_library()
-    if _bound is not lib:
-        for name, args in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, _int
-        for name in _WS_SIZES:
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = [_i64], _i64
-        _bound = lib
-    return lib
+    return _hip.bind(_SIGNATURES, _WS_SIZES)
 
 
 def _u8c(t, what):

@@ -7,7 +7,7 @@ Nothing here synchronises or reads back: the one host read of a triplet classifi
 import torch
 
 from . import _hip
-from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, i64c, require_cuda
+from ._hip import _vp, _i64, _p, _check, _on, _stream, f32c, i64c, require_cuda
 
 _SIGNATURES = {
     'kge_positional_corrupt': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
@@ -15,22 +15,11 @@ _SIGNATURES = {
     'kge_threshold_count': [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
 }
 _WS_SIZES = ('kge_positional_ws_elems', 'kge_relation_max_ws_elems')        # int64_t f(int64_t)
-_bound = None
 
 
 def load_library():
     """The handle of _hip.load_library() with the argtypes of this header bound."""
-    global _bound
-    lib = _hip.load_library()
-    if _bound is not lib:
-        for name, args in _SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, _int
-        for name in _WS_SIZES:
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = [_i64], _i64
-        _bound = lib
-    return lib
+    return _hip.bind(_SIGNATURES, _WS_SIZES)
 
 
 def positional_corrupt(heads, tails, rels, mask_u8, u_h, u_t, fb_h, fb_t, offsets_h, values_h, offsets_t, values_t, n_rel):
