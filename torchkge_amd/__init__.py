@@ -12,6 +12,7 @@ from .inference import EntityInference
 from .models import TransEModel, TransHModel, TransDModel, TorusEModel, TransRModel, DistMultModel, ComplExModel, RESCALModel, HolEModel, AnalogyModel, ConvKBModel
 from .sampling import BernoulliNegativeSampler, UniformNegativeSampler
 from .determinism import set_deterministic, is_deterministic, deterministic
+from .rowgrad import set_row_gradients, is_row_gradients, row_gradients
 
 
 # Names of the reference that this package does not provide at its top level: a clear error

@@ -368,18 +368,59 @@ def sort_perm(keys, n_keys):
         return _key_perm(keys, None, n_keys)
 
 
-def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs):
+def _score_triples_bwd_rows(lib, kind, tabs, n_tables, d_ent, d_rel, h, t, r, go, needs):
+    """score_triples_bwd in row-gradient mode (torchkge_amd.rowgrad): the gradient of every table with row streams is
+    the uncoalesced sparse tensor (ids, per-triple rows) -- a view of the rows buffer where the stream's leading
+    dimension is the table's width, a copy for TransR's max(d_ent, d_rel) layout.  No sort, no sum, no table-sized
+    tensor and no host read; every batch size takes the row mode.  The per-relation matrices (RESCAL, TransR) are
+    reduced as ever into a dense gradient."""
+    from ._hip_rows import sparse_rows
+    B, dev = h.shape[0], h.device
+    streams, tail = _BWD_STREAMS[kind], _BWD_REL_TAIL.get(kind)
+    ld = max(d_ent, d_rel) if kind == TRANSR else d_ent
+    n_streams = 4 if tail else max(s0 + ns for _, s0, ns, _ in streams)
+    rows = torch.empty(n_streams * B * ld, dtype=torch.float32, device=dev)
+    grads = [None] * n_tables
+    with _on(dev):
+        if B:
+            _check(lib.kge_score_triples_bwd(kind, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]),
+                                             d_ent, d_rel, _p(h), _p(t), _p(r), B, _p(go), None, None, None, None,
+                                             _p(rows), ld, _stream()), 'kge_score_triples_bwd')
+        ids = {'ht': None, 'r': r}
+        for ti, s0, ns, key in streams:
+            if needs[ti]:
+                if ids[key] is None:
+                    ids[key] = torch.cat((h, t))
+                d = tabs[ti].shape[1]
+                vals = rows[s0 * B * ld:(s0 + ns) * B * ld].view(ns * B, ld)
+                grads[ti] = sparse_rows(ids[key], vals if ld == d else vals[:, :d].contiguous(), tabs[ti].shape)
+        if tail and needs[tail[0]]:
+            ti, name, args = tail
+            g = grads[ti] = torch.zeros_like(tabs[ti])
+            if B:
+                perm = _key_perm(r, None, g.shape[0])
+                U, V = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
+                _check(getattr(lib, name)(*(args(U, V, ld, d_ent, d_rel) + (_p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
+                                                                             _stream()))), name)
+    return [g if n else None for g, n in zip(grads, needs)]
+
+
+def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs, row_grads=False):
     """Returns a list of gradient tensors (or None) matching ``tables``.  Large
     batches take the sorted reduction (per-triple gradient rows, then one atomic
     row-add per run of equal target rows) instead of one atomic per element.
     In deterministic mode (torchkge_amd.determinism) EVERY batch takes the row mode
     and the rows are summed by kge_segment_sum_ordered: no float atomic, a fixed order.
-    A table whose ``needs`` flag is False costs no sort and no sum."""
+    A table whose ``needs`` flag is False costs no sort and no sum.
+    ``row_grads`` (torchkge_amd.rowgrad, as the forward read it): the rows are not reduced at all but returned as
+    uncoalesced sparse gradients (_score_triples_bwd_rows)."""
     lib = load_library()
-    det = _hip_det.is_deterministic()
     tabs = [f32c(x) for x in tables] + [None] * (4 - len(tables))
-    grads = [torch.zeros_like(x) for x in tabs[:len(tables)]] + [None] * (4 - len(tables))
     go = f32c(grad_out)
+    if row_grads:
+        return _score_triples_bwd_rows(lib, kind, tabs, len(tables), d_ent, d_rel, h, t, r, go, needs)
+    det = _hip_det.is_deterministic()
+    grads = [torch.zeros_like(x) for x in tabs[:len(tables)]] + [None] * (4 - len(tables))
     B = h.shape[0]
     dev = h.device
     streams, tail = _BWD_STREAMS[kind], _BWD_REL_TAIL.get(kind)

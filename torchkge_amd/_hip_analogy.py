@@ -5,6 +5,7 @@ table of their own because include/kge_hip.h, kge_lp_desc and its ABI version do
 import torch
 
 from . import _hip, _hip_det
+from ._hip_rows import sparse_rows
 from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, f32rows, i64c, require_cuda
 
 SIDE_REL = 5        # KGE_ANALOGY_SIDE_REL
@@ -101,10 +102,12 @@ def score_triples(ent, rel, h, t, r):
     return out
 
 
-def score_triples_bwd(ent, rel, h, t, r, grad_out, needs):
+def score_triples_bwd(ent, rel, h, t, r, grad_out, needs, row_grads=False):
     """Gradients of the six tables (None where ``needs`` says so): per-triple gradient rows in packed layout, reduced
     per entity / relation by _hip_det.reduce_rows (kge_key_sort, then kge_segment_sum_rows, or kge_segment_sum_ordered in
-    deterministic mode) into packed gradients whose column slices are the tables' -- no per-element atomics."""
+    deterministic mode) into packed gradients whose column slices are the tables' -- no per-element atomics.
+    ``row_grads`` (torchkge_amd.rowgrad, as the forward read it): no reduction -- every gradient is the uncoalesced sparse
+    tensor of the ids and a copy of its column slice of the packed rows."""
     lib = load_library()
     ent, rel = _prep(ent), _prep(rel)
     d_sc, d_c = _dims(ent)
@@ -121,6 +124,12 @@ def score_triples_bwd(ent, rel, h, t, r, grad_out, needs):
                                                                            K, _stream()])), 'kge_analogy_score_triples_bwd')
         for first, n_rows, k0, k1, src in ((0, n_ent, h, t, rows), (3, n_rel, r, None, rows[2 * B:])):
             if not any(needs[first:first + 3]):
+                continue
+            if row_grads:
+                ids = r if k1 is None else torch.cat((k0, k1))
+                for j, (c0, c1) in enumerate(((0, d_sc), (d_sc, d_sc + d_c), (d_sc + d_c, K))):
+                    if needs[first + j]:
+                        out[first + j] = sparse_rows(ids, src[:ids.shape[0], c0:c1].contiguous(), (n_rows, c1 - c0))
                 continue
             g = torch.zeros(n_rows, K, dtype=torch.float32, device=dev)
             if B:

@@ -10,6 +10,7 @@ import ctypes
 import torch
 
 from . import _hip, _hip_det
+from ._hip_rows import sparse_rows
 from ._hip import _vp, _i64, _int, _p, _check, _on, _stream, f32c, f32rows, i64c, require_cuda
 
 MAX_DIM = 512       # KGE_CONVKB_MAX_DIM: of each of d (emb_dim) and F (n_filters)
@@ -184,11 +185,13 @@ def score_triples(E, R, ws, d, F, h, t, r):
     return out
 
 
-def score_triples_bwd(E, R, ws, d, F, h, t, r, s, grad_out, needs):
+def score_triples_bwd(E, R, ws, d, F, h, t, r, s, grad_out, needs, row_grads=False):
     """Gradients of (ent_emb, rel_emb, conv weight (F, 3, 1), conv bias, linear weight (2, F d), linear bias), None
     where ``needs`` says so.  Entity / relation gradients: per-triple rows reduced by _hip_det.reduce_rows
     (kge_key_sort, then kge_segment_sum_rows, or kge_segment_sum_ordered in deterministic mode; no per-element
-    atomics); the four layer gradients: one reduction kernel over the batch (fixed-shape trees: the same bits on every run)."""
+    atomics); the four layer gradients: one reduction kernel over the batch (fixed-shape trees: the same bits on every run).
+    ``row_grads`` (torchkge_amd.rowgrad, as the forward read it): no reduction -- the entity / relation gradients are the
+    uncoalesced sparse tensors of the ids and views of the rows; the layer gradients stay dense."""
     lib = load_library()
     E, R = f32rows(E), f32rows(R)
     h, t, r = i64c(h), i64c(t), i64c(r)
@@ -211,6 +214,10 @@ def score_triples_bwd(E, R, ws, d, F, h, t, r, s, grad_out, needs):
                                                 _stream()), 'kge_convkb_score_triples_bwd')
         for pos, n_rows, k0, k1, first in ((0, E.shape[0], h, t, 0), (1, R.shape[0], r, None, 2 * B)):
             if not needs[pos]:
+                continue
+            if row_grads:
+                ids = r if k1 is None else torch.cat((k0, k1))
+                out[pos] = sparse_rows(ids, rows[first:first + ids.shape[0]], (n_rows, d))
                 continue
             grad = torch.zeros(n_rows, d, dtype=torch.float32, device=dev)
             if B:

@@ -9,6 +9,7 @@ import torch
 
 from .. import _hip
 from .. import _hip_analogy
+from ..rowgrad import is_row_gradients
 from ..utils.modeling import init_embedding
 from .interfaces import BilinearModel, _table_of
 from .translation import _ent_range
@@ -314,6 +315,7 @@ class RESCALModel(_OperatorModel):
     (L2-normalised rows) and ``rel_mat`` (n_rel, emb_dim * emb_dim), M_r = rel_mat[r].view(d, d)."""
 
     _kind = _hip.RESCAL
+    _DENSE_GRAD_TABLES = ('rel_mat',)       # reduced per relation by kge_rescal_rel_grad: not row-shaped
 
     def __init__(self, emb_dim, n_entities, n_relations):
         super().__init__(emb_dim, n_entities, n_relations)
@@ -373,6 +375,7 @@ class _AnalogyScore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, t, r, *tables):
         tabs = [x.detach() for x in tables]
+        ctx.row_grads = is_row_gradients()      # read here: a loss built inside row_gradients() keeps the mode
         ctx.save_for_backward(h, t, r, *tabs)
         return _hip_analogy.score_triples(tabs[:3], tabs[3:], h, t, r)
 
@@ -380,7 +383,7 @@ class _AnalogyScore(torch.autograd.Function):
     def backward(ctx, grad_out):
         h, t, r = ctx.saved_tensors[:3]
         tabs = list(ctx.saved_tensors[3:])
-        grads = _hip_analogy.score_triples_bwd(tabs[:3], tabs[3:], h, t, r, grad_out, ctx.needs_input_grad[3:])
+        grads = _hip_analogy.score_triples_bwd(tabs[:3], tabs[3:], h, t, r, grad_out, ctx.needs_input_grad[3:], row_grads=ctx.row_grads)
         return (None,) * 3 + tuple(grads)
 
 

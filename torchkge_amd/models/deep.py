@@ -8,6 +8,7 @@ import torch
 from torch import nn
 
 from .. import _hip, _hip_convkb
+from ..rowgrad import is_row_gradients
 from ..utils.modeling import init_embedding
 from .interfaces import Model
 
@@ -21,13 +22,15 @@ class _ConvKBScore(torch.autograd.Function):
         ws = _hip_convkb.prepare(conv_w, conv_b, lin_w, lin_b, d)
         s = _hip_convkb.score_triples(ent, rel, ws, d, F, h, t, r)
         ctx.d, ctx.F = d, F
+        ctx.row_grads = is_row_gradients()      # read here: a loss built inside row_gradients() keeps the mode
         ctx.save_for_backward(h, t, r, ent, rel, ws, s)
         return s
 
     @staticmethod
     def backward(ctx, grad_out):
         h, t, r, ent, rel, ws, s = ctx.saved_tensors
-        grads = _hip_convkb.score_triples_bwd(ent, rel, ws, ctx.d, ctx.F, h, t, r, s, grad_out, ctx.needs_input_grad[5:])
+        grads = _hip_convkb.score_triples_bwd(ent, rel, ws, ctx.d, ctx.F, h, t, r, s, grad_out, ctx.needs_input_grad[5:],
+                                              row_grads=ctx.row_grads)
         return (None,) * 5 + tuple(grads)
 
 

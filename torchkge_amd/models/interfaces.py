@@ -18,6 +18,7 @@ import torch
 from torch.nn import Module
 
 from .. import _hip
+from ..rowgrad import is_row_gradients
 
 
 class _ScoreTriples(torch.autograd.Function):
@@ -28,6 +29,7 @@ class _ScoreTriples(torch.autograd.Function):
     def forward(ctx, kind, d_ent, d_rel, h, t, r, *tables):
         tabs = [x.detach() for x in tables]
         ctx.kind, ctx.d_ent, ctx.d_rel = kind, d_ent, d_rel
+        ctx.row_grads = is_row_gradients()      # read here: a loss built inside row_gradients() keeps the mode
         ctx.save_for_backward(h, t, r, *tabs)
         return _hip.score_triples(kind, tabs, d_ent, d_rel, h, t, r)
 
@@ -37,7 +39,7 @@ class _ScoreTriples(torch.autograd.Function):
         tabs = list(ctx.saved_tensors[3:])
         needs = ctx.needs_input_grad[6:]
         grads = _hip.score_triples_bwd(ctx.kind, tabs, ctx.d_ent, ctx.d_rel, _hip.i64c(h),
-                                       _hip.i64c(t), _hip.i64c(r), grad_out, needs)
+                                       _hip.i64c(t), _hip.i64c(r), grad_out, needs, row_grads=ctx.row_grads)
         return (None,) * 6 + tuple(grads)
 
 
@@ -159,6 +161,7 @@ class Model(Module):
     _kind = None          # kge_hip.h model kind
     _ENT_TABLES = ()      # names of the entity-indexed nn.Embedding tables (row-sharded across GPUs)
     _ENT_POS = (0,)       # their positions in _tables()
+    _DENSE_GRAD_TABLES = ()     # names of the nn.Embedding tables whose gradient stays dense in row-gradient mode
 
     def __init__(self, n_entities, n_relations):
         super().__init__()

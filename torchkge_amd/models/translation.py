@@ -642,6 +642,7 @@ class TransRModel(TranslationModel):
     the path the last problem took ('expand' or 'exact')."""
 
     _kind = _hip.TRANSR
+    _DENSE_GRAD_TABLES = ('proj_mat',)      # reduced per relation by kge_transr_rel_grad: not row-shaped
     _ENT_TABLES = ('ent_emb',)
     lp_sort_queries_by_relation = True     # (the epilogue gathers Z[r_i, c]: queries in relation order share those rows)
     lp_last_path = None
