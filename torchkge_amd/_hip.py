@@ -659,6 +659,7 @@ def split_accum_model():
 
 SPLIT_EPS_SCALE = 1.0          # multiplies the proven error band of the f16-split prefilter (tests shrink it)
 SPLIT_LIST_PER_QUERY = 64      # capacity of the uncertain-pair list per query of the batch (floor; grows with N)
+SPLIT_PREFIX_MAX_UNITS = 128   # widest operand kge_lp_split_prefix_max folds (k16 units: K <= 2031)
 
 
 def _row_operand(X, K, X1, K1, is_query, dot, row_index):
@@ -708,6 +709,11 @@ def split_table(X, K=None, aug=None, X1=None, K1=None, dot=False, nmax0=None, nm
     """Candidate operand of the split prefilter + the prefix squared-norm maxima that tighten its error
     band (kge_lp_split_rows with cell sums, kge_lp_split_prefix_max): (Es, e2pref)."""
     lib = load_library()
+    width = (X.shape[1] if K is None else K) + (0 if X1 is None else (X1.shape[1] if K1 is None else K1))
+    if int(lib.kge_lp_split_units(int(width), 1)) > SPLIT_PREFIX_MAX_UNITS:
+        # rows past the prefix-maximum kernel's width (K > 2031, e.g. ComplEx d >= 1016): the plain band, which needs no
+        # prefix maxima (e2pref = None) -- wider, equally certified
+        return split_rows(X, K=K, aug=aug, X1=X1, K1=K1, dot=dot, nmax0=nmax0, nmax1=nmax1), None
     Es, css = split_rows(X, K=K, aug=aug, X1=X1, K1=K1, dot=dot, nmax0=nmax0, nmax1=nmax1, cell_ss=True)
     units_p = css.shape[0]
     e2 = torch.zeros(units_p, dtype=torch.float32, device=X.device)
@@ -745,15 +751,26 @@ def hi_rows(X, K=None, is_query=False, aug=None, X1=None, K1=None, dot=False, nm
 HI_STREAM = os.environ.get('KGE_HI_STREAM', '1') != '0'    # one-product level on the free-running kernel (lp_hi_stream.hip)
 
 
+HI_STREAM_PANEL_UNITS = 32      # k16 units of the resident query panel (kge_hi_stream_launch; tests/width_table.py checks it)
+
+
 def hi_stream_ok(K):
-    """Does the free-running one-product sweep (fragment-major candidate table, kge_split_args.es_frag) handle K columns?"""
+    """Does the free-running one-product sweep (fragment-major candidate table, kge_split_args.es_frag) handle K columns
+    with PLAIN thresholds (KGE_LP_DOT / KGE_LP_L2_EXPAND)?  The projection modes: and hi_stream_panel_ok(K)."""
     return HI_STREAM and int(load_library().kge_lp_hi_stream_supported(int(K))) == 1
+
+
+def hi_stream_panel_ok(K):
+    """Do rows of K columns fit the free-running sweep's RESIDENT query panel?  What sweeps past it -- the chunked-panel
+    kernel of 33 / 65 units -- has plain thresholds, one query per column, one global list: kge_lp_split_count answers
+    KGE_EUNSUPPORTED to a projection mode (KGE_LP_L2_PROJH / _PROJD) there, so such problems keep the planar table."""
+    return (int(K) + 2 + 15) // 16 <= HI_STREAM_PANEL_UNITS
 
 
 def hi_stream_groups_ok(mode, K):
     """Does the free-running sweep take GROUPED query columns (ColumnPlan.members) for this problem?  r06: the plain-threshold
     modes (KGE_LP_DOT / KGE_LP_L2_EXPAND) on rows short enough for the resident panel (<= 32 k16 units)."""
-    return mode in (LP_DOT, LP_L2_EXPAND) and (int(K) + 2 + 15) // 16 <= 32
+    return mode in (LP_DOT, LP_L2_EXPAND) and hi_stream_panel_ok(K)
 
 
 def hi_table(X, K=None, aug=None, X1=None, K1=None, dot=False, nmax0=None, nmax1=None, frag=False):

@@ -358,8 +358,15 @@ class Model(Module):
         """Columns of the all-candidates GEMM (ComplEx: 2 d)."""
         return self._d_rel
 
+    # does this model's split count carry a projection epilogue (KGE_LP_L2_PROJH / _PROJD: TransH, TransD)?  The free-running
+    # kernel has one on its resident panel only, so what decides es_frag must know the mode (_hip.hi_stream_panel_ok)
+    _lp_proj_counts = False
+
     def _level1_stream(self):
-        return bool(self.lp_hi_stream) and _hip.hi_stream_ok(self._lp_width())
+        K = self._lp_width()
+        if self._lp_proj_counts and not _hip.hi_stream_panel_ok(K):
+            return False        # (TransH / TransD at 33 / 65 units: the planar one-product kernel)
+        return bool(self.lp_hi_stream) and _hip.hi_stream_ok(K)
 
     # ... which CAN sweep query COLUMNS (one matrix sweep per distinct query row, the members' thresholds compared in the
     # epilogue: lp_hi_stream_kernel<.., GS = 4>, r06) for the plain-threshold counts -- TransE-L2, DistMult, ComplEx -- on rows

@@ -287,6 +287,7 @@ class TransHModel(TranslationModel):
     lp_sort_queries_by_relation = True
     lp_dedupe_queries = 'relation-major'   # ColumnPlan with the columns in relation order (same reason)
     lp_stream_columns = False              # (the free-running kernel's projection epilogue sweeps per query)
+    _lp_proj_counts = True                 # (... and exists for rows of its resident panel only: Model._level1_stream)
 
     def _tables(self):
         return [self.ent_emb.weight, self.rel_emb.weight, self.norm_vect.weight]
@@ -416,6 +417,7 @@ class TransDModel(TranslationModel):
     lp_sort_queries_by_relation = True     # (as TransH: the epilogue gathers G[r_i, c])
     lp_dedupe_queries = 'relation-major'
     lp_stream_columns = False
+    _lp_proj_counts = True
 
     def __init__(self, ent_emb_dim, rel_emb_dim, n_entities, n_relations):
         super().__init__(n_entities, n_relations, 'L2')
