@@ -425,6 +425,94 @@ def test_pair_count_and_filter_kernels_on_carved_descriptors(hip, mode, B, N, K)
             assert_guard_intact(v)
 
 
+PAIR_GRID_CAP = 256 * 14        # blocks of the pair kernels (one wavefront, 64 pairs per round): past it a block loops
+
+
+@pytest.mark.parametrize('mode', ['dot', 'l2d', 'l1d_ax', 'tel2'])
+@pytest.mark.parametrize('K', [17, 64])
+def test_pair_scores_past_the_grid_cap(hip, mode, K):
+    """kge_lp_pair_scores with more 64-pair groups than the grid has blocks (the first blocks take a second round, the
+    last group is partial): every output is the bits of the score matrix at (qi, ci), 0 outside the shard.  K = 64 runs
+    the staged chains on float4 rows (dot, L2 direct, torus eL2), K = 17 the staged dot chain on unaligned rows and the
+    scalar walk; l1d_ax the scalar walk with the rank-1 term."""
+    lib = hip.load_library()
+    B, N = 65, 193
+    P = 64 * PAIR_GRID_CAP + 65
+    ops = make_ops(mode, B, N, K)
+    S = packed_scores(hip, mode, ops).cpu().numpy()
+    g = torch.Generator().manual_seed(P + K)
+    qi = torch.randint(0, B, (P,), generator=g)
+    ci = torch.randint(0, N + 2 * C_BASE, (P,), generator=g)        # GLOBAL ids, a few outside [C_BASE, C_BASE + N)
+    loc = ci - C_BASE
+    inside = (loc >= 0) & (loc < N)
+    assert 0 < int((~inside).sum()) < P // 10
+    ref = np.where(inside.numpy(), S[qi.numpy(), loc.clamp(0, N - 1).numpy()], np.float32(0)).astype(np.float32)
+    prob, dv = problem(hip, mode, ops, {}, c_base=C_BASE)
+    d_qi, d_ci = carve(qi, poison=0, device='cuda'), carve(ci, poison=N + C_BASE, device='cuda')
+    out = guarded_out(P)
+    assert raw(lib, 'kge_lp_pair_scores', prob.desc, d_qi, d_ci, P, out) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.int32), ref.view(np.int32))
+    for v in [out, d_qi, d_ci] + list(dv.values()):
+        assert_guard_intact(v)
+
+
+def filter_expect_dense(S, st, true_glob, tg2d, N):
+    """filter_expect for segments of one length, vectorised: tg2d (B, L) holds query i's segment."""
+    c = tg2d - C_BASE
+    inside = (c >= 0) & (c < N)
+    is_true = tg2d == true_glob[:, None]
+    ge = np.take_along_axis(S, np.clip(c, 0, N - 1), 1) >= st[:, None]
+    neg = (-INF >= st).astype(np.int32)
+    sub = ((ge.astype(np.int32) - neg[:, None]) * (inside & ~is_true)).sum(1).astype(np.int32)
+    return sub, (inside & is_true).any(1).astype(np.int32)
+
+
+@pytest.mark.parametrize('mode', ['dot', 'l1d'])
+def test_planned_filter_correction_past_the_grid_cap(hip, mode):
+    """kge_lp_filter_sub_planned with more flattened (key, target) pairs than 64 per block of the scoring grid: 600
+    queries with distinct segments of 400 targets (below the hub-list length, so the short compare runs), sub / found
+    the integers the score matrix gives."""
+    lib = hip.load_library()
+    B, N, K, L = 600, 512, 64, 400
+    assert B * L > 64 * PAIR_GRID_CAP
+    ops = make_ops(mode, B, N, K)
+    S = packed_scores(hip, mode, ops).cpu().numpy()
+    g = torch.Generator().manual_seed(B + N + L)
+    true_loc = torch.randint(0, N, (B,), generator=g)
+    st = S[np.arange(B), true_loc.numpy()]
+    tg2d = torch.stack([torch.randperm(N + 2 * C_BASE, generator=g)[:L] for _ in range(B)])     # distinct GLOBAL ids
+    for i in range(0, B, 2):            # every other segment holds its query's true entity
+        if not bool((tg2d[i] == true_loc[i] + C_BASE).any()):
+            tg2d[i, 0] = true_loc[i] + C_BASE
+    tg2d = tg2d.sort(1).values
+    lo = torch.arange(B, dtype=torch.int64) * L
+    hi, tg = lo + L, tg2d.reshape(-1).to(torch.int32)
+    true_glob = (true_loc + C_BASE).numpy()
+    sub_ref, found_ref = filter_expect_dense(S, st, true_glob, tg2d.numpy(), N)
+    few = filter_expect(S[:8], st[:8], true_loc[:8] + C_BASE, lo[:8], hi[:8], tg, N)        # the vectorised form is the loop's
+    assert np.array_equal(few[0], sub_ref[:8]) and np.array_equal(few[1], found_ref[:8])
+    assert 0 < int(found_ref.sum()) < B and int(np.abs(sub_ref).sum()) > 0
+    prob, dv = problem(hip, mode, ops, {}, c_base=C_BASE)
+    d_st = carve(torch.from_numpy(st.copy()), poison=NAN, device='cuda')
+    d_true = carve(true_loc + C_BASE, poison=N + C_BASE, device='cuda')
+    d_lo, d_hi = carve(lo, poison=0, device='cuda'), carve(hi, poison=0, device='cuda')
+    d_tg = carve(tg, poison=N + C_BASE, device='cuda')
+    n_t = B * L
+    woff, long_q, n_pairs = hip.filter_plan_build(d_lo, d_hi, n_t, 512)
+    assert n_pairs == n_t and int(long_q.shape[0]) == 0
+    fs = guarded_out(n_t)
+    sub, found = guarded_out(B, dtype=torch.int32), guarded_out(B, dtype=torch.int32)
+    rc = raw(lib, 'kge_lp_filter_sub_planned', prob.desc, d_st, d_true, d_lo, d_hi, d_tg, n_t, woff, n_pairs, None, 0, fs, sub,
+             found)
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(sub.cpu().numpy(), sub_ref)
+    assert np.array_equal(found.cpu().numpy(), found_ref)
+    for v in [fs, sub, found, d_st, d_true, d_lo, d_hi, d_tg] + list(dv.values()):
+        assert_guard_intact(v)
+
+
 @pytest.mark.parametrize('mode', MODES)
 @pytest.mark.parametrize('K', [8, 17])
 def test_pointer_advancing_chunks_and_row_blocks_equal_the_slices(hip, mode, K):

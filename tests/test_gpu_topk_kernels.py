@@ -1,4 +1,4 @@
-"""GPU tests of the three top-k selection kernels of torchkge_amd/csrc/rank_filter.hip (run with -m gpu on an MI355X):
+"""GPU tests of the three top-k selection kernels of torchkge_amd/csrc/topk.hip (run with -m gpu on an MI355X):
 topk_chunk_reg_kernel<8 | 16 | 32> (the one-pass register selection behind kge_topk_chunk for k <= 32), topk_chunk_kernel
 (its k-pass fallback: k > 32, or KGE_TOPK_REG=0) and topk_kernel (kge_topk).
 

@@ -55,6 +55,27 @@ __device__ __forceinline__ int wave_sum_i(int v)
     return v;
 }
 
+constexpr int RB = 256; // threads per row-block
+
+__device__ __forceinline__ int block_sum_i(int v, int *sh)
+{
+    v = wave_sum_i(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    int t = 0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
+    return t;
+}
+
+static inline int grid1d(int64_t n, int per_block)
+{
+    int64_t b = (n + per_block - 1) / per_block;
+    const int64_t cap = 256 * 16;
+    return (int)(b < cap ? (b > 0 ? b : 1) : cap);
+}
+
 // ---- the scoring contract of kge_lp_desc (see include/kge_hip.h) ----------
 __device__ __forceinline__ float lp_chain_dot(const float *__restrict__ a, const float *__restrict__ t,
                                               int K, float acc)
@@ -196,149 +217,6 @@ __device__ __forceinline__ float lp_pair_score(const kge_lp_desc &d, int64_t i, 
         }
     }
     return -acc;
-}
-
-// ---- wave-cooperative exact pair scores (MFMA modes) ------------------------------
-// One lane per (query, candidate) pair runs the scalar chain above -- one
-// accumulator in a fixed order, it cannot be split across lanes -- but the two
-// rows of each of the wavefront's 64 pairs are fetched COOPERATIVELY, 32 k at a
-// time, as 128-byte row segments (8 lanes x float4 per row, all of a chunk's
-// loads in flight together) and handed to their lane through LDS (row stride 36
-// floats: conflict-free b128 stores and loads).  A lane-per-row gather touches 64
-// different cache lines per load instruction and is ~5x slower.
-// Every lane of the wavefront must call; `qs`/`es` are this wavefront's own
-// 64 x KGE_PS_LD floats of LDS.  Bit-identical to lp_pair_score.
-#ifndef KGE_PS_KC_V
-#define KGE_PS_KC_V 32      /* 8 float4 pieces per row: the piece -> (row, column) split is shifts, and hipcc keeps */
-#define KGE_PS_LD_V 36      /* the pipelined loop at 88 VGPRs (40 / 44 hoisted 80 address registers and spilled)   */
-#endif
-constexpr int KGE_PS_KC = KGE_PS_KC_V, KGE_PS_LD = KGE_PS_LD_V;
-
-static inline bool kge_lp_vec4(const kge_lp_desc &d)
-{
-    bool v = (d.K0 % 4 == 0) && (d.lda0 % 4 == 0) && (d.ldt0 % 4 == 0) && kge_aligned16(d.A0) && kge_aligned16(d.T0);
-    if (d.K1 > 0)
-        v = v && (d.K1 % 4 == 0) && (d.lda1 % 4 == 0) && (d.ldt1 % 4 == 0) && kge_aligned16(d.A1) && kge_aligned16(d.T1);
-    return v;
-}
-
-// the direct modes' chains (lp_pair_score without the rank-1 term), one accumulator: L2 one fmaf per k in
-// ascending order; L1 and the torus modes one add per aligned 4-group of k, the group as (m0+m1)+(m2+m3).  `a` / `t`
-// must be readable (zero-filled) up to the next multiple of 4 -- the staged chunks below are.
-// CH: 1 = L1 direct, 2 = L2 direct, or a KGE_LP_TORUS_* mode
-template <int CH>
-__device__ __forceinline__ float lp_chain_direct(const float *__restrict__ a, const float *__restrict__ t, int K, float acc)
-{
-    if (CH != 2) {
-        constexpr int OP = CH == 1 ? (int)KGE_LP_L1_DIRECT : CH;
-        for (int k = 0; k < K; k += 4) {
-            const float4 av = *reinterpret_cast<const float4 *>(a + k), tv = *reinterpret_cast<const float4 *>(t + k);
-            acc = acc + ((lp_direct_term<OP>(av.x - tv.x) + lp_direct_term<OP>(av.y - tv.y)) +
-                         (lp_direct_term<OP>(av.z - tv.z) + lp_direct_term<OP>(av.w - tv.w)));
-        }
-    } else {
-        for (int k = 0; k < K; ++k) {
-            const float diff = a[k] - t[k];
-            acc = fmaf(diff, diff, acc);
-        }
-    }
-    return acc;
-}
-
-// CH: 0 = the MFMA modes' dot chain (lp_chain_dot), 1 = L1 direct, 2 = L2 direct, KGE_LP_TORUS_*: that torus mode
-template <bool VEC4, int CH = 0>
-__device__ __forceinline__ float lp_staged_segment(const float *__restrict__ A, int64_t lda,
-                                                   const float *__restrict__ T, int64_t ldt, int K, int qi, int ci,
-                                                   float *qs, float *es, float acc)
-{
-    const int lane = threadIdx.x & 63;
-    // Full chunks (16-byte aligned rows): software-pipelined -- the NEXT chunk's 16 row loads are issued before
-    // the current chunk's sequential chain runs, so the chain (32 dependent FMAs fed from LDS) hides under the
-    // loads' latency instead of following it: a pair costs one load latency plus the chains, not one per chunk.
-    // The 16 in-flight float4 are NAMED scalars (macro-expanded): as arrays carried around the chunk loop hipcc
-    // left them in scratch memory (272 B of private segment, 3.5x slower than no pipelining at all).
-    static_assert(KGE_PS_KC == 32, "the fetch / store macros below are written out for 8 float4 pieces per row");
-    int k0 = 0;
-    if (VEC4 && K >= KGE_PS_KC) {
-        float4 q0, q1, q2, q3, q4, q5, q6, q7, e0, e1, e2, e3, e4, e5, e6, e7;
-#define KGE_PS_FETCH(IT, KK)                                                                                  \
-    {                                                                                                         \
-        const int idx_ = lane + 64 * IT, rr_ = idx_ >> 3, pc_ = idx_ & 7;                                     \
-        const int rq_ = __shfl(qi, rr_, 64), rc_ = __shfl(ci, rr_, 64);                                      \
-        q##IT = *reinterpret_cast<const float4 *>(A + (int64_t)rq_ * lda + (KK) + pc_ * 4);                   \
-        e##IT = *reinterpret_cast<const float4 *>(T + (int64_t)rc_ * ldt + (KK) + pc_ * 4);                   \
-    }
-#define KGE_PS_STORE(IT)                                                                                      \
-    {                                                                                                         \
-        const int idx_ = lane + 64 * IT, rr_ = idx_ >> 3, pc_ = idx_ & 7;                                     \
-        *reinterpret_cast<float4 *>(qs + rr_ * KGE_PS_LD + pc_ * 4) = q##IT;                                  \
-        *reinterpret_cast<float4 *>(es + rr_ * KGE_PS_LD + pc_ * 4) = e##IT;                                  \
-    }
-#define KGE_PS_ALL(M, ...) M(0, ##__VA_ARGS__) M(1, ##__VA_ARGS__) M(2, ##__VA_ARGS__) M(3, ##__VA_ARGS__) \
-                           M(4, ##__VA_ARGS__) M(5, ##__VA_ARGS__) M(6, ##__VA_ARGS__) M(7, ##__VA_ARGS__)
-        KGE_PS_ALL(KGE_PS_FETCH, 0)
-        for (; k0 + KGE_PS_KC <= K; k0 += KGE_PS_KC) {
-            KGE_PS_ALL(KGE_PS_STORE)
-            if (k0 + 2 * KGE_PS_KC <= K) { KGE_PS_ALL(KGE_PS_FETCH, k0 + KGE_PS_KC) }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // same wave: LDS executes in order
-            if (CH == 0) acc = lp_chain_dot(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, KGE_PS_KC, acc);
-            else acc = lp_chain_direct<CH>(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, KGE_PS_KC, acc);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        }
-#undef KGE_PS_ALL
-#undef KGE_PS_STORE
-#undef KGE_PS_FETCH
-    }
-    for (; k0 < K; k0 += KGE_PS_KC) {      // the last, partial chunk (and everything when rows are not 16-byte aligned)
-        const int kc = min(KGE_PS_KC, K - k0);
-        {
-            const int pieces = (kc + 3) >> 2;
-            for (int idx = lane; idx < 64 * pieces; idx += 64) { // uniform trip count
-                const int rr = idx / pieces, pc = idx - rr * pieces;
-                const int rq = __shfl(qi, rr, 64), rc = __shfl(ci, rr, 64);
-                const float *qp = A + (int64_t)rq * lda + k0 + pc * 4;
-                const float *ep = T + (int64_t)rc * ldt + k0 + pc * 4;
-                const int left = kc - pc * 4;
-                float4 qv, ev;
-                qv.x = qp[0]; ev.x = ep[0];
-                qv.y = left > 1 ? qp[1] : 0.f; ev.y = left > 1 ? ep[1] : 0.f;
-                qv.z = left > 2 ? qp[2] : 0.f; ev.z = left > 2 ? ep[2] : 0.f;
-                qv.w = left > 3 ? qp[3] : 0.f; ev.w = left > 3 ? ep[3] : 0.f;
-                *reinterpret_cast<float4 *>(qs + rr * KGE_PS_LD + pc * 4) = qv;
-                *reinterpret_cast<float4 *>(es + rr * KGE_PS_LD + pc * 4) = ev;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        if (CH == 0) acc = lp_chain_dot(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, kc, acc);
-        else acc = lp_chain_direct<CH>(qs + lane * KGE_PS_LD, es + lane * KGE_PS_LD, kc, acc);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    return acc;
-}
-
-// plain direct modes (no rank-1 term): -sum_k |q - t| resp. -sum_k (q - t)^2, bit-identical to lp_pair_score
-template <bool VEC4, bool L1>
-__device__ __forceinline__ float lp_pair_score_staged_direct(const kge_lp_desc &d, int qi, int ci, float *qs, float *es)
-{
-    return -lp_staged_segment<VEC4, L1 ? 1 : 2>(d.A0, d.lda0, d.T0, d.ldt0, d.K0, qi, ci, qs, es, 0.0f);
-}
-
-// plain direct or torus modes by chain code (CH of lp_staged_segment: 1 L1, 2 L2, KGE_LP_TORUS_*), bit-identical to
-// lp_pair_score
-template <bool VEC4, int CH>
-__device__ __forceinline__ float lp_pair_score_staged_ch(const kge_lp_desc &d, int qi, int ci, float *qs, float *es)
-{
-    static_assert(CH == 1 || CH == 2 || CH == KGE_LP_TORUS_L1 || CH == KGE_LP_TORUS_L2 || CH == KGE_LP_TORUS_EL2, "chain code");
-    return lp_direct_finish<CH>(lp_staged_segment<VEC4, CH>(d.A0, d.lda0, d.T0, d.ldt0, d.K0, qi, ci, qs, es, 0.0f));
-}
-
-// MFMA modes only (KGE_LP_IS_MFMA); (qi, ci) must be valid rows on every lane
-template <bool VEC4>
-__device__ __forceinline__ float lp_pair_score_staged(const kge_lp_desc &d, int qi, int ci, float *qs, float *es)
-{
-    float acc = lp_staged_segment<VEC4>(d.A0, d.lda0, d.T0, d.ldt0, d.K0, qi, ci, qs, es, 0.0f);
-    if (d.K1 > 0) acc = lp_staged_segment<VEC4>(d.A1, d.lda1, d.T1, d.ldt1, d.K1, qi, ci, qs, es, acc);
-    return lp_epilogue_any(d, acc, qi, ci);
 }
 
 // tuning knob for experiments (env KGE_LP_TARGET_BLOCKS), default `dflt`

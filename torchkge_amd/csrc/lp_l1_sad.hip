@@ -14,7 +14,7 @@
 //   |D - s L| <= 1.004 K   (each operand is within 0.5 of x s after rounding, + 0.002 for the product's own rounding)
 //   the exact kernel's value F = fl(L) is within (K + 1) 2^-24 L of L  (one rounding per subtract / add, ascending k)
 //   count  <=>  F_c <= U_i,  U_i = -s_true_i.      D <= T_lo_i: certainly counted;  D >= T_hi_i: certainly not;
-//   T_lo < D < T_hi: UNCERTAIN -> listed, re-scored exactly (lp_pair_score_staged_direct == lp_pair_score ==
+//   T_lo < D < T_hi: UNCERTAIN -> listed, re-scored exactly (lp_pair_exact.h: lp_pair_score_staged_ch == lp_pair_score ==
 //   lp_direct_kernel, bit for bit).
 // raw_count first receives #{D < T_hi}; kge_lp_sad_recheck takes 1 off for every listed pair whose exact score is
 // below s_true: the counts are EXACTLY those of kge_lp_count_ge.  tests/test_gpu_parity.py checks that.
@@ -22,7 +22,7 @@
 // Kernel: the register tiling of lp_direct.hip (256 threads as 16 x 16, 8 x 8 pairs per thread, operands staged
 // through double-buffered LDS 32 k at a time: 64 B per row, row stride 80 B -> conflict-free b128), 4 v_sad_u16
 // per (pair, 8 k).  Uncertain pairs are buffered in LDS per tile and handed to the global list by one atomic.
-#include "kge_common.h"
+#include "lp_pair_exact.h"
 
 #ifndef KGE_SAD_UNROLL
 #define KGE_SAD_UNROLL 1
@@ -314,27 +314,6 @@ __global__ __launch_bounds__(NT, 2) void lp_l1_sad_count_kernel(const SadParams 
     }
 }
 
-// exact re-scoring of the listed pairs (plain direct modes): one lane per pair, rows staged cooperatively
-template <bool VEC4, bool L1>
-__global__ __launch_bounds__(64, 2) void direct_recheck_kernel(const kge_lp_desc d, const float *__restrict__ s_true,
-                                                               const int32_t *__restrict__ list, int32_t cap,
-                                                               const int32_t *__restrict__ list_count, int32_t *raw_count)
-{
-    __shared__ __attribute__((aligned(16))) float qs[64 * KGE_PS_LD];
-    __shared__ __attribute__((aligned(16))) float es[64 * KGE_PS_LD];
-    const int lane = threadIdx.x;
-    const int n = (int)min((unsigned)*list_count, (unsigned)cap);
-    const int ngroups = (n + 63) >> 6;
-    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const int pi = grp * 64 + lane;
-        const bool valid = pi < n;
-        const int pj = valid ? pi : grp * 64;
-        const int qi = list[2 * pj], ci = list[2 * pj + 1];
-        const float sc = lp_pair_score_staged_direct<VEC4, L1>(d, qi, ci, qs, es);
-        if (valid && !(sc >= s_true[qi])) atomicSub(&raw_count[qi], 1);
-    }
-}
-
 } // namespace
 
 extern "C" int64_t kge_lp_sad_cols_padded(int K) { return ((int64_t)K + 7) / 8 * 8; }
@@ -425,13 +404,15 @@ extern "C" int kge_lp_sad_recheck(const kge_lp_desc *d, const float *s_true, con
     if ((d->mode != KGE_LP_L1_DIRECT && d->mode != KGE_LP_L2_DIRECT) || d->Wq) return KGE_EINVAL;
     if (d->B == 0 || d->N == 0) return 0;
     if (!s_true || !list || cap <= 0 || !list_count || !raw_count) return KGE_EINVAL;
-    const int grid = cap / 64 + 1 < 256 * 14 ? cap / 64 + 1 : 256 * 14;
-    hipStream_t st = kge_s(stream);
-    const bool v4 = kge_lp_vec4(*d), l1 = d->mode == KGE_LP_L1_DIRECT;
-    if (v4 && l1) hipLaunchKernelGGL((direct_recheck_kernel<true, true>), dim3(grid), dim3(64), 0, st, *d, s_true, list, cap, list_count, raw_count);
-    else if (v4) hipLaunchKernelGGL((direct_recheck_kernel<true, false>), dim3(grid), dim3(64), 0, st, *d, s_true, list, cap, list_count, raw_count);
-    else if (l1) hipLaunchKernelGGL((direct_recheck_kernel<false, true>), dim3(grid), dim3(64), 0, st, *d, s_true, list, cap, list_count, raw_count);
-    else hipLaunchKernelGGL((direct_recheck_kernel<false, false>), dim3(grid), dim3(64), 0, st, *d, s_true, list, cap, list_count, raw_count);
-    KGE_CHECK_LAUNCH();
-    return 0;
+    const int grid = lp_pair_grid((int64_t)cap + 1);      // cap / 64 + 1 wavefronts: the length is only known on the device
+    return lp_pair_dispatch<PAIR_STAGED>(*d, [&](auto v) {
+        using V = decltype(v);
+        if constexpr (V::chain == PAIR_DOT) return KGE_EINVAL;      // (not reached: plain L1 / L2 only, checked above)
+        else {
+            hipLaunchKernelGGL(lp_list_recheck_kernel<V>, dim3(grid), dim3(64), 0, kge_s(stream), *d, s_true, list, cap,
+                               list_count, raw_count, nullptr);
+            KGE_CHECK_LAUNCH();
+            return 0;
+        }
+    });
 }

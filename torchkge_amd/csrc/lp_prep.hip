@@ -7,7 +7,7 @@
 // (translation.py:260-284, :629-652): instead of caching P[r,e,:] (R x N x d
 // floats) the engine keeps one scalar per (entity[,relation]).
 // One wavefront per row; all HBM-bound and tiny next to the scoring kernels.
-#include "kge_common.h"
+#include "lp_pair_exact.h"     // KGE_PS_KC / KGE_PS_LD, lp_pair_grid: the row kernels stage chunks of the same shape, 64 rows a wavefront
 
 namespace {
 
@@ -644,10 +644,8 @@ extern "C" int kge_row_sqnorm(const float *X, int64_t ld, int64_t rows, int K, f
             auto k = row_sqnorm_staged_kernel<16, 4>;
             hipLaunchKernelGGL(k, dim3((int)blocks), dim3(256), 0, kge_s(stream), X, ld, rows, K, out, max_io);
         } else {
-            const int64_t groups = (rows + 63) / 64;
             auto k = row_sqnorm_staged_kernel<64, 1>;
-            hipLaunchKernelGGL(k, dim3((int)(groups < 256 * 14 ? groups : 256 * 14)), dim3(64), 0,
-                               kge_s(stream), X, ld, rows, K, out, max_io);
+            hipLaunchKernelGGL(k, dim3(lp_pair_grid(rows)), dim3(64), 0, kge_s(stream), X, ld, rows, K, out, max_io);
         }
     } else {
         hipLaunchKernelGGL(row_sqnorm_kernel, dim3(grid_threads(rows, 64)), dim3(64), 0, kge_s(stream), X, ld, rows, K,
@@ -681,9 +679,8 @@ extern "C" int kge_row_dot(const float *X, const float *Y, int64_t ld, int64_t r
             const int64_t groups = (rows + 15) / 16;
             hipLaunchKernelGGL(row_dot_staged_kernel<16>, dim3((int)groups), dim3(64), 0, kge_s(stream), X, Y, ld, rows, K, scale, out);
         } else {
-            const int64_t groups = (rows + 63) / 64;
-            hipLaunchKernelGGL(row_dot_staged_kernel<64>, dim3((int)(groups < 256 * 14 ? groups : 256 * 14)), dim3(64), 0,
-                               kge_s(stream), X, Y, ld, rows, K, scale, out);
+            hipLaunchKernelGGL(row_dot_staged_kernel<64>, dim3(lp_pair_grid(rows)), dim3(64), 0, kge_s(stream), X, Y, ld, rows, K,
+                               scale, out);
         }
     } else {
         hipLaunchKernelGGL(row_dot_kernel, dim3(grid_threads(rows, 64)), dim3(64), 0, kge_s(stream), X, Y, ld, rows, K, scale, out);

@@ -14,7 +14,7 @@
 // and classifies every (query, candidate) pair against two per-query thresholds:
 //   acc >= a_hi : certainly counted          acc < a_lo : certainly not counted
 //   a_lo <= acc < a_hi : UNCERTAIN -> appended to a list and re-scored by the
-//   exact scalar chain (kge_common.h: lp_pair_score_staged, bit-identical to the
+//   exact scalar chain (lp_pair_exact.h: lp_pair_score_staged, bit-identical to the
 //   fp32 MFMA tile kernel and to oracle/kge_oracle.c).
 // raw_count[i] first receives #{acc >= a_lo}; kge_lp_split_recheck then takes 1
 // off for every listed pair whose exact score is below s_true.  The resulting

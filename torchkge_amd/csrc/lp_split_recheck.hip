@@ -1,32 +1,11 @@
 // Exact recheck of the f16-split prefilter (lp_split_mfma.hip has the error analysis): the pairs the count sweep listed
 // as uncertain are re-scored by the exact scalar chain, from one global list or region by region.
 #include "lp_split_common.h"
+#include "lp_pair_exact.h"
 
 namespace {
 
-// Exact re-scoring of the listed pairs: one lane per pair, rows staged cooperatively
-// (kge_common.h: lp_pair_score_staged).
-template <bool VEC4>
-__global__ __launch_bounds__(64, 2) void split_recheck_kernel(const kge_lp_desc d, const float *__restrict__ s_true,
-                                                           const int32_t *__restrict__ list, int32_t cap,
-                                                           const int32_t *__restrict__ list_count, int32_t *raw_count,
-                                                           float *list_stat)
-{
-    __shared__ __attribute__((aligned(16))) float qs[64 * KGE_PS_LD];
-    __shared__ __attribute__((aligned(16))) float es[64 * KGE_PS_LD];
-    const int lane = threadIdx.x;
-    const int n = (int)min((unsigned)*list_count, (unsigned)cap);   // (a count past the capacity means overflow: the caller redoes the count)
-    if (list_stat && blockIdx.x == 0 && lane == 0) atomicAdd(list_stat, (float)n);   // pairs re-scored per evaluation (level policy)
-    const int ngroups = (n + 63) >> 6;
-    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const int pi = grp * 64 + lane;
-        const bool valid = pi < n;
-        const int pj = valid ? pi : grp * 64;       // idle lanes shadow the group's first pair
-        const int qi = list[2 * pj], ci = list[2 * pj + 1];
-        const float sc = lp_pair_score_staged<VEC4>(d, qi, ci, qs, es);
-        if (valid && !(sc >= s_true[qi])) atomicSub(&raw_count[qi], 1);
-    }
-}
+// (the listed pairs of one global list: lp_pair_exact.h: lp_list_recheck_kernel, instantiated by kge_lp_split_recheck below)
 
 // ---- exact re-scoring REGION BY REGION (r05) -------------------------------------------------------------------------
 // The free-running sweep can leave its uncertain pairs in regions of the list, one per (query panel, 32-query sub-tile)
@@ -193,16 +172,17 @@ extern "C" int kge_lp_split_recheck(const kge_lp_desc *d, const float *s_true, c
     if (d->B == 0 || d->N == 0) return 0;
     if (!s_true || !list || cap <= 0 || !list_count || !raw_count) return KGE_EINVAL;
     if (!KGE_LP_IS_MFMA(d->mode)) return KGE_EINVAL;
-    const bool vec4 = kge_lp_vec4(*d);
     const int grid = split_num_cus() * kge_env_int("KGE_SPLIT_RECHECK_WAVES", 160 * 1024 / (2 * 64 * KGE_PS_LD * 4));
-    if (vec4)
-        hipLaunchKernelGGL(split_recheck_kernel<true>, dim3(grid), dim3(64), 0, kge_s(stream), *d, s_true, list, cap,
-                           list_count, raw_count, list_stat);
-    else
-        hipLaunchKernelGGL(split_recheck_kernel<false>, dim3(grid), dim3(64), 0, kge_s(stream), *d, s_true, list,
-                           cap, list_count, raw_count, list_stat);
-    KGE_CHECK_LAUNCH();
-    return 0;
+    return lp_pair_dispatch<PAIR_STAGED>(*d, [&](auto v) {
+        using V = decltype(v);
+        if constexpr (V::chain != PAIR_DOT) return KGE_EINVAL;      // (not reached: the MFMA modes run the dot chain)
+        else {
+            hipLaunchKernelGGL(lp_list_recheck_kernel<V>, dim3(grid), dim3(64), 0, kge_s(stream), *d, s_true, list, cap,
+                               list_count, raw_count, list_stat);
+            KGE_CHECK_LAUNCH();
+            return 0;
+        }
+    });
 }
 
 /* regions of the list of n queries' sweep: 3 per panel of 96 queries (kge_split_args.region_count) */
