@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from oracle import kge_oracle as orc
-from tests.helpers import ROOT, GOLDEN
+from tests.helpers import ROOT, GOLDEN, raw
 from tests.test_transr_host import scoring64, side_scores64, relation_scores64
 
 pytestmark = pytest.mark.gpu
@@ -186,6 +186,50 @@ def test_query_transform_vs_float64_and_order_independence(hip, de, dr):
     assert torch.equal(Qg, Q) and torch.equal(Ug, U)
     _, U3 = hip.transr_query(hip.SIDE_TAIL, None, Pd, None, de, dr, None, None, rd, Q=Qt)
     assert torch.equal(U3, Ut)
+
+
+@pytest.mark.parametrize('dr,de', [(1, 1), (24, 24), (64, 64), (65, 64), (70, 130)])
+def test_rel_grad_reduction_tiles_and_segments(hip, dr, de):
+    """kge_transr_rel_grad / kge_rescal_rel_grad called directly: one 64 x 64 tile, an exact tile, one column past a
+    tile, 2 x 3 ragged tiles; per relation an empty, a single-triple, a 16, 17, 33 and 133 triple segment (the reduction
+    stages 16 triples per step) of shuffled triples.  Every element is an n-term fp32 fmaf chain: its error against
+    float64 is at most n 2^-24 (|U|^T |V|), asserted doubled.  The square shapes give the same bits through both exports."""
+    lib = hip.load_library()
+    n_rel, lens = 6, [16, 0, 133, 1, 33, 17]
+    B = sum(lens)
+    g = torch.Generator().manual_seed(dr * 1000 + de)
+    r = torch.repeat_interleave(torch.arange(n_rel), torch.tensor(lens))[torch.randperm(B, generator=g)]
+    U = torch.randn(B, dr + 3, generator=g).cuda()[:, :dr]      # row stride width + 3
+    V = torch.randn(B, de + 3, generator=g).cuda()[:, :de]
+    rd = r.cuda()
+    perm = hip._key_perm(rd, None, n_rel)
+    assert not torch.equal(perm.cpu(), torch.arange(B))
+
+    def run(name):
+        gM = torch.full((n_rel, dr * de), float('nan'), device='cuda')
+        if name == 'kge_transr_rel_grad':
+            rc = raw(lib, name, U, U.stride(0), V, V.stride(0), dr, de, rd, perm, B, n_rel, gM, gM.stride(0))
+        else:
+            rc = raw(lib, name, U, V, U.stride(0), de, rd, perm, B, n_rel, gM, gM.stride(0))
+        assert rc == 0, name
+        return gM
+
+    gM = run('kge_transr_rel_grad')
+    assert torch.equal(run('kge_transr_rel_grad'), gM)
+    if dr == de:
+        assert V.stride(0) == U.stride(0) and torch.equal(run('kge_rescal_rel_grad'), gM)
+    got = gM.cpu().double().view(n_rel, dr, de)
+    U64, V64 = U.cpu().double(), V.cpu().double()
+    for rho, n in enumerate(lens):
+        sel = r == rho
+        assert int(sel.sum()) == n
+        ref = U64[sel].t() @ V64[sel]
+        bound = n * 2.0 ** -23 * (U64[sel].abs().t() @ V64[sel].abs())
+        err = (got[rho] - ref).abs()
+        print('relation %d n %d max err %.3e (max bound %.3e)' % (rho, n, err.max().item(), bound.max().item()))
+        assert bool((err <= bound).all()), (rho, n)
+        if n == 0:
+            assert not gM[rho].view(torch.int32).any()
 
 
 def test_dimension_limits(hip):

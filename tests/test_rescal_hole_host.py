@@ -96,9 +96,10 @@ def test_float64_restatement_reproduces_the_fixture(kind):
 
 
 def test_operator_kernels_hold_no_lane_crossing_packed_f32_operand():
-    """bilinear_xform.hip (query transform, relation rows, K1 forward / backward, d rel_mat reduction) is built without
-    the SLP vectoriser like the MFMA count kernels; its gfx950 assembly, compiled with the build's own flags, holds no
-    packed f32 instruction with an op_sel bit set (the form test_host_logic.py explains)."""
+    """bilinear_xform.hip (its instantiations of rel_operator.h's query transform, relation rows, K1 forward / backward;
+    the d rel_mat reduction is transr_xform.hip's kernel) is built without the SLP vectoriser like the MFMA count kernels;
+    its gfx950 assembly, compiled with the build's own flags, holds no packed f32 instruction with an op_sel bit set (the
+    form test_host_logic.py explains)."""
     from torchkge_amd.csrc import build as hb
     src = 'bilinear_xform.hip'
     assert src in hb.SOURCES and '-fno-slp-vectorize' in hb.EXTRA_FLAGS[src]
@@ -107,12 +108,12 @@ def test_operator_kernels_hold_no_lane_crossing_packed_f32_operand():
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     text = r.stdout
-    for k in ('bilinear_query_kernel', 'relation_rows_kernel', 'bilinear_score_fwd_kernel', 'bilinear_score_bwd_kernel',
-              'rescal_rel_grad_kernel'):
+    full, general = ('rel_query_kernelINS_10BilinearOpELb%dEEE' % f for f in (1, 0))
+    for k in (full, general, 'relation_rows_kernel', 'bilinear_score_fwd_kernel', 'bilinear_score_bwd_kernel'):
         assert k in text, k
     bad = [l.strip() for l in text.split('\n')
            if re.search(r'\bv_pk_(fma|mul|add)_f32\b', l) and re.search(r'op_sel:\[[01,]*1[01,]*\]', l)]
     assert not bad, bad[:4]
     # no scratch spills in the query transform (its 16 accumulators stay in registers)
-    m = re.search(r'bilinear_query_kernelILb1EEEvN.*?\.private_segment_fixed_size:\s*(\d+)', text, re.S)
-    assert m is None or int(m.group(1)) == 0
+    m = re.search(r'\.name:\s*\S*' + full + r'\S*\n.*?\.private_segment_fixed_size:\s*(\d+)', text, re.S)
+    assert m is not None and int(m.group(1)) == 0, m

@@ -149,8 +149,8 @@ def test_transr_kernels_isa():
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     text = r.stdout
-    for k in ('proj_sqnorm_kernel', 'transr_query_kernel', 'transr_score_fwd_kernel', 'transr_score_bwd_kernel',
-              'transr_rel_grad_kernel'):
+    for k in ('proj_sqnorm_kernel', 'rel_query_kernelINS_8TransROpELb0EEE', 'transr_score_fwd_kernel',
+              'transr_score_bwd_kernel', 'rel_outer_grad_kernel'):
         assert k in text, k
     bad = [l.strip() for l in text.split('\n')
            if re.search(r'\bv_pk_(fma|mul|add)_f32\b', l) and re.search(r'op_sel:\[[01,]*1[01,]*\]', l)]

@@ -4,22 +4,17 @@
 // Once the query row is transformed (tail side q = x . B_r, head side q = x . B_r^T), the all-candidates score is
 // the plain dot product q . E[c] of DistMult: everything downstream (KGE_LP_DOT, the split prefilter, filter, ranks)
 // is reused.  This file holds what is specific to these two models:
-//   - the relation-grouped query transform of evaluate() (kge_bilinear_query): rows sorted by relation, each tile of
-//     B_r staged in LDS once per group of up to 64 rows (HolE: generated there from the d floats of R[r]);
+//   - the query transform of evaluate() (kge_bilinear_query) as an Op of the relation-grouped transform of
+//     rel_operator.h: which entity row, which side of B_r, the shard's ownership (HolE: the tile of B_r is generated in LDS
+//     from the d floats of R[r]);
 //   - the relation-candidate rows of relation prediction (kge_bilinear_relation_rows);
-//   - scoring_function forward / backward (reached through kge_score_triples / _bwd) and RESCAL's relation-grouped
-//     reduction of d rel_mat (kge_rescal_rel_grad).
+//   - scoring_function forward / backward (reached through kge_score_triples / _bwd); RESCAL's d rel_mat
+//     (kge_rescal_rel_grad) is the square case of the per-relation reduction in transr_xform.hip.
 // Every sum is an explicit fmaf chain in a fixed order (-ffp-contract=off): a transformed query row depends on
 // (entity, relation, side) only, never on the rest of the batch or on where the row sits in a tile.
-#include "kge_common.h"
+#include "rel_operator.h"
 
 namespace {
-
-constexpr int QT_ROWS = 64;     // rows of one query-transform tile (sorted positions)
-constexpr int QT_COLS = 64;     // output columns of one tile
-constexpr int QT_KC = 16;       // k chunk staged in LDS (d % 16 == 0: full chunks, unrolled inner loop)
-constexpr int QT_THREADS = 256;
-constexpr int QT_PER_THREAD = QT_ROWS * QT_COLS / QT_THREADS;   // 16 accumulators
 
 // coefficient of x[k] in output column j: tail side B[k][j], head side B[j][k]; rr = the relation's row
 __device__ __forceinline__ float op_coef(int kind, bool head, const float *__restrict__ rr, int d, int k, int j)
@@ -30,113 +25,35 @@ __device__ __forceinline__ float op_coef(int kind, bool head, const float *__res
     return rr[m];
 }
 
-struct QueryParams {
+// kge_bilinear_query as an Op of rel_query_kernel (rel_operator.h).  A run is one (relation, side): the two sides of a
+// relation read B_r in different index orders.  A row whose entity lies outside the shard [ent_lo, ent_lo + ent_n) is
+// written as zeros (the owning rank's row is added to it).
+struct BilinearOp {
+    int K, J;                           // both d
     int kind, side;
-    const float *X; int64_t ldx;        // entity rows (whole table, shard or replica)
     const float *Rt; int64_t ldr;       // relation table: rel_mat (n_rel, d*d) or R (n_rel, d)
     const int64_t *h, *t, *r;
-    int64_t n_facts, n_rows;
-    int d;
-    int64_t ent_lo, ent_n;
-    const int64_t *perm;                // optional: the rows in relation order
-    float *Q; int64_t ldq;
-};
+    int64_t n_facts;
+    int64_t ent_lo, ent_n;              // ent_n < 0: X is the whole table
 
-template <bool FULL>
-__global__ __launch_bounds__(QT_THREADS) void bilinear_query_kernel(const QueryParams p)
-{
-    __shared__ float Xs[QT_ROWS][QT_KC + 1];
-    __shared__ float Bs[QT_KC][QT_COLS + 1];
-    __shared__ int64_t row_out[QT_ROWS];    // output row
-    __shared__ int64_t row_key[QT_ROWS];    // relation * 2 + head side
-    __shared__ int64_t row_src[QT_ROWS];    // local entity row, -1: not owned by this shard
-    __shared__ int run_lo[QT_ROWS + 1];
-    __shared__ int n_runs;
-    const int tid = threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.x * QT_ROWS;
-    const int nr = (int)((p.n_rows - p0) < QT_ROWS ? (p.n_rows - p0) : QT_ROWS);
-    const int c0 = blockIdx.y * QT_COLS;
-    const int d = p.d;
-    if (tid < QT_ROWS) {
-        int64_t out = -1, key = -1, src = -1;
-        if (tid < nr) {
-            const int64_t pos = p.perm ? p.perm[p0 + tid] : p0 + tid;
-            const bool second = p.side == KGE_SIDE_BOTH && pos >= p.n_facts;
-            const bool head = p.side == KGE_SIDE_HEAD || second;
-            const int64_t f = second ? pos - p.n_facts : pos;
-            const int64_t e = (head ? p.t[f] : p.h[f]) - p.ent_lo;
-            out = pos;
-            key = p.r[f] * 2 + (head ? 1 : 0);
-            src = (p.ent_n < 0 || (e >= 0 && e < p.ent_n)) ? e : -1;
-        }
-        row_out[tid] = out; row_key[tid] = key; row_src[tid] = src;
+    __device__ RelRow row(int64_t pos) const
+    {
+        const bool second = side == KGE_SIDE_BOTH && pos >= n_facts;
+        const bool head = side == KGE_SIDE_HEAD || second;
+        const int64_t f = second ? pos - n_facts : pos;
+        const int64_t e = (head ? t[f] : h[f]) - ent_lo;
+        return RelRow{pos, r[f] * 2 + (head ? 1 : 0), (ent_n < 0 || (e >= 0 && e < ent_n)) ? e : -1, 0.f};
     }
-    __syncthreads();
-    if (tid == 0) {     // runs of equal (relation, side) among the tile's rows
-        int n = 0;
-        for (int i = 0; i < nr; ++i)
-            if (i == 0 || row_key[i] != row_key[i - 1]) run_lo[n++] = i;
-        run_lo[n] = nr;
-        n_runs = n;
-    }
-    __syncthreads();
-    const int col = tid & (QT_COLS - 1), rg = tid / QT_COLS;
-    float acc[QT_PER_THREAD];
-#pragma unroll
-    for (int s = 0; s < QT_PER_THREAD; ++s) acc[s] = 0.f;
-    for (int k0 = 0; k0 < d; k0 += QT_KC) {
-        const int kn = FULL ? QT_KC : (d - k0 < QT_KC ? d - k0 : QT_KC);
-        for (int idx = tid; idx < QT_ROWS * QT_KC; idx += QT_THREADS) {
-            const int rr = idx / QT_KC, kk = idx % QT_KC;
-            const int64_t src = row_src[rr];
-            Xs[rr][kk] = (src >= 0 && kk < kn) ? p.X[src * p.ldx + k0 + kk] : 0.f;
-        }
-        for (int ru = 0; ru < n_runs; ++ru) {
-            const int rs = run_lo[ru], re = run_lo[ru + 1];
-            const int64_t key = row_key[rs];
-            const bool head = (key & 1) != 0;
-            const float *rrow = p.Rt + (key >> 1) * p.ldr;
-            __syncthreads();        // Xs complete; the previous run's readers of Bs are done
-            for (int idx = tid; idx < QT_KC * QT_COLS; idx += QT_THREADS) {
-                int kk, jj;
-                if (p.kind == KGE_RESCAL && head) { kk = idx % QT_KC; jj = idx / QT_KC; }     // M[j][k]: k contiguous
-                else { jj = idx % QT_COLS; kk = idx / QT_COLS; }
-                const int j = c0 + jj;
-                Bs[kk][jj] = (kk < kn && j < d) ? op_coef(p.kind, head, rrow, d, k0 + kk, j) : 0.f;
-            }
-            __syncthreads();
-            if (FULL) {
-#pragma unroll
-                for (int kk = 0; kk < QT_KC; ++kk) {
-                    const float b = Bs[kk][col];
-#pragma unroll
-                    for (int s = 0; s < QT_PER_THREAD; ++s) {
-                        const int row = rg + 4 * s;
-                        if (row >= rs && row < re) acc[s] = fmaf(Xs[row][kk], b, acc[s]);
-                    }
-                }
-            } else {
-                for (int kk = 0; kk < kn; ++kk) {
-                    const float b = Bs[kk][col];
-#pragma unroll
-                    for (int s = 0; s < QT_PER_THREAD; ++s) {
-                        const int row = rg + 4 * s;
-                        if (row >= rs && row < re) acc[s] = fmaf(Xs[row][kk], b, acc[s]);
-                    }
-                }
-            }
-        }
-        __syncthreads();            // before the next chunk overwrites Xs
-    }
-    const int j = c0 + col;
-    if (j < d) {
-#pragma unroll
-        for (int s = 0; s < QT_PER_THREAD; ++s) {
-            const int row = rg + 4 * s;
-            if (row < nr) p.Q[row_out[row] * p.ldq + j] = row_src[row] >= 0 ? acc[s] : 0.f;
-        }
-    }
-}
+    struct Coefs {
+        int kind, d;
+        bool head;
+        const float *rr;
+        __device__ bool k_contiguous() const { return kind == KGE_RESCAL && head; }    // M[j][k]
+        __device__ float operator()(int k, int j) const { return op_coef(kind, head, rr, d, k, j); }
+    };
+    __device__ Coefs coefs(int64_t key) const { return Coefs{kind, K, (key & 1) != 0, Rt + (key >> 1) * ldr}; }
+    __device__ float finish(const RelRow &w, int, float acc) const { return w.src >= 0 ? acc : 0.f; }
+};
 
 // relation prediction rows: RESCAL out[i, a*d + b] = h_a t_b; HolE out[i, k] = chain_j h_j t_{(j+k) mod d}
 __global__ __launch_bounds__(256) void relation_rows_kernel(int kind, const float *__restrict__ H, int64_t ldh,
@@ -165,18 +82,6 @@ __global__ __launch_bounds__(256) void relation_rows_kernel(int kind, const floa
 }
 
 // ---- scoring_function: h^ . B_r . t^ with x^ = x / max(||x||, 1e-12), four triples per block (one per wave) ----
-constexpr int SC_WAVES = 4;
-constexpr int SC_MAXD = 512;
-
-__device__ __forceinline__ float load_normalized(const float *__restrict__ x, int d, int lane, float *xs)
-{
-    float ss = 0.f;
-    for (int k = lane; k < d; k += 64) ss = fmaf(x[k], x[k], ss);
-    const float n = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
-    for (int k = lane; k < d; k += 64) xs[k] = x[k] / n;
-    return n;
-}
-
 struct BScoreParams {
     int kind;
     const float *E, *Rt;
@@ -193,7 +98,7 @@ struct BScoreParams {
 
 __global__ __launch_bounds__(SC_WAVES * 64) void bilinear_score_fwd_kernel(const BScoreParams p)
 {
-    __shared__ float hs[SC_WAVES][SC_MAXD], ts[SC_WAVES][SC_MAXD];
+    __shared__ float hs[SC_WAVES][REL_MAXD], ts[SC_WAVES][REL_MAXD];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, d = p.d;
     for (int64_t base = (int64_t)blockIdx.x * SC_WAVES; base < p.B; base += (int64_t)gridDim.x * SC_WAVES) {
         const int64_t i = base + w;
@@ -233,7 +138,7 @@ __device__ __forceinline__ void emit_row(const BScoreParams &p, int stream, int6
 
 __global__ __launch_bounds__(SC_WAVES * 64) void bilinear_score_bwd_kernel(const BScoreParams p)
 {
-    __shared__ float hs[SC_WAVES][SC_MAXD], ts[SC_WAVES][SC_MAXD], gh[SC_WAVES][SC_MAXD], gt[SC_WAVES][SC_MAXD];
+    __shared__ float hs[SC_WAVES][REL_MAXD], ts[SC_WAVES][REL_MAXD], gh[SC_WAVES][REL_MAXD], gt[SC_WAVES][REL_MAXD];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, d = p.d;
     for (int64_t base = (int64_t)blockIdx.x * SC_WAVES; base < p.B; base += (int64_t)gridDim.x * SC_WAVES) {
         const int64_t i = base + w;
@@ -293,76 +198,10 @@ __global__ __launch_bounds__(SC_WAVES * 64) void bilinear_score_bwd_kernel(const
     }
 }
 
-// d rel_mat of RESCAL, relation-grouped: gM[rho] = sum over the triples of rho, in sorted order, of U_i V_i^T (a GEMM
-// whose K is the relation's triples).  One block per (relation, 64 x 64 tile); rho's segment by binary search.
-constexpr int RG_KC = 16;
-
-__global__ __launch_bounds__(256) void rescal_rel_grad_kernel(const float *__restrict__ U, const float *__restrict__ V,
-                                                              int64_t ld, int d, const int64_t *__restrict__ r,
-                                                              const int64_t *__restrict__ perm, int64_t B,
-                                                              float *__restrict__ gM, int64_t ldg)
-{
-    __shared__ float Us[RG_KC][QT_COLS + 1], Vs[RG_KC][QT_COLS + 1];
-    __shared__ int64_t seg[2];
-    __shared__ int64_t rowid[RG_KC];
-    const int64_t rho = blockIdx.x;
-    const int nt = (d + QT_COLS - 1) / QT_COLS;
-    const int a0 = (blockIdx.y / nt) * QT_COLS, b0 = (blockIdx.y % nt) * QT_COLS;
-    const int tid = threadIdx.x;
-    if (tid < 2) {      // first sorted position whose key is >= rho + tid
-        int64_t lo = 0, hi = B;
-        const int64_t key = rho + tid;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (r[perm[mid]] < key) lo = mid + 1;
-            else hi = mid;
-        }
-        seg[tid] = lo;
-    }
-    __syncthreads();
-    const int64_t s0 = seg[0], s1 = seg[1];
-    const int col = tid & (QT_COLS - 1), rg = tid / QT_COLS;
-    float acc[QT_PER_THREAD];
-#pragma unroll
-    for (int s = 0; s < QT_PER_THREAD; ++s) acc[s] = 0.f;
-    for (int64_t j0 = s0; j0 < s1; j0 += RG_KC) {
-        const int kn = (s1 - j0) < RG_KC ? (int)(s1 - j0) : RG_KC;
-        if (tid < RG_KC) rowid[tid] = tid < kn ? perm[j0 + tid] : -1;
-        __syncthreads();
-        for (int idx = tid; idx < RG_KC * QT_COLS; idx += 256) {
-            const int kk = idx / QT_COLS, cc = idx % QT_COLS;
-            const int64_t i = rowid[kk];
-            Us[kk][cc] = (i >= 0 && a0 + cc < d) ? U[i * ld + a0 + cc] : 0.f;
-            Vs[kk][cc] = (i >= 0 && b0 + cc < d) ? V[i * ld + b0 + cc] : 0.f;
-        }
-        __syncthreads();
-        for (int kk = 0; kk < kn; ++kk) {
-            const float v = Vs[kk][col];
-#pragma unroll
-            for (int s = 0; s < QT_PER_THREAD; ++s) acc[s] = fmaf(Us[kk][rg + 4 * s], v, acc[s]);
-        }
-        __syncthreads();
-    }
-    const int b = b0 + col;
-    if (b < d) {
-#pragma unroll
-        for (int s = 0; s < QT_PER_THREAD; ++s) {
-            const int a = a0 + rg + 4 * s;
-            if (a < d) gM[rho * ldg + (int64_t)a * d + b] = acc[s];
-        }
-    }
-}
-
-inline int sc_grid(int64_t B)
-{
-    const int64_t blocks = (B + SC_WAVES - 1) / SC_WAVES;
-    return (int)(blocks < 8192 ? (blocks > 0 ? blocks : 1) : 8192);
-}
-
 int check_operator_kind(int kind, const float *E, const float *Rt, int d_ent, int d_rel)
 {
     if (kind != KGE_RESCAL && kind != KGE_HOLE) return KGE_EINVAL;
-    if (!E || !Rt || d_ent < 1 || d_ent > SC_MAXD) return KGE_EINVAL;
+    if (!E || !Rt || d_ent < 1 || d_ent > REL_MAXD) return KGE_EINVAL;
     if (d_rel != (kind == KGE_RESCAL ? d_ent * d_ent : d_ent)) return KGE_EINVAL;
     return 0;
 }
@@ -406,18 +245,19 @@ extern "C" int kge_bilinear_query(int kind, int side, const float *X, int64_t ld
 {
     if (kind != KGE_RESCAL && kind != KGE_HOLE) return KGE_EINVAL;
     if (side != KGE_SIDE_TAIL && side != KGE_SIDE_HEAD && side != KGE_SIDE_BOTH) return KGE_EINVAL;
-    if (d < 1 || d > 512 || B < 0 || ldx < d || ldq < d) return KGE_EINVAL;
+    if (d < 1 || d > REL_MAXD || B < 0 || ldx < d || ldq < d) return KGE_EINVAL;
     if (ldr < (kind == KGE_RESCAL ? (int64_t)d * d : (int64_t)d)) return KGE_EINVAL;
     if (B == 0) return 0;
     if (!X || !Rt || !r || !Q) return KGE_EINVAL;
     if ((side != KGE_SIDE_HEAD && !h) || (side != KGE_SIDE_TAIL && !t)) return KGE_EINVAL;
     const int64_t rows = side == KGE_SIDE_BOTH ? 2 * B : B;
     if ((rows + QT_ROWS - 1) / QT_ROWS > 0x7fffffffll) return KGE_EINVAL;
-    QueryParams p{kind, side, X, ldx, Rt, ldr, h, t, r, B, rows, d, ent_lo, ent_n, perm, Q, ldq};
+    const RelQueryIO io{X, ldx, perm, rows, Q, ldq};
+    const BilinearOp op{d, d, kind, side, Rt, ldr, h, t, r, B, ent_lo, ent_n};
     const dim3 grid((unsigned)((rows + QT_ROWS - 1) / QT_ROWS), (unsigned)((d + QT_COLS - 1) / QT_COLS));
     hipStream_t s = kge_s(stream);
-    if (d % QT_KC == 0) hipLaunchKernelGGL(bilinear_query_kernel<true>, grid, dim3(QT_THREADS), 0, s, p);
-    else hipLaunchKernelGGL(bilinear_query_kernel<false>, grid, dim3(QT_THREADS), 0, s, p);
+    if (d % QT_KC == 0) hipLaunchKernelGGL((rel_query_kernel<BilinearOp, true>), grid, dim3(QT_THREADS), 0, s, io, op);
+    else hipLaunchKernelGGL((rel_query_kernel<BilinearOp, false>), grid, dim3(QT_THREADS), 0, s, io, op);
     KGE_CHECK_LAUNCH();
     return 0;
 }
@@ -427,7 +267,7 @@ extern "C" int kge_bilinear_relation_rows(int kind, const float *H, int64_t ldh,
 {
     if (kind != KGE_RESCAL && kind != KGE_HOLE) return KGE_EINVAL;
     const int64_t w = kind == KGE_RESCAL ? (int64_t)d * d : d;
-    if (d < 1 || d > 512 || B < 0 || ldh < d || ldt < d || ldo < w) return KGE_EINVAL;
+    if (d < 1 || d > REL_MAXD || B < 0 || ldh < d || ldt < d || ldo < w) return KGE_EINVAL;
     if (B == 0) return 0;
     if (!H || !T || !out) return KGE_EINVAL;
     const int64_t n = B * w;
@@ -442,13 +282,9 @@ extern "C" int kge_rescal_rel_grad(const float *U, const float *V, int64_t ld, i
                                    const int64_t *perm, int64_t B, int64_t n_rel, float *gM, int64_t ldg,
                                    kge_stream_t stream)
 {
-    if (d < 1 || d > 512 || B < 0 || n_rel < 0 || ld < d || ldg < (int64_t)d * d) return KGE_EINVAL;
+    if (d < 1 || d > REL_MAXD || B < 0 || n_rel < 0 || ld < d || ldg < (int64_t)d * d) return KGE_EINVAL;
     if (n_rel == 0) return 0;
     if (!gM || (B > 0 && (!U || !V || !r || !perm))) return KGE_EINVAL;
     if (n_rel > 0x7fffffffll) return KGE_EINVAL;
-    const int nt = (d + QT_COLS - 1) / QT_COLS;
-    hipLaunchKernelGGL(rescal_rel_grad_kernel, dim3((unsigned)n_rel, (unsigned)(nt * nt)), dim3(256), 0, kge_s(stream),
-                       U, V, ld, d, r, perm, B, gM, ldg);
-    KGE_CHECK_LAUNCH();
-    return 0;
+    return kge_rel_outer_grad(U, ld, V, ld, d, d, r, perm, B, n_rel, gM, ldg, kge_s(stream));     // the square case
 }

@@ -32,6 +32,11 @@ int kge_transr_score_bwd(const float *E, const float *R, const float *M, int d_e
                          const int64_t *t, const int64_t *r, int64_t B, const float *go, float *rows, int64_t rows_ld,
                          hipStream_t s);
 
+// gM[rho] = sum over the triples of relation rho, in the order of perm, of U_i V_i^T (d_r x d_e): the reduction behind
+// kge_transr_rel_grad and, with d_r = d_e, kge_rescal_rel_grad, which validate their own arguments (transr_xform.hip)
+int kge_rel_outer_grad(const float *U, int64_t ldu, const float *V, int64_t ldv, int d_r, int d_e, const int64_t *r,
+                       const int64_t *perm, int64_t B, int64_t n_rel, float *gM, int64_t ldg, hipStream_t s);
+
 static inline bool kge_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Running maximum in a device scalar (non-negative floats compared as bit patterns).  Same-address atomics

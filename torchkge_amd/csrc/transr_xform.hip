@@ -7,18 +7,18 @@
 // This file holds what is specific to TransR:
 //   - kge_transr_proj_sqnorm: out[r, j] = || M_r x_j + b_r ||^2 on v_mfma_f32_32x32x2_f32; the projected rows live in
 //     accumulators only (the Z table of an evaluation; with x = e_h - e_t and b = rel_emb the relation-prediction scores);
-//   - kge_transr_query: q, u of a batch, rows grouped by relation (kge_key_sort), operator tiles staged in LDS once per group;
-//   - scoring_function forward / backward (through kge_score_triples / _bwd, kind KGE_TRANSR) and the relation-grouped
-//     reduction of d proj_mat (kge_transr_rel_grad).
+//   - kge_transr_query: q, u of a batch as two Ops of the relation-grouped transform of rel_operator.h (rows grouped by
+//     relation with kge_key_sort): M_r read row-wise with the +- R[r] finish, then M_r^T;
+//   - scoring_function forward / backward (through kge_score_triples / _bwd, kind KGE_TRANSR);
+//   - the per-relation outer-product reduction, rectangular: d proj_mat (kge_transr_rel_grad) and, square, RESCAL's
+//     d rel_mat (kge_rescal_rel_grad in bilinear_xform.hip) through kge_rel_outer_grad.
 // Every sum has a fixed order (-ffp-contract=off, explicit fmaf): no float atomics, and no result depends on the grid, on
 // where a row sits in a tile or on the rest of the batch.
-#include "kge_common.h"
+#include "rel_operator.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
-
-constexpr int TR_MAXD = 512;
 
 // ---- a. projected squared norms ------------------------------------------------------------------------------------
 // Block: 4 waves, one relation, 128 rows of X; wave w owns rows [32 w, 32 w + 32) for ALL output columns.  The output
@@ -163,124 +163,40 @@ __global__ __launch_bounds__(PN_THREADS) void proj_sqnorm_kernel(const ProjNormP
 // out[pos, j] = chain_k in(pos)[k] * C[k][j]  (+ sgn(pos) * R[rel(pos), j]),  k ascending, one accumulator per output.
 //   stage 1 (TO_REL):  in = entity rows (d_e), C[k][j] = M_r[j, k], j < d_r, bias = the relation row (tail +, head -)
 //   stage 2 (!TO_REL): in = the q rows of stage 1 (d_r), C[k][j] = M_r[k, j], j < d_e, no bias
-// Rows are visited in the order of `perm` (by relation): a tile of 64 sorted rows stages each operator tile once per run
-// of equal relation (bilinear_xform.hip's scheme, rectangular).
-constexpr int QT_ROWS = 64, QT_COLS = 64, QT_KC = 16, QT_THREADS = 256;
-constexpr int QT_PER_THREAD = QT_ROWS * QT_COLS / QT_THREADS;
-
-struct RQueryParams {
+// An Op of rel_query_kernel (rel_operator.h); a run is one relation: both sides read M_r in the same index order and
+// differ in the sign of the bias only.  Instantiated in the general form alone (no unrolled whole-chunk loop).
+struct TransROp {
+    int K, J;                           // stage 1: (d_e, d_r), stage 2: (d_r, d_e)
     int side, to_rel;
-    const float *X; int64_t ldx;        // stage 1: entity table (indexed by h / t) or gathered rows (h == t == NULL);
-                                        // stage 2: q rows by position
     const float *M; int64_t ldm;
     const float *R; int64_t ldr;        // stage 1 bias table (n_rel, d_r)
-    const int64_t *h, *t, *r;
-    int64_t n_facts, n_rows;
-    int d_e, d_r;
-    const int64_t *perm;
-    float *out; int64_t ldo;
-};
+    const int64_t *h, *t, *r;           // h, t: stage 1 over the entity table; NULL: the rows of X by position
+    int64_t n_facts;
+    int d_e;
 
-__global__ __launch_bounds__(QT_THREADS) void transr_query_kernel(const RQueryParams p)
-{
-    __shared__ float Xs[QT_ROWS][QT_KC + 1];
-    __shared__ float Bs[QT_KC][QT_COLS + 1];
-    __shared__ int64_t row_out[QT_ROWS], row_rel[QT_ROWS], row_src[QT_ROWS];
-    __shared__ float row_sgn[QT_ROWS];
-    __shared__ int run_lo[QT_ROWS + 1];
-    __shared__ int n_runs;
-    const int tid = threadIdx.x;
-    const int64_t p0 = (int64_t)blockIdx.x * QT_ROWS;
-    const int nr = (int)((p.n_rows - p0) < QT_ROWS ? (p.n_rows - p0) : QT_ROWS);
-    const int c0 = blockIdx.y * QT_COLS;
-    const int K = p.to_rel ? p.d_e : p.d_r, J = p.to_rel ? p.d_r : p.d_e;
-    if (tid < QT_ROWS) {
-        int64_t out = -1, rel = -1, src = 0;
-        float sgn = 0.f;
-        if (tid < nr) {
-            const int64_t pos = p.perm ? p.perm[p0 + tid] : p0 + tid;
-            const bool second = p.side == KGE_SIDE_BOTH && pos >= p.n_facts;
-            const bool head = p.side == KGE_SIDE_HEAD || second;
-            const int64_t f = second ? pos - p.n_facts : pos;
-            out = pos;
-            rel = p.r[f];
-            sgn = head ? -1.f : 1.f;
-            src = (p.to_rel && p.h) ? (head ? p.t[f] : p.h[f]) : pos;
-        }
-        row_out[tid] = out; row_rel[tid] = rel; row_src[tid] = src; row_sgn[tid] = sgn;
+    __device__ RelRow row(int64_t pos) const
+    {
+        const bool second = side == KGE_SIDE_BOTH && pos >= n_facts;
+        const bool head = side == KGE_SIDE_HEAD || second;
+        const int64_t f = second ? pos - n_facts : pos;
+        return RelRow{pos, r[f], (to_rel && h) ? (head ? t[f] : h[f]) : pos, head ? -1.f : 1.f};
     }
-    __syncthreads();
-    if (tid == 0) {
-        int n = 0;
-        for (int i = 0; i < nr; ++i)
-            if (i == 0 || row_rel[i] != row_rel[i - 1]) run_lo[n++] = i;
-        run_lo[n] = nr;
-        n_runs = n;
+    struct Coefs {
+        int to_rel, d_e;
+        const float *Mr;
+        __device__ bool k_contiguous() const { return to_rel != 0; }     // M[j][k]; stage 2 reads M[k][j]
+        __device__ float operator()(int k, int j) const { return to_rel ? Mr[(int64_t)j * d_e + k] : Mr[(int64_t)k * d_e + j]; }
+    };
+    __device__ Coefs coefs(int64_t rel) const { return Coefs{to_rel, d_e, M + rel * ldm}; }
+    __device__ float finish(const RelRow &w, int j, float acc) const
+    {
+        return (to_rel && R) ? fmaf(w.sgn, R[w.key * ldr + j], acc) : acc;
     }
-    __syncthreads();
-    const int col = tid & (QT_COLS - 1), rg = tid / QT_COLS;
-    float acc[QT_PER_THREAD];
-#pragma unroll
-    for (int s = 0; s < QT_PER_THREAD; ++s) acc[s] = 0.f;
-    for (int k0 = 0; k0 < K; k0 += QT_KC) {
-        const int kn = K - k0 < QT_KC ? K - k0 : QT_KC;
-        for (int idx = tid; idx < QT_ROWS * QT_KC; idx += QT_THREADS) {
-            const int rr = idx / QT_KC, kk = idx % QT_KC;
-            Xs[rr][kk] = (rr < nr && kk < kn) ? p.X[row_src[rr] * p.ldx + k0 + kk] : 0.f;
-        }
-        for (int ru = 0; ru < n_runs; ++ru) {
-            const int rs = run_lo[ru], re = run_lo[ru + 1];
-            const float *Mr = p.M + row_rel[rs] * p.ldm;
-            __syncthreads();
-            for (int idx = tid; idx < QT_KC * QT_COLS; idx += QT_THREADS) {
-                int kk, jj;
-                if (p.to_rel) { kk = idx % QT_KC; jj = idx / QT_KC; }       // M[j][k]: k contiguous
-                else { jj = idx % QT_COLS; kk = idx / QT_COLS; }            // M[k][j]: j contiguous
-                const int j = c0 + jj, k = k0 + kk;
-                float v = 0.f;
-                if (kk < kn && j < J) v = p.to_rel ? Mr[(int64_t)j * p.d_e + k] : Mr[(int64_t)k * p.d_e + j];
-                Bs[kk][jj] = v;
-            }
-            __syncthreads();
-            for (int kk = 0; kk < kn; ++kk) {
-                const float b = Bs[kk][col];
-#pragma unroll
-                for (int s = 0; s < QT_PER_THREAD; ++s) {
-                    const int row = rg + 4 * s;
-                    if (row >= rs && row < re) acc[s] = fmaf(Xs[row][kk], b, acc[s]);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    const int j = c0 + col;
-    if (j < J) {
-#pragma unroll
-        for (int s = 0; s < QT_PER_THREAD; ++s) {
-            const int row = rg + 4 * s;
-            if (row < nr) {
-                float v = acc[s];
-                if (p.to_rel && p.R) v = fmaf(row_sgn[row], p.R[row_rel[row] * p.ldr + j], v);
-                p.out[row_out[row] * p.ldo + j] = v;
-            }
-        }
-    }
-}
+};
 
 // ---- c. scoring_function --------------------------------------------------------------------------------------------
 // x^ = x / max(||x||, 1e-12) of the gathered h, t rows, v = h^ - t^, p_c = chain_k M_r[c, k] v_k (k ascending) + r_c,
 // score = -sum_c p_c^2 (lanes over c, fmaf per lane in ascending c, then the wavefront tree).  One triple per wave.
-constexpr int SC_WAVES = 4;
-
-__device__ __forceinline__ float load_normalized(const float *__restrict__ x, int d, int lane, float *xs)
-{
-    float ss = 0.f;
-    for (int k = lane; k < d; k += 64) ss = fmaf(x[k], x[k], ss);
-    const float n = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
-    for (int k = lane; k < d; k += 64) xs[k] = x[k] / n;
-    return n;
-}
-
 struct RScoreParams {
     const float *E, *R, *M;
     int d_e, d_r;
@@ -294,7 +210,7 @@ struct RScoreParams {
 
 __global__ __launch_bounds__(SC_WAVES * 64) void transr_score_fwd_kernel(const RScoreParams p)
 {
-    __shared__ float hs[SC_WAVES][TR_MAXD], ts[SC_WAVES][TR_MAXD];
+    __shared__ float hs[SC_WAVES][REL_MAXD], ts[SC_WAVES][REL_MAXD];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, d_e = p.d_e, d_r = p.d_r;
     for (int64_t base = (int64_t)blockIdx.x * SC_WAVES; base < p.B; base += (int64_t)gridDim.x * SC_WAVES) {
         const int64_t i = base + w;
@@ -329,7 +245,7 @@ __global__ __launch_bounds__(SC_WAVES * 64) void transr_score_fwd_kernel(const R
 // left operand of kge_transr_rel_grad), 3: v = h^ - t^ (its right operand)
 __global__ __launch_bounds__(SC_WAVES * 64) void transr_score_bwd_kernel(const RScoreParams p)
 {
-    __shared__ float hs[SC_WAVES][TR_MAXD], ts[SC_WAVES][TR_MAXD], vs[SC_WAVES][TR_MAXD], gs[SC_WAVES][TR_MAXD];
+    __shared__ float hs[SC_WAVES][REL_MAXD], ts[SC_WAVES][REL_MAXD], vs[SC_WAVES][REL_MAXD], gs[SC_WAVES][REL_MAXD];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, d_e = p.d_e, d_r = p.d_r;
     for (int64_t base = (int64_t)blockIdx.x * SC_WAVES; base < p.B; base += (int64_t)gridDim.x * SC_WAVES) {
         const int64_t i = base + w;
@@ -363,9 +279,9 @@ __global__ __launch_bounds__(SC_WAVES * 64) void transr_score_bwd_kernel(const R
             for (int k = lane; k < d_e; k += 64) V[k] = vs[w][k];
             // d v_k = chain_c M_r[c, k] g_c;  d h^ = d v, d t^ = -d v
             float sh = 0.f, st = 0.f;
-            float dv[TR_MAXD / 64];
+            float dv[REL_MAXD / 64];
 #pragma unroll
-            for (int q = 0; q < TR_MAXD / 64; ++q) {
+            for (int q = 0; q < REL_MAXD / 64; ++q) {
                 const int k = lane + 64 * q;
                 float u = 0.f;
                 if (k < d_e) {
@@ -379,7 +295,7 @@ __global__ __launch_bounds__(SC_WAVES * 64) void transr_score_bwd_kernel(const R
             const bool ch = nh <= 1e-12f, ct = nt <= 1e-12f;
             float *DH = p.rows + i * p.rows_ld, *DT = p.rows + ((int64_t)p.B + i) * p.rows_ld;
 #pragma unroll
-            for (int q = 0; q < TR_MAXD / 64; ++q) {
+            for (int q = 0; q < REL_MAXD / 64; ++q) {
                 const int k = lane + 64 * q;
                 if (k < d_e) {
                     DH[k] = ch ? dv[q] / nh : (dv[q] - hs[w][k] * sh) / nh;
@@ -391,15 +307,17 @@ __global__ __launch_bounds__(SC_WAVES * 64) void transr_score_bwd_kernel(const R
     }
 }
 
-// d proj_mat, relation-grouped: gM[rho][a * d_e + b] = sum over the triples of rho, in sorted order, of U_i[a] V_i[b]
-// (a < d_r, b < d_e).  One block per (relation, 64 x 64 tile); rho's segment of perm by binary search.
-constexpr int RG_KC = 16;
+// ---- d. the per-relation outer-product reduction --------------------------------------------------------------------
+// d proj_mat, and with d_r = d_e RESCAL's d rel_mat (kge_rel_outer_grad): gM[rho][a * d_e + b] = sum over the triples of
+// rho, in sorted order, of U_i[a] V_i[b] (a < d_r, b < d_e) -- a GEMM whose K is the relation's triples.  One block per
+// (relation, 64 x 64 tile); rho's segment of perm by binary search.
+constexpr int RG_KC = 16;       // triples staged per step
 
-__global__ __launch_bounds__(256) void transr_rel_grad_kernel(const float *__restrict__ U, int64_t ldu,
-                                                              const float *__restrict__ V, int64_t ldv, int d_r, int d_e,
-                                                              const int64_t *__restrict__ r,
-                                                              const int64_t *__restrict__ perm, int64_t B,
-                                                              float *__restrict__ gM, int64_t ldg)
+__global__ __launch_bounds__(256) void rel_outer_grad_kernel(const float *__restrict__ U, int64_t ldu,
+                                                             const float *__restrict__ V, int64_t ldv, int d_r, int d_e,
+                                                             const int64_t *__restrict__ r,
+                                                             const int64_t *__restrict__ perm, int64_t B,
+                                                             float *__restrict__ gM, int64_t ldg)
 {
     __shared__ float Us[RG_KC][QT_COLS + 1], Vs[RG_KC][QT_COLS + 1];
     __shared__ int64_t seg[2];
@@ -452,20 +370,26 @@ __global__ __launch_bounds__(256) void transr_rel_grad_kernel(const float *__res
     }
 }
 
-inline int sc_grid(int64_t B)
-{
-    const int64_t blocks = (B + SC_WAVES - 1) / SC_WAVES;
-    return (int)(blocks < 8192 ? (blocks > 0 ? blocks : 1) : 8192);
-}
-
 inline int check_dims(int d_e, int d_r)
 {
     if (d_e < 1 || d_r < 1) return KGE_EINVAL;
-    if (d_e > TR_MAXD || d_r > TR_MAXD) return KGE_EUNSUPPORTED;
+    if (d_e > REL_MAXD || d_r > REL_MAXD) return KGE_EUNSUPPORTED;
     return 0;
 }
 
 } // namespace
+
+// the reduction behind kge_transr_rel_grad and kge_rescal_rel_grad (declared in kge_common.h): arguments validated by
+// the caller, n_rel in [1, 2^31)
+int kge_rel_outer_grad(const float *U, int64_t ldu, const float *V, int64_t ldv, int d_r, int d_e, const int64_t *r,
+                       const int64_t *perm, int64_t B, int64_t n_rel, float *gM, int64_t ldg, hipStream_t s)
+{
+    const int nta = (d_r + QT_COLS - 1) / QT_COLS, ntb = (d_e + QT_COLS - 1) / QT_COLS;
+    hipLaunchKernelGGL(rel_outer_grad_kernel, dim3((unsigned)n_rel, (unsigned)(nta * ntb)), dim3(256), 0, s,
+                       U, ldu, V, ldv, d_r, d_e, r, perm, B, gM, ldg);
+    KGE_CHECK_LAUNCH();
+    return 0;
+}
 
 // KGE_TRANSR behind kge_score_triples / kge_score_triples_bwd (declared in kge_common.h)
 int kge_transr_score_fwd(const float *E, const float *R, const float *M, int d_ent, int d_rel, const int64_t *h,
@@ -533,15 +457,17 @@ extern "C" int kge_transr_query(int side, const float *X, int64_t ldx, const flo
     if (tiles > 0x7fffffffll) return KGE_EINVAL;
     hipStream_t s = kge_s(stream);
     if (X) {            // X NULL: Q is given (a query already in relation space), only U is computed
-        RQueryParams p{side, 1, X, ldx, M, ldm, R, ldr, h, t, r, B, rows, d_e, d_r, perm, Q, ldq};
-        hipLaunchKernelGGL(transr_query_kernel, dim3((unsigned)tiles, (unsigned)((d_r + QT_COLS - 1) / QT_COLS)),
-                           dim3(QT_THREADS), 0, s, p);
+        const RelQueryIO io{X, ldx, perm, rows, Q, ldq};
+        const TransROp op{d_e, d_r, side, 1, M, ldm, R, ldr, h, t, r, B, d_e};
+        hipLaunchKernelGGL((rel_query_kernel<TransROp, false>), dim3((unsigned)tiles, (unsigned)((d_r + QT_COLS - 1) / QT_COLS)),
+                           dim3(QT_THREADS), 0, s, io, op);
         KGE_CHECK_LAUNCH();
     }
     if (U) {
-        RQueryParams p2{side, 0, Q, ldq, M, ldm, nullptr, 0, nullptr, nullptr, r, B, rows, d_e, d_r, perm, U, ldu};
-        hipLaunchKernelGGL(transr_query_kernel, dim3((unsigned)tiles, (unsigned)((d_e + QT_COLS - 1) / QT_COLS)),
-                           dim3(QT_THREADS), 0, s, p2);
+        const RelQueryIO io{Q, ldq, perm, rows, U, ldu};
+        const TransROp op{d_r, d_e, side, 0, M, ldm, nullptr, 0, nullptr, nullptr, r, B, d_e};
+        hipLaunchKernelGGL((rel_query_kernel<TransROp, false>), dim3((unsigned)tiles, (unsigned)((d_e + QT_COLS - 1) / QT_COLS)),
+                           dim3(QT_THREADS), 0, s, io, op);
         KGE_CHECK_LAUNCH();
     }
     return 0;
@@ -557,9 +483,5 @@ extern "C" int kge_transr_rel_grad(const float *U, int64_t ldu, const float *V, 
     if (n_rel == 0) return 0;
     if (!gM || (B > 0 && (!U || !V || !r || !perm))) return KGE_EINVAL;
     if (n_rel > 0x7fffffffll) return KGE_EINVAL;
-    const int nta = (d_r + QT_COLS - 1) / QT_COLS, ntb = (d_e + QT_COLS - 1) / QT_COLS;
-    hipLaunchKernelGGL(transr_rel_grad_kernel, dim3((unsigned)n_rel, (unsigned)(nta * ntb)), dim3(256), 0, kge_s(stream),
-                       U, ldu, V, ldv, d_r, d_e, r, perm, B, gM, ldg);
-    KGE_CHECK_LAUNCH();
-    return 0;
+    return kge_rel_outer_grad(U, ldu, V, ldv, d_r, d_e, r, perm, B, n_rel, gM, ldg, kge_s(stream));
 }
