@@ -2,7 +2,7 @@
 """Negative samplers with the reference's interface (torchkge/sampling.py:16-592):
 ``NegativeSampler``, ``UniformNegativeSampler``, ``BernoulliNegativeSampler``
 (``.bern_probs``, ``.corrupt_batch(heads, tails, relations, n_neg=None)``,
-``.corrupt_kg(batch_size, use_cuda, which)``), ``PositionalNegativeSampler``
+``.corrupt_kg(batch_size, use_cuda, which, on_device=False)``), ``PositionalNegativeSampler``
 (``.possible_heads / .possible_tails / .n_poss_heads / .n_poss_tails``),
 ``BernoulliRelationNegativeSampler`` (``.bern_probs``, ``.rel_share``; three
 vectors out) and ``get_possible_heads_tails``.
@@ -48,22 +48,42 @@ class NegativeSampler:
         self.n_facts_val = 0 if kg_val is None else kg_val.n_facts
         self.n_facts_test = 0 if kg_test is None else kg_test.n_facts
         self.sync_free = False
+        self._device_graphs = {}        # id(graph) -> its three vectors on the GPU (corrupt_kg(on_device=True))
+
+    def _device_graph(self, kg):
+        """(heads, tails, relations) of ``kg`` on the GPU, uploaded once per sampler."""
+        hit = self._device_graphs.get(id(kg))
+        if hit is None:
+            hit = self._device_graphs[id(kg)] = (kg.head_idx.cuda(), kg.tail_idx.cuda(), kg.relations.cuda())
+        return hit
 
     def corrupt_batch(self, heads, tails, relations, n_neg):
         raise NotYetImplementedError('NegativeSampler is just an interface, please consider using '
                                      'a child class where this is implemented.')
 
-    def corrupt_kg(self, batch_size, use_cuda, which='main'):
-        """Corrupt a whole graph batch by batch with n_neg=1 (sampling.py:76-138)."""
+    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False):
+        """Corrupt a whole graph batch by batch with n_neg=1 (sampling.py:76-138): the reference's driver, host tensors
+        out.  ``on_device=True`` takes the graph's vectors to the GPU once, corrupts slices of them and returns the two
+        negative vectors as device tensors: nothing goes through the host (what TrainDataLoader with use_cuda='all' and
+        TripletClassificationEvaluator use)."""
         assert which in ['main', 'train', 'test', 'val']
         if which == 'val':
             assert self.n_facts_val > 0
         if which == 'test':
             assert self.n_facts_test > 0
-        tmp_cuda = 'batch' if use_cuda else None
         kg = self.kg_val if which == 'val' else (self.kg_test if which == 'test' else self.kg)
-        dataloader = DataLoader(kg, batch_size=batch_size, use_cuda=tmp_cuda)
         corr_heads, corr_tails = [], []
+        if on_device:
+            assert kg is not None and kg.n_facts > 0
+            h, t, r = self._device_graph(kg)
+            for lo in range(0, h.shape[0], batch_size):
+                sl = slice(lo, lo + batch_size)
+                neg_heads, neg_tails = self.corrupt_batch(h[sl], t[sl], r[sl], n_neg=1)
+                corr_heads.append(neg_heads)
+                corr_tails.append(neg_tails)
+            return cat(corr_heads).long(), cat(corr_tails).long()
+        tmp_cuda = 'batch' if use_cuda else None
+        dataloader = DataLoader(kg, batch_size=batch_size, use_cuda=tmp_cuda)
         for batch in dataloader:
             neg_heads, neg_tails = self.corrupt_batch(batch[0], batch[1], batch[2], n_neg=1)
             corr_heads.append(neg_heads)
@@ -265,23 +285,6 @@ class PositionalNegativeSampler(BernoulliNegativeSampler):
         return _hip_triplet.positional_corrupt(heads, tails, relations, mask.to(torch.uint8), u_h, u_t, fb_h, fb_t,
                                                ih.offsets, ih.values, it.offsets, it.values, self.n_rel)
 
-    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False):
-        """The reference's driver (host tensors out); ``on_device=True`` keeps the graph's vectors and the negatives
-        on the GPU from end to end (what TripletClassificationEvaluator uses)."""
-        if not on_device:
-            return super().corrupt_kg(batch_size, use_cuda, which)
-        assert which in ['main', 'train', 'test', 'val']
-        kg = self.kg_val if which == 'val' else (self.kg_test if which == 'test' else self.kg)
-        assert kg is not None and kg.n_facts > 0
-        h, t, r = kg.head_idx.cuda(), kg.tail_idx.cuda(), kg.relations.cuda()
-        corr_heads, corr_tails = [], []
-        for lo in range(0, h.shape[0], batch_size):
-            sl = slice(lo, lo + batch_size)
-            neg_heads, neg_tails = self.corrupt_batch(h[sl], t[sl], r[sl], n_neg=1)
-            corr_heads.append(neg_heads)
-            corr_tails.append(neg_tails)
-        return cat(corr_heads), cat(corr_tails)
-
 
 class BernoulliRelationNegativeSampler(NegativeSampler):
     """Corrupts either the relation of a fact or, with the Bernoulli choice of Wang et al. 2014, its head or its tail
@@ -361,7 +364,7 @@ class BernoulliRelationNegativeSampler(NegativeSampler):
         kg = self.kg_val if which == 'val' else (self.kg_test if which == 'test' else self.kg)
         out = ([], [], [])
         if on_device:
-            h, t, r = kg.head_idx.cuda(), kg.tail_idx.cuda(), kg.relations.cuda()
+            h, t, r = self._device_graph(kg)
             batches = ((h[lo:lo + batch_size], t[lo:lo + batch_size], r[lo:lo + batch_size])
                        for lo in range(0, h.shape[0], batch_size))
         else:

@@ -10,8 +10,6 @@ from .operations import get_rank, get_mask, get_bernoulli_probs, get_tph, get_hp
 
 def __getattr__(name):
     if name in ('Trainer', 'TrainDataLoader'):
-        raise NotProvidedError('torchkge_amd.utils does not provide %s (torchkge/utils/training.py is host glue outside the hot '
-                          'path): write the tutorial loop around Model.forward -- sampler.corrupt_batch, model(h, t, r, nh, '
-                          'nt), criterion, backward, optimizer.step -- see tests/test_reference_style.py and INTEGRATION.md'
-                          % name)
+        raise NotProvidedError('torchkge_amd.utils does not provide %s at this level yet -- import it from '
+                               'torchkge_amd.utils.training, the module the reference keeps it in (see INTEGRATION.md)' % name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -1,0 +1,197 @@
+# -*- coding: utf-8 -*-
+"""``TrainDataLoader`` and ``Trainer`` with the reference's interface (torchkge/utils/training.py:15-200), so that the
+reference's training tutorial runs with the import changed:
+
+    from torchkge_amd.utils.training import Trainer
+    trainer = Trainer(model, criterion, kg_train, n_epochs, batch_size, optimizer, sampling_type='bern', use_cuda='all')
+    trainer.run()
+
+What is the engine's own:
+  * with ``fused=True`` (the default) a criterion of ``utils/losses.py`` is replaced by its fused counterpart
+    (``utils/fused_losses.py``: loss and gradients from one kge_pair_loss, finite in saturation); any other criterion
+    takes the generic path -- forward, ``criterion(p, n)``, backward, step;
+  * an optimizer of ``torchkge_amd.optim`` makes every step run inside ``row_gradients()``;
+  * ``sync_free=True``: ``run()`` reads nothing back -- the sampler draws without its host read, the steps add their loss
+    into one device float per epoch, ``epoch_losses`` fetches the epoch sums on first access;
+  * ``sampler=``: any object with a ``corrupt_kg`` instead of the two built-in samplers;
+  * ``get_counter_examples()`` is None before ``run()`` and the last epoch's negatives after it (the reference's
+    ``run`` asks its loader for them before the first iteration and raises).
+
+The models live on the GPU: ``use_cuda`` is 'all' or 'batch'."""
+import contextlib
+
+import torch
+
+from .. import optim
+from ..data_structures import SmallKG
+from ..rowgrad import row_gradients
+from ..sampling import BernoulliNegativeSampler, UniformNegativeSampler
+from .data import get_n_batches
+from .fused_losses import fused_for
+
+
+class TrainDataLoader:
+    """Batches of true and negatively sampled facts: dicts with the keys ``h, t, r, nh, nt``, the last one short.  Every
+    ``__iter__`` corrupts the whole graph anew (``sampler.corrupt_kg``).
+
+    ``use_cuda``: None (host tensors), 'batch' (each batch is moved when it is returned) or 'all' (the graph's vectors
+    move once, the negatives are drawn on the device and the batches are slices: nothing goes through the host).
+    ``sampler``: an object with ``corrupt_kg(batch_size, use_cuda, on_device=...)``; ``sampling_type`` ('unif' / 'bern')
+    is then ignored.  ``sync_free=True`` sets the sampler's ``sync_free`` flag."""
+
+    def __init__(self, kg, batch_size, sampling_type, use_cuda=None, *, sampler=None, sync_free=False):
+        self.h, self.t, self.r = kg.head_idx, kg.tail_idx, kg.relations
+        self.use_cuda = use_cuda
+        self.b_size = batch_size
+        self.iterator = None
+        if sampler is not None:
+            self.sampler = sampler
+        elif sampling_type == 'unif':
+            self.sampler = UniformNegativeSampler(kg)
+        elif sampling_type == 'bern':
+            self.sampler = BernoulliNegativeSampler(kg)
+        else:
+            raise ValueError("sampling_type is 'unif' or 'bern', got %r" % (sampling_type,))
+        if sync_free:
+            self.sampler.sync_free = True
+        self.tmp_cuda = use_cuda in ['batch', 'all']
+        if use_cuda == 'all':
+            self.h, self.t, self.r = self.h.cuda(), self.t.cuda(), self.r.cuda()
+
+    def __len__(self):
+        return get_n_batches(len(self.h), self.b_size)
+
+    def __iter__(self):
+        self.iterator = TrainDataLoaderIter(self)
+        return self.iterator
+
+    def get_counter_examples(self):
+        """``SmallKG(nh, nt, r)`` of the latest ``__iter__``; None before the first."""
+        if self.iterator is None:
+            return None
+        return SmallKG(self.iterator.nh, self.iterator.nt, self.iterator.r)
+
+
+class TrainDataLoaderIter:
+    def __init__(self, loader):
+        self.h, self.t, self.r = loader.h, loader.t, loader.r
+        if loader.use_cuda == 'all':
+            self.nh, self.nt = loader.sampler.corrupt_kg(loader.b_size, True, on_device=True)
+        else:
+            self.nh, self.nt = loader.sampler.corrupt_kg(loader.b_size, loader.tmp_cuda)
+        if loader.use_cuda:
+            self.nh, self.nt = self.nh.cuda(), self.nt.cuda()
+        self.use_cuda = loader.use_cuda
+        self.b_size = loader.b_size
+        self.n_batches = get_n_batches(len(self.h), self.b_size)
+        self.current_batch = 0
+
+    def __next__(self):
+        if self.current_batch == self.n_batches:
+            raise StopIteration
+        sl = slice(self.current_batch * self.b_size, (self.current_batch + 1) * self.b_size)
+        self.current_batch += 1
+        batch = {'h': self.h[sl], 't': self.t[sl], 'r': self.r[sl], 'nh': self.nh[sl], 'nt': self.nt[sl]}
+        if self.use_cuda == 'batch':
+            batch = {k: v.cuda() for k, v in batch.items()}
+        return batch
+
+    def __iter__(self):
+        return self
+
+
+class Trainer:
+    """The reference's training procedure: per epoch a fresh corruption of ``kg_train``, one step per batch,
+    ``model.normalize_parameters()``; the mean loss of every epoch is kept in ``epoch_losses``."""
+
+    def __init__(self, model, criterion, kg_train, n_epochs, batch_size, optimizer, sampling_type='bern', use_cuda=None,
+                 *, fused=True, sync_free=False, sampler=None, verbose=True):
+        if use_cuda not in ('all', 'batch'):
+            raise ValueError("Trainer: use_cuda must be 'all' or 'batch', got %r -- the engine's models live on the GPU, "
+                             "there is no CPU training path" % (use_cuda,))
+        self.model = model
+        self.criterion = criterion
+        self.kg_train = kg_train
+        self.use_cuda = use_cuda
+        self.n_epochs = n_epochs
+        self.optimizer = optimizer
+        self.sampling_type = sampling_type
+        self.batch_size = batch_size
+        self.n_triples = len(kg_train)
+        self.fused = fused
+        self.sync_free = sync_free
+        self.sampler = sampler
+        self.verbose = verbose
+        self.counter_examples = None
+        self._fused_criterion = fused_for(criterion) if fused else None
+        self._row_mode = isinstance(optimizer, (optim.RowSGD, optim.RowAdagrad, optim.RowAdam))
+        self._loader = None
+        self._epoch_losses = []
+        self._epoch_sums = None         # sync_free: (device vector of the epochs' loss sums, batches per epoch)
+
+    def _step(self, batch, acc=None):
+        """One training step; the loss as a device scalar, also added to the device float ``acc`` when given."""
+        with row_gradients() if self._row_mode else contextlib.nullcontext():
+            self.optimizer.zero_grad()
+            p, n = self.model(batch['h'], batch['t'], batch['r'], batch['nh'], batch['nt'])
+            if self._fused_criterion is not None:
+                loss = self._fused_criterion(p, n, acc)
+            else:
+                loss = self.criterion(p, n)
+                if acc is not None:
+                    acc.add_(loss.detach())
+            loss.backward()
+            self.optimizer.step()
+        return loss.detach()
+
+    def process_batch(self, current_batch):
+        """One step on a batch of the loader; its loss as a Python float (the step's one host read)."""
+        return self._step(current_batch).item()
+
+    def run(self):
+        self.model.cuda()
+        if isinstance(self.criterion, torch.nn.Module):
+            self.criterion.cuda()
+        epochs = range(self.n_epochs)
+        bar = None
+        if self.verbose:
+            try:
+                from tqdm.autonotebook import tqdm
+                epochs = bar = tqdm(epochs, unit='epoch')
+            except ImportError:
+                pass
+        if self._loader is None:        # kept: a later run() uploads nothing again
+            self._loader = TrainDataLoader(self.kg_train, batch_size=self.batch_size, sampling_type=self.sampling_type,
+                                           use_cuda=self.use_cuda, sampler=self.sampler, sync_free=self.sync_free)
+        data_loader = self._loader
+        self._epoch_losses, self._epoch_sums = [], None
+        if self.sync_free:
+            device = next(self.model.parameters()).device
+            self._epoch_sums = (torch.zeros(self.n_epochs, dtype=torch.float32, device=device), len(data_loader))
+        for epoch in epochs:
+            if self.sync_free:
+                acc = self._epoch_sums[0][epoch]        # a view: the steps add into the vector's own element
+                for batch in data_loader:
+                    self._step(batch, acc)
+            else:
+                sum_ = 0
+                for batch in data_loader:
+                    sum_ += self.process_batch(batch)
+                self._epoch_losses.append(sum_ / len(data_loader))
+                if bar is not None:
+                    bar.set_description('Epoch {} | mean loss: {:.5f}'.format(epoch + 1, self._epoch_losses[-1]))
+            self.model.normalize_parameters()
+            self.counter_examples = data_loader.get_counter_examples()
+
+    @property
+    def epoch_losses(self):
+        """The mean step loss of every epoch of the last ``run()``, as Python floats.  After a ``sync_free`` run the
+        first access reads the epoch sums back (one copy)."""
+        if self._epoch_sums is not None:
+            sums, n_batches = self._epoch_sums
+            self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
+        return self._epoch_losses
+
+    def get_counter_examples(self):
+        """The counter-examples of the last epoch as a ``SmallKG``; None before ``run()``."""
+        return self.counter_examples
