@@ -43,6 +43,7 @@ def test_library_exports_every_symbol_the_header_declares():
         assert hasattr(lib, name), name
     from torchkge_amd.csrc import build as hb
     assert 'segment_sum_ordered.hip' in hb.SOURCES and 'segment_levels.h' in hb.HEADERS
+    assert 'segment_sum_rows.hip' in hb.SOURCES
     assert any(h.endswith('kge_hip_det.h') for h in hb.HEADERS)
     for h in hb.HEADERS:
         assert os.path.exists(os.path.join(hb.HERE, h)), h

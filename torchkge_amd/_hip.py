@@ -368,6 +368,24 @@ def sort_perm(keys, n_keys):
         return _key_perm(keys, None, n_keys)
 
 
+def _bwd_layout(kind, d_ent, d_rel):
+    """(streams, tail, ld, n_streams) of kge_score_triples_bwd's rows buffer: the row streams of `kind`, its per-relation
+    tail (or None), the leading dimension of every row and the number of streams the kernel writes."""
+    streams, tail = _BWD_STREAMS[kind], _BWD_REL_TAIL.get(kind)
+    ld = max(d_ent, d_rel) if kind == TRANSR else d_ent
+    return streams, tail, ld, 4 if tail else max(s0 + ns for _, s0, ns, _ in streams)
+
+
+def _bwd_rel_tail(lib, tail, rows, ld, d_ent, d_rel, r, perm, g):
+    """The per-relation matrix gradient `g` of a _BWD_REL_TAIL kind, from the rows U, V of streams 2 / 3 and the order
+    `perm` of the relation ids."""
+    _, name, args = tail
+    B = r.shape[0]
+    U, V = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
+    _check(getattr(lib, name)(*(args(U, V, ld, d_ent, d_rel) + (_p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
+                                                                 _stream()))), name)
+
+
 def _score_triples_bwd_rows(lib, kind, tabs, n_tables, d_ent, d_rel, h, t, r, go, needs):
     """score_triples_bwd in row-gradient mode (torchkge_amd.rowgrad): the gradient of every table with row streams is
     the uncoalesced sparse tensor (ids, per-triple rows) -- a view of the rows buffer where the stream's leading
@@ -376,9 +394,7 @@ def _score_triples_bwd_rows(lib, kind, tabs, n_tables, d_ent, d_rel, h, t, r, go
     reduced as ever into a dense gradient."""
     from ._hip_rows import sparse_rows
     B, dev = h.shape[0], h.device
-    streams, tail = _BWD_STREAMS[kind], _BWD_REL_TAIL.get(kind)
-    ld = max(d_ent, d_rel) if kind == TRANSR else d_ent
-    n_streams = 4 if tail else max(s0 + ns for _, s0, ns, _ in streams)
+    streams, tail, ld, n_streams = _bwd_layout(kind, d_ent, d_rel)
     rows = torch.empty(n_streams * B * ld, dtype=torch.float32, device=dev)
     grads = [None] * n_tables
     with _on(dev):
@@ -395,13 +411,9 @@ def _score_triples_bwd_rows(lib, kind, tabs, n_tables, d_ent, d_rel, h, t, r, go
                 vals = rows[s0 * B * ld:(s0 + ns) * B * ld].view(ns * B, ld)
                 grads[ti] = sparse_rows(ids[key], vals if ld == d else vals[:, :d].contiguous(), tabs[ti].shape)
         if tail and needs[tail[0]]:
-            ti, name, args = tail
-            g = grads[ti] = torch.zeros_like(tabs[ti])
+            g = grads[tail[0]] = torch.zeros_like(tabs[tail[0]])
             if B:
-                perm = _key_perm(r, None, g.shape[0])
-                U, V = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
-                _check(getattr(lib, name)(*(args(U, V, ld, d_ent, d_rel) + (_p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
-                                                                             _stream()))), name)
+                _bwd_rel_tail(lib, tail, rows, ld, d_ent, d_rel, r, _key_perm(r, None, g.shape[0]), g)
     return [g if n else None for g, n in zip(grads, needs)]
 
 
@@ -423,13 +435,11 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs, row_
     grads = [torch.zeros_like(x) for x in tabs[:len(tables)]] + [None] * (4 - len(tables))
     B = h.shape[0]
     dev = h.device
-    streams, tail = _BWD_STREAMS[kind], _BWD_REL_TAIL.get(kind)
+    streams, tail, ld, n_streams = _bwd_layout(kind, d_ent, d_rel)
     # the atomic mode: the kernel adds element by element into the zeroed gradient tables, no rows.  (TorusE: always the
     # row mode -- no per-element float atomics; the same bits on every run need the deterministic mode, which sums the
     # rows through kge_segment_sum_ordered)
     atomic = B < BWD_SORTED_MIN_BATCH and kind in _BWD_ATOMIC and (not det or B == 0)
-    ld = max(d_ent, d_rel) if kind == TRANSR else d_ent
-    n_streams = 4 if tail else max(s0 + ns for _, s0, ns, _ in streams)
     rows = None if atomic else torch.empty(n_streams * B * ld, dtype=torch.float32, device=dev)
     gp = grads if atomic else [None] * 4
     with _on(dev):
@@ -446,12 +456,9 @@ def score_triples_bwd(kind, tables, d_ent, d_rel, h, t, r, grad_out, needs, row_
                     perms[key] = _hip_det.reduce_rows(rows.data_ptr() + s0 * B * ld * 4, ld, g.shape[1], k0, k1, g,
                                                       perm=perms[key], det=det)
             if tail and needs[tail[0]]:
-                ti, name, args = tail
-                g = grads[ti]
+                g = grads[tail[0]]
                 perm = perms['r'] if perms['r'] is not None else _key_perm(r, None, g.shape[0])
-                U, V = rows.data_ptr() + 2 * B * ld * 4, rows.data_ptr() + 3 * B * ld * 4
-                _check(getattr(lib, name)(*(args(U, V, ld, d_ent, d_rel) + (_p(r), _p(perm), B, g.shape[0], _p(g), g.stride(0),
-                                                                             _stream()))), name)
+                _bwd_rel_tail(lib, tail, rows, ld, d_ent, d_rel, r, perm, g)
     return [g if n else None for g, n in zip(grads[:len(tables)], needs)]
 
 

@@ -4,7 +4,7 @@
 // target id with one atomic row-add per run -- which needs the positions of [k0 | k1] ordered by id.  The ids are
 // entity / relation indices (< 2^key_bits), so a device radix sort over key_bits bits of (id, position) pairs does it in
 // two or three passes: rocPRIM's radix_sort_pairs on 32-bit keys and a counting iterator for the positions.
-// (kge_key_hist / kge_key_scatter in score_triples.hip are the counting-sort alternative: their wave-aggregated atomics
+// (kge_key_hist / kge_key_scatter at the end of this file are the counting-sort alternative: their wave-aggregated atomics
 // walk up to 64 distinct ids per wavefront one after the other, 113 us per id stream at B = 32768 against ~25 here.)
 #include "kge_common.h"
 #include <cstring>
@@ -25,6 +25,58 @@ __global__ void perm_widen_kernel(const unsigned *__restrict__ pos, int64_t n, i
 {
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x)
         perm[j] = (int64_t)pos[j];
+}
+
+// counting sort of small-integer keys (entity / relation ids): histogram, (host: cumsum), scatter.
+// Atomics are aggregated per wavefront: one atomic per DISTINCT key among a wavefront's 64 keys.  Real
+// graphs are heavy-tailed (a hub entity / relation owns 10% of a batch) and same-address atomics
+// serialise at ~12 ns each past the L2s: 100 us per launch at B = 32768 on a Zipf batch before this.
+__device__ __forceinline__ int64_t readlane64(int64_t v, int src)
+{
+    const unsigned lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), src);
+    const unsigned hi = __builtin_amdgcn_readlane((int)((uint64_t)v >> 32), src);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__global__ void key_hist_kernel(const int64_t *__restrict__ k0, int64_t n0, const int64_t *__restrict__ k1, int64_t n1,
+                                int32_t *hist)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n = n0 + n1, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t jb = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; jb < n; jb += stride) {   // wave-uniform trip count
+        const int64_t j = jb + lane;
+        const bool act = j < n;
+        const int64_t key = act ? (j < n0 ? k0[j] : k1[j - n0]) : -1;
+        unsigned long long todo = __ballot(act);
+        while (todo) {
+            const int lead = __ffsll((long long)todo) - 1;
+            const int64_t kl = readlane64(key, lead);
+            const unsigned long long same = __ballot(act && key == kl);
+            if (lane == lead) atomicAdd(&hist[kl], (int)__popcll(same));
+            todo &= ~same;
+        }
+    }
+}
+__global__ void key_scatter_kernel(const int64_t *__restrict__ k0, int64_t n0, const int64_t *__restrict__ k1,
+                                   int64_t n1, const int64_t *__restrict__ offsets, int32_t *cursor, int64_t *perm)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n = n0 + n1, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t jb = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; jb < n; jb += stride) {
+        const int64_t j = jb + lane;
+        const bool act = j < n;
+        const int64_t key = act ? (j < n0 ? k0[j] : k1[j - n0]) : -1;
+        unsigned long long todo = __ballot(act);
+        while (todo) {
+            const int lead = __ffsll((long long)todo) - 1;
+            const int64_t kl = readlane64(key, lead);
+            const unsigned long long same = __ballot(act && key == kl);
+            int base = 0;
+            if (lane == lead) base = atomicAdd(&cursor[kl], (int)__popcll(same));
+            base = __builtin_amdgcn_readlane(base, lead);
+            if (act && key == kl) perm[offsets[kl] + base + (int)__popcll(same & ((1ull << lane) - 1ull))] = j;
+            todo &= ~same;
+        }
+    }
 }
 
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
@@ -69,6 +121,30 @@ extern "C" int kge_key_sort(const int64_t *k0, int64_t n0, const int64_t *k1, in
                                              pos_out, (size_t)n, 0u, (unsigned)key_bits, s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(perm_widen_kernel, dim3(grid), dim3(256), 0, s, pos_out, n, perm);
+    KGE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int kge_key_hist(const int64_t *k0, int64_t n0, const int64_t *k1, int64_t n1, int32_t *hist,
+                            kge_stream_t stream)
+{
+    if (n0 < 0 || n1 < 0 || !hist || (n0 > 0 && !k0) || (n1 > 0 && !k1)) return KGE_EINVAL;
+    if (n0 + n1 == 0) return 0;
+    const int64_t n = n0 + n1;
+    hipLaunchKernelGGL(key_hist_kernel, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0,
+                       kge_s(stream), k0, n0, k1, n1, hist);
+    KGE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int kge_key_scatter(const int64_t *k0, int64_t n0, const int64_t *k1, int64_t n1, const int64_t *offsets,
+                               int32_t *cursor, int64_t *perm, kge_stream_t stream)
+{
+    if (n0 < 0 || n1 < 0 || !offsets || !cursor || !perm || (n0 > 0 && !k0) || (n1 > 0 && !k1)) return KGE_EINVAL;
+    if (n0 + n1 == 0) return 0;
+    const int64_t n = n0 + n1;
+    hipLaunchKernelGGL(key_scatter_kernel, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0,
+                       kge_s(stream), k0, n0, k1, n1, offsets, cursor, perm);
     KGE_CHECK_LAUNCH();
     return 0;
 }

@@ -9,7 +9,8 @@
 //   ComplEx  models/bilinear.py:460-473       Re<h, r, conj t>   (no normalisation)
 // (x^ = x / max(||x||_2, 1e-12), torch.nn.functional.normalize).
 // The backward kernel recomputes the forward intermediates from the same
-// gathered rows and scatters gradients with fp32 atomics.
+// gathered rows and writes one gradient row per gathered row (or scatters it
+// with fp32 atomics).
 #include <type_traits>
 #include "kge_common.h"
 
@@ -107,20 +108,45 @@ struct ScoreParams {
     float *out;
 };
 
-// Rows a triple gathers, per model kind: table and index of row j (0: h, 1: t, 2: r)
-//   TransE / DistMult: E[h] E[t] R[r]            TransH: E[h] E[t] R[r] W[r]
-//   ComplEx: Re[h] Im[h] Re[t] Im[t] Rre[r] Rim[r]   TransD: E[h] E[t] Ep[h] Ep[t] R[r] Rp[r]
-template <int KIND> struct RowSet;
-template <> struct RowSet<KGE_TRANSE_L1> { static constexpr int NR = 3; };
-template <> struct RowSet<KGE_TRANSE_L2> { static constexpr int NR = 3; };
-template <> struct RowSet<KGE_DISTMULT> { static constexpr int NR = 3; };
-template <> struct RowSet<KGE_TRANSH> { static constexpr int NR = 4; };
-template <> struct RowSet<KGE_COMPLEX> { static constexpr int NR = 6; };
-template <> struct RowSet<KGE_TRANSD> { static constexpr int NR = 6; };
-template <> struct RowSet<KGE_TORUSE_L1> { static constexpr int NR = 3; };
-template <> struct RowSet<KGE_TORUSE_TORUS_L1> { static constexpr int NR = 3; };
-template <> struct RowSet<KGE_TORUSE_TORUS_L2> { static constexpr int NR = 3; };
-template <> struct RowSet<KGE_TORUSE_TORUS_EL2> { static constexpr int NR = 3; };
+// Rows a triple gathers, per model kind -- THE table of this file.  Row j is read from table t<tab> at the id it names
+// (a row at h or t is d_ent wide, a row at r d_rel wide) and is L2-normalised or not; the backward's gradient of row j is
+// gradient stream j of the header's contract (include/kge_hip.h) and is added into g<tab> at the same id.  gather_rows,
+// normalize_rows, emit_row and the zero fill of a triple without gradient all read it from here.
+//   TransE / DistMult / TorusE: E[h] E[t] R[r]             TransH: E[h] E[t] R[r] W[r]
+//   ComplEx: Re[h] Re[t] Im[h] Im[t] Rre[r] Rim[r]         TransD: E[h] E[t] Ep[h] Ep[t] R[r] Rp[r]
+enum { ID_H, ID_T, ID_R };
+struct Row {
+    int tab, id;
+    bool norm;
+};
+struct Rows {
+    int n;
+    Row row[6];
+};
+constexpr Rows row_set(int kind)
+{
+    switch (kind) {
+    case KGE_TRANSE_L1:
+    case KGE_TRANSE_L2:
+    case KGE_DISTMULT: return {3, {{0, ID_H, true}, {0, ID_T, true}, {1, ID_R, false}}};
+    case KGE_TRANSH: return {4, {{0, ID_H, true}, {0, ID_T, true}, {1, ID_R, false}, {2, ID_R, true}}};
+    case KGE_COMPLEX:
+        return {6, {{0, ID_H, false}, {0, ID_T, false}, {1, ID_H, false}, {1, ID_T, false}, {2, ID_R, false}, {3, ID_R, false}}};
+    case KGE_TRANSD:
+        return {6, {{0, ID_H, true}, {0, ID_T, true}, {2, ID_H, true}, {2, ID_T, true}, {1, ID_R, true}, {3, ID_R, true}}};
+    default: return {3, {{0, ID_H, false}, {0, ID_T, false}, {1, ID_R, false}}};    // the four TorusE kinds: frac, no norm
+    }
+}
+template <int KIND> struct RowSet {
+    static constexpr int NR = row_set(KIND).n;
+    static constexpr Rows rows() { return row_set(KIND); }
+};
+// one of four pointers by a table number that is a constant once the caller's loop over the rows is unrolled
+template <typename T>
+__device__ __forceinline__ T *table_of(int tab, T *a0, T *a1, T *a2, T *a3)
+{
+    return tab == 0 ? a0 : tab == 1 ? a1 : tab == 2 ? a2 : a3;
+}
 
 // TorusE (translation.py:705-721): frac(x) = x - trunc(x) (torch.frac: exact in fp32, keeps the sign) of the gathered
 // rows, x = (h + r) - t, score = -diss(x) -- the per-element terms of the all-candidates modes (kge_common.h)
@@ -164,36 +190,35 @@ template <int KIND, bool VEC4, int NE>
 __device__ __forceinline__ void gather_rows(const ScoreParams &p, int64_t hi, int64_t ti, int64_t ri, int lane,
                                             float (&x)[RowSet<KIND>::NR][NE])
 {
-    const int de = p.d_ent, dr = p.d_rel;
-    if (KIND == KGE_COMPLEX) {
-        load_row<VEC4, NE>(p.t0 + hi * de, de, lane, x[0]);
-        load_row<VEC4, NE>(p.t1 + hi * de, de, lane, x[1]);
-        load_row<VEC4, NE>(p.t0 + ti * de, de, lane, x[2]);
-        load_row<VEC4, NE>(p.t1 + ti * de, de, lane, x[3]);
-        load_row<VEC4, NE>(p.t2 + ri * dr, dr, lane, x[4]);
-        load_row<VEC4, NE>(p.t3 + ri * dr, dr, lane, x[5]);
-    } else if (KIND == KGE_TRANSD) {
-        load_row<VEC4, NE>(p.t0 + hi * de, de, lane, x[0]);
-        load_row<VEC4, NE>(p.t0 + ti * de, de, lane, x[1]);
-        load_row<VEC4, NE>(p.t2 + hi * de, de, lane, x[2]);
-        load_row<VEC4, NE>(p.t2 + ti * de, de, lane, x[3]);
-        load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, x[4]);
-        load_row<VEC4, NE>(p.t3 + ri * dr, dr, lane, x[5]);
-    } else {
-        load_row<VEC4, NE>(p.t0 + hi * de, de, lane, x[0]);
-        load_row<VEC4, NE>(p.t0 + ti * de, de, lane, x[1]);
-        load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, x[2]);
-        if (KIND == KGE_TRANSH) load_row<VEC4, NE>(p.t2 + ri * dr, dr, lane, x[RowSet<KIND>::NR - 1]);
+    constexpr auto rs = RowSet<KIND>::rows();
+    const int64_t id[3] = {hi, ti, ri};
+    // the loads are issued id by id -- the rows at h, then at t, then at r -- whatever their place in the row set: the two
+    // rows of ComplEx at one entity next to each other measured 4 % faster in the forward than in stream order
+#pragma unroll
+    for (int k = ID_H; k <= ID_R; ++k) {
+        const int d = k == ID_R ? p.d_rel : p.d_ent;
+#pragma unroll
+        for (int j = 0; j < RowSet<KIND>::NR; ++j)
+            if (rs.row[j].id == k) load_row<VEC4, NE>(table_of(rs.row[j].tab, p.t0, p.t1, p.t2, p.t3) + id[k] * d, d, lane, x[j]);
     }
+}
+
+// F.normalize of the rows that the kind normalises; n[j] = the clamped norm of row j (normalize_bwd)
+template <int KIND, int NE, bool EXACT>
+__device__ __forceinline__ void normalize_rows(float (&x)[RowSet<KIND>::NR][NE], float (&n)[RowSet<KIND>::NR])
+{
+    constexpr auto rs = RowSet<KIND>::rows();
+#pragma unroll
+    for (int j = 0; j < RowSet<KIND>::NR; ++j) n[j] = rs.row[j].norm ? normalize_inplace<NE, EXACT>(x[j]) : 1.f;
 }
 
 template <int KIND, bool VEC4, int NE>
 __device__ __forceinline__ float score_rows(const ScoreParams &p, int lane, float (&x)[RowSet<KIND>::NR][NE])
 {
+    float n[RowSet<KIND>::NR];  // (the forward has no use for the norms)
+    normalize_rows<KIND, NE, false>(x, n);
     if (KIND == KGE_TRANSE_L1 || KIND == KGE_TRANSE_L2) {
         float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2];
-        normalize_inplace<NE, false>(h);
-        normalize_inplace<NE, false>(t);
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
@@ -215,14 +240,12 @@ __device__ __forceinline__ float score_rows(const ScoreParams &p, int lane, floa
         return lp_direct_finish<MODE>(wave_sum_dpp(s));
     } else if (KIND == KGE_DISTMULT) {
         float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2];
-        normalize_inplace<NE, false>(h);
-        normalize_inplace<NE, false>(t);
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < NE; ++e) s += (h[e] * r[e]) * t[e];
         return wave_sum_dpp(s);
     } else if (KIND == KGE_COMPLEX) {
-        float (&reh)[NE] = x[0], (&imh)[NE] = x[1], (&ret)[NE] = x[2], (&imt)[NE] = x[3], (&rer)[NE] = x[4], (&imr)[NE] = x[5];
+        float (&reh)[NE] = x[0], (&ret)[NE] = x[1], (&imh)[NE] = x[2], (&imt)[NE] = x[3], (&rer)[NE] = x[4], (&imr)[NE] = x[5];
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < NE; ++e)
@@ -230,9 +253,6 @@ __device__ __forceinline__ float score_rows(const ScoreParams &p, int lane, floa
         return wave_sum_dpp(s);
     } else if (KIND == KGE_TRANSH) {
         float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2], (&w)[NE] = x[3];
-        normalize_inplace<NE, false>(h);
-        normalize_inplace<NE, false>(t);
-        normalize_inplace<NE, false>(w);
         const float hw = dotp<NE>(h, w), tw = dotp<NE>(t, w);
         float s = 0.f;
 #pragma unroll
@@ -247,12 +267,6 @@ __device__ __forceinline__ float score_rows(const ScoreParams &p, int lane, floa
         return -(n * n);
     } else { // KGE_TRANSD
         float (&h)[NE] = x[0], (&t)[NE] = x[1], (&hp)[NE] = x[2], (&tp)[NE] = x[3], (&r)[NE] = x[4], (&rp)[NE] = x[5];
-        normalize_inplace<NE, false>(h);
-        normalize_inplace<NE, false>(t);
-        normalize_inplace<NE, false>(hp);
-        normalize_inplace<NE, false>(tp);
-        normalize_inplace<NE, false>(r);
-        normalize_inplace<NE, false>(rp);
         const float sh = dotp<NE>(h, hp), st = dotp<NE>(t, tp);
         const int dr = p.d_rel;
         float s = 0.f;
@@ -353,312 +367,186 @@ __device__ __forceinline__ void normalize_bwd(const float (&xn)[NE], float n, fl
     for (int e = 0; e < NE; ++e) g[e] = clamped ? g[e] / n : (g[e] - xn[e] * xg) / n;
 }
 
-template <bool VEC4, int NE>
+// Gradient row j of triple i (RowSet<KIND>): stream j of the rows buffer or, in the atomic mode, added into row id[j's id]
+// of the gradient table of the table row j was read from
+template <int KIND, bool VEC4, int NE>
+__device__ __forceinline__ void emit_row(const BwdParams &q, int64_t i, const int64_t (&id)[3], int j, int lane,
+                                         const float (&g)[NE])
+{
+    const Row w = RowSet<KIND>::rows().row[j];
+    const int d = w.id == ID_R ? q.f.d_rel : q.f.d_ent;
+    if (q.rows) store_row<VEC4, NE>(q.rows + ((int64_t)j * q.f.B + i) * q.rows_ld, d, lane, g);
+    else scatter_row<VEC4, NE>(table_of(w.tab, q.g0, q.g1, q.g2, q.g3) + id[w.id] * d, d, lane, g);
+}
+
+// The counterpart of score_rows: the gradients of the gathered rows x of triple i, each emitted as soon as it is complete
+template <int KIND, bool VEC4, int NE>
+__device__ __forceinline__ void bwd_rows(const BwdParams &q, int64_t i, const int64_t (&id)[3], float go, int lane,
+                                         float (&x)[RowSet<KIND>::NR][NE])
+{
+    const int dr = q.f.d_rel;
+    auto emit = [&](int j, const float (&g)[NE]) __attribute__((always_inline)) { emit_row<KIND, VEC4, NE>(q, i, id, j, lane, g); };
+    float n[RowSet<KIND>::NR];
+    normalize_rows<KIND, NE, true>(x, n);
+    if (KIND == KGE_TRANSE_L1 || KIND == KGE_TRANSE_L2) {
+        float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2];
+        float gd[NE];
+        // score = -sum f(diff); dscore/ddiff = -sign(diff) (L1) or -2 diff (L2)
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const float diff = (h[e] + r[e]) - t[e];
+            const float sg = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
+            gd[e] = go * ((KIND == KGE_TRANSE_L1) ? -sg : -2.f * diff);
+        }
+        emit(2, gd);        // d/dr = gd
+        float gh[NE], gt[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) { gh[e] = gd[e]; gt[e] = -gd[e]; }
+        normalize_bwd<NE>(h, n[0], gh);
+        normalize_bwd<NE>(t, n[1], gt);
+        emit(0, gh);
+        emit(1, gt);
+    } else if (is_toruse(KIND)) {
+        // frac is applied to the gathered copies' .data: autograd sees the identity, so d/dh = d/dr = dscore/dx and
+        // d/dt = -dscore/dx with x = (frac h + frac r) - frac t
+        float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2];
+        float gd[NE], gt[NE];
+        frac_inplace<NE>(h);
+        frac_inplace<NE>(t);
+        frac_inplace<NE>(r);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const float g = toruse_dscore<toruse_mode(KIND)>((h[e] + r[e]) - t[e], go);
+            gd[e] = g;
+            gt[e] = -g;
+        }
+        emit(2, gd);
+        emit(0, gd);
+        emit(1, gt);
+    } else if (KIND == KGE_DISTMULT) {
+        float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2];
+        float gh[NE], gt[NE], gr[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            gh[e] = go * r[e] * t[e];
+            gt[e] = go * h[e] * r[e];
+            gr[e] = go * h[e] * t[e];
+        }
+        normalize_bwd<NE>(h, n[0], gh);
+        normalize_bwd<NE>(t, n[1], gt);
+        emit(0, gh);
+        emit(1, gt);
+        emit(2, gr);
+    } else if (KIND == KGE_COMPLEX) {
+        float (&reh)[NE] = x[0], (&ret)[NE] = x[1], (&imh)[NE] = x[2], (&imt)[NE] = x[3], (&rer)[NE] = x[4], (&imr)[NE] = x[5];
+        float g[NE];    // one gradient row at a time
+        // s = reh(rer ret + imr imt) + imh(rer imt - imr ret)
+#pragma unroll
+        for (int e = 0; e < NE; ++e) g[e] = go * (rer[e] * ret[e] + imr[e] * imt[e]);
+        emit(0, g);     // d/d reh
+#pragma unroll
+        for (int e = 0; e < NE; ++e) g[e] = go * (rer[e] * imt[e] - imr[e] * ret[e]);
+        emit(2, g);     // d/d imh
+#pragma unroll
+        for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * rer[e] - imh[e] * imr[e]);
+        emit(1, g);     // d/d ret
+#pragma unroll
+        for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * imr[e] + imh[e] * rer[e]);
+        emit(3, g);     // d/d imt
+#pragma unroll
+        for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * ret[e] + imh[e] * imt[e]);
+        emit(4, g);     // d/d rer
+#pragma unroll
+        for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * imt[e] - imh[e] * ret[e]);
+        emit(5, g);     // d/d imr
+    } else if (KIND == KGE_TRANSH) {
+        float (&h)[NE] = x[0], (&t)[NE] = x[1], (&r)[NE] = x[2], (&w)[NE] = x[3];
+        float gd[NE];
+        const float hw = dotp<NE>(h, w), tw = dotp<NE>(t, w);
+        // diff = (h - t) - (hw - tw) w + r ; score = -|diff|^2
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const float diff = ((h[e] - hw * w[e]) + r[e]) - (t[e] - tw * w[e]);
+            gd[e] = go * (-2.f * diff);
+        }
+        emit(2, gd);    // d/dr
+        const float gdw = dotp<NE>(gd, w);
+        float gh[NE], gt[NE], gw[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            gh[e] = gd[e] - gdw * w[e];         // d/dh^ = gd - (gd.w) w
+            gt[e] = -gh[e];
+            // d/dw^ = -(hw - tw) gd - (gd.w)(h - t)
+            gw[e] = -(hw - tw) * gd[e] - gdw * (h[e] - t[e]);
+        }
+        normalize_bwd<NE>(h, n[0], gh);
+        normalize_bwd<NE>(t, n[1], gt);
+        normalize_bwd<NE>(w, n[3], gw);
+        emit(0, gh);
+        emit(1, gt);
+        emit(3, gw);
+    } else { // KGE_TRANSD
+        float (&h)[NE] = x[0], (&t)[NE] = x[1], (&hp)[NE] = x[2], (&tp)[NE] = x[3], (&r)[NE] = x[4], (&rp)[NE] = x[5];
+        float gd[NE];
+        const float sh = dotp<NE>(h, hp), st = dotp<NE>(t, tp);
+        // diff_k = (sh - st) rp_k + [k<dr](h_k - t_k) + r_k   (k < dr; zero beyond)
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const bool in = elem_index<VEC4, NE>(e, lane) < dr;
+            const float diff = ((rp[e] * sh + (in ? h[e] : 0.f)) + r[e]) - (rp[e] * st + (in ? t[e] : 0.f));
+            gd[e] = in ? go * (-2.f * diff) : 0.f;
+        }
+        const float gdrp = dotp<NE>(gd, rp);
+        float gr[NE], grp[NE], gh[NE], gt[NE], ghp[NE], gtp[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            gr[e] = gd[e];
+            grp[e] = (sh - st) * gd[e];
+            gh[e] = gd[e] + gdrp * hp[e];   // via [:dr] slice and via sh = h.hp
+            gt[e] = -gd[e] - gdrp * tp[e];
+            ghp[e] = gdrp * h[e];
+            gtp[e] = -gdrp * t[e];
+        }
+        normalize_bwd<NE>(r, n[4], gr);
+        normalize_bwd<NE>(rp, n[5], grp);
+        normalize_bwd<NE>(h, n[0], gh);
+        normalize_bwd<NE>(t, n[1], gt);
+        normalize_bwd<NE>(hp, n[2], ghp);
+        normalize_bwd<NE>(tp, n[3], gtp);
+        emit(4, gr);
+        emit(5, grp);
+        emit(0, gh);
+        emit(1, gt);
+        emit(2, ghp);
+        emit(3, gtp);
+    }
+}
+
+// One wavefront per triple, specialised per model kind as the forward is: gather the kind's rows, recompute the
+// forward's intermediates from them, emit one gradient row per gathered row.
+template <int KIND, bool VEC4, int NE>
 __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void score_bwd_kernel(const BwdParams q)
 {
+    constexpr int NR = RowSet<KIND>::NR;
     const ScoreParams &p = q.f;
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * WAVES_PER_BLOCK;
-    const int de = p.d_ent, dr = p.d_rel;
 
     for (int64_t i = wave; i < p.B; i += nwaves) {
-        const int64_t hi = p.h[i], ti = p.t[i], ri = p.r[i];
+        const int64_t id[3] = {p.h[i], p.t[i], p.r[i]};
         const float go = q.go[i];
-#define KGE_EMIT(STREAM, G, IDX, D, X)                                                              \
-    do {                                                                                            \
-        if (q.rows) store_row<VEC4, NE>(q.rows + ((int64_t)(STREAM) * p.B + i) * q.rows_ld, D, lane, X); \
-        else scatter_row<VEC4, NE>((G) + (IDX) * (D), D, lane, X);                                  \
-    } while (0)
         if (go == 0.f) {
             if (q.rows) {   // this triple's rows still have to exist (as zeros) for the reduction
-                const int ns = (p.kind == KGE_TRANSD || p.kind == KGE_COMPLEX) ? 6 : (p.kind == KGE_TRANSH ? 4 : 3);
-                for (int st = 0; st < ns; ++st)
-                    for (int k = lane; k < de; k += 64) q.rows[((int64_t)st * p.B + i) * q.rows_ld + k] = 0.f;
+                // (d_ent columns of every stream, a stream of d_rel < d_ent wide rows (TransD) included)
+                for (int st = 0; st < NR; ++st)
+                    for (int k = lane; k < p.d_ent; k += 64) q.rows[((int64_t)st * p.B + i) * q.rows_ld + k] = 0.f;
             }
             continue;
         }
-        if (p.kind == KGE_TRANSE_L1 || p.kind == KGE_TRANSE_L2) {
-            float h[NE], t[NE], r[NE], gd[NE];
-            load_row<VEC4, NE>(p.t0 + hi * de, de, lane, h);
-            load_row<VEC4, NE>(p.t0 + ti * de, de, lane, t);
-            load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, r);
-            const float nh = normalize_inplace<NE>(h), nt = normalize_inplace<NE>(t);
-            // score = -sum f(diff); dscore/ddiff = -sign(diff) (L1) or -2 diff (L2)
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                const float diff = (h[e] + r[e]) - t[e];
-                const float sg = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
-                gd[e] = go * ((p.kind == KGE_TRANSE_L1) ? -sg : -2.f * diff);
-            }
-            KGE_EMIT(2, q.g1, ri, dr, gd);       // d/dr = gd
-            float gh[NE], gt[NE];
-#pragma unroll
-            for (int e = 0; e < NE; ++e) { gh[e] = gd[e]; gt[e] = -gd[e]; }
-            normalize_bwd<NE>(h, nh, gh);
-            normalize_bwd<NE>(t, nt, gt);
-            KGE_EMIT(0, q.g0, hi, de, gh);
-            KGE_EMIT(1, q.g0, ti, de, gt);
-        } else if (is_toruse(p.kind)) {
-            // frac is applied to the gathered copies' .data: autograd sees the identity, so d/dh = d/dr = dscore/dx and
-            // d/dt = -dscore/dx with x = (frac h + frac r) - frac t
-            float h[NE], t[NE], r[NE], gd[NE], gt[NE];
-            load_row<VEC4, NE>(p.t0 + hi * de, de, lane, h);
-            load_row<VEC4, NE>(p.t0 + ti * de, de, lane, t);
-            load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, r);
-            frac_inplace<NE>(h);
-            frac_inplace<NE>(t);
-            frac_inplace<NE>(r);
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                const float x = (h[e] + r[e]) - t[e];
-                float g;
-                switch (p.kind) {
-                case KGE_TORUSE_TORUS_L1: g = toruse_dscore<KGE_LP_TORUS_L1>(x, go); break;
-                case KGE_TORUSE_TORUS_L2: g = toruse_dscore<KGE_LP_TORUS_L2>(x, go); break;
-                case KGE_TORUSE_TORUS_EL2: g = toruse_dscore<KGE_LP_TORUS_EL2>(x, go); break;
-                default: g = toruse_dscore<KGE_LP_L1_DIRECT>(x, go);
-                }
-                gd[e] = g;
-                gt[e] = -g;
-            }
-            KGE_EMIT(2, q.g1, ri, dr, gd);
-            KGE_EMIT(0, q.g0, hi, de, gd);
-            KGE_EMIT(1, q.g0, ti, de, gt);
-        } else if (p.kind == KGE_DISTMULT) {
-            float h[NE], t[NE], r[NE], gh[NE], gt[NE], gr[NE];
-            load_row<VEC4, NE>(p.t0 + hi * de, de, lane, h);
-            load_row<VEC4, NE>(p.t0 + ti * de, de, lane, t);
-            load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, r);
-            const float nh = normalize_inplace<NE>(h), nt = normalize_inplace<NE>(t);
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                gh[e] = go * r[e] * t[e];
-                gt[e] = go * h[e] * r[e];
-                gr[e] = go * h[e] * t[e];
-            }
-            normalize_bwd<NE>(h, nh, gh);
-            normalize_bwd<NE>(t, nt, gt);
-            KGE_EMIT(0, q.g0, hi, de, gh);
-            KGE_EMIT(1, q.g0, ti, de, gt);
-            KGE_EMIT(2, q.g1, ri, dr, gr);
-        } else if (p.kind == KGE_COMPLEX) {
-            float reh[NE], imh[NE], ret[NE], imt[NE], rer[NE], imr[NE], g[NE];
-            load_row<VEC4, NE>(p.t0 + hi * de, de, lane, reh);
-            load_row<VEC4, NE>(p.t1 + hi * de, de, lane, imh);
-            load_row<VEC4, NE>(p.t0 + ti * de, de, lane, ret);
-            load_row<VEC4, NE>(p.t1 + ti * de, de, lane, imt);
-            load_row<VEC4, NE>(p.t2 + ri * dr, dr, lane, rer);
-            load_row<VEC4, NE>(p.t3 + ri * dr, dr, lane, imr);
-            // s = reh(rer ret + imr imt) + imh(rer imt - imr ret)
-#pragma unroll
-            for (int e = 0; e < NE; ++e) g[e] = go * (rer[e] * ret[e] + imr[e] * imt[e]);
-            KGE_EMIT(0, q.g0, hi, de, g); // d/d reh
-#pragma unroll
-            for (int e = 0; e < NE; ++e) g[e] = go * (rer[e] * imt[e] - imr[e] * ret[e]);
-            KGE_EMIT(2, q.g1, hi, de, g); // d/d imh
-#pragma unroll
-            for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * rer[e] - imh[e] * imr[e]);
-            KGE_EMIT(1, q.g0, ti, de, g); // d/d ret
-#pragma unroll
-            for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * imr[e] + imh[e] * rer[e]);
-            KGE_EMIT(3, q.g1, ti, de, g); // d/d imt
-#pragma unroll
-            for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * ret[e] + imh[e] * imt[e]);
-            KGE_EMIT(4, q.g2, ri, dr, g); // d/d rer
-#pragma unroll
-            for (int e = 0; e < NE; ++e) g[e] = go * (reh[e] * imt[e] - imh[e] * ret[e]);
-            KGE_EMIT(5, q.g3, ri, dr, g); // d/d imr
-        } else if (p.kind == KGE_TRANSH) {
-            float h[NE], t[NE], r[NE], w[NE], gd[NE];
-            load_row<VEC4, NE>(p.t0 + hi * de, de, lane, h);
-            load_row<VEC4, NE>(p.t0 + ti * de, de, lane, t);
-            load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, r);
-            load_row<VEC4, NE>(p.t2 + ri * dr, dr, lane, w);
-            const float nh = normalize_inplace<NE>(h), nt = normalize_inplace<NE>(t);
-            const float nw = normalize_inplace<NE>(w);
-            const float hw = dotp<NE>(h, w), tw = dotp<NE>(t, w);
-            // diff = (h - t) - (hw - tw) w + r ; score = -|diff|^2
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                const float diff = ((h[e] - hw * w[e]) + r[e]) - (t[e] - tw * w[e]);
-                gd[e] = go * (-2.f * diff);
-            }
-            KGE_EMIT(2, q.g1, ri, dr, gd); // d/dr
-            const float gdw = dotp<NE>(gd, w);
-            float gh[NE], gt[NE], gw[NE];
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                gh[e] = gd[e] - gdw * w[e];         // d/dh^ = gd - (gd.w) w
-                gt[e] = -gh[e];
-                // d/dw^ = -(hw - tw) gd - (gd.w)(h - t)
-                gw[e] = -(hw - tw) * gd[e] - gdw * (h[e] - t[e]);
-            }
-            normalize_bwd<NE>(h, nh, gh);
-            normalize_bwd<NE>(t, nt, gt);
-            normalize_bwd<NE>(w, nw, gw);
-            KGE_EMIT(0, q.g0, hi, de, gh);
-            KGE_EMIT(1, q.g0, ti, de, gt);
-            KGE_EMIT(3, q.g2, ri, dr, gw);
-        } else { // KGE_TRANSD
-            float h[NE], t[NE], hp[NE], tp[NE], r[NE], rp[NE], gd[NE];
-            load_row<VEC4, NE>(p.t0 + hi * de, de, lane, h);
-            load_row<VEC4, NE>(p.t0 + ti * de, de, lane, t);
-            load_row<VEC4, NE>(p.t2 + hi * de, de, lane, hp);
-            load_row<VEC4, NE>(p.t2 + ti * de, de, lane, tp);
-            load_row<VEC4, NE>(p.t1 + ri * dr, dr, lane, r);
-            load_row<VEC4, NE>(p.t3 + ri * dr, dr, lane, rp);
-            const float nh = normalize_inplace<NE>(h), nt = normalize_inplace<NE>(t);
-            const float nhp = normalize_inplace<NE>(hp), ntp = normalize_inplace<NE>(tp);
-            const float nr = normalize_inplace<NE>(r), nrp = normalize_inplace<NE>(rp);
-            const float sh = dotp<NE>(h, hp), st = dotp<NE>(t, tp);
-            // diff_k = (sh - st) rp_k + [k<dr](h_k - t_k) + r_k   (k < dr; zero beyond)
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                const bool in = elem_index<VEC4, NE>(e, lane) < dr;
-                const float diff = ((rp[e] * sh + (in ? h[e] : 0.f)) + r[e]) - (rp[e] * st + (in ? t[e] : 0.f));
-                gd[e] = in ? go * (-2.f * diff) : 0.f;
-            }
-            const float gdrp = dotp<NE>(gd, rp);
-            float gr[NE], grp[NE], gh[NE], gt[NE], ghp[NE], gtp[NE];
-#pragma unroll
-            for (int e = 0; e < NE; ++e) {
-                gr[e] = gd[e];
-                grp[e] = (sh - st) * gd[e];
-                gh[e] = gd[e] + gdrp * hp[e];   // via [:dr] slice and via sh = h.hp
-                gt[e] = -gd[e] - gdrp * tp[e];
-                ghp[e] = gdrp * h[e];
-                gtp[e] = -gdrp * t[e];
-            }
-            normalize_bwd<NE>(r, nr, gr);
-            normalize_bwd<NE>(rp, nrp, grp);
-            normalize_bwd<NE>(h, nh, gh);
-            normalize_bwd<NE>(t, nt, gt);
-            normalize_bwd<NE>(hp, nhp, ghp);
-            normalize_bwd<NE>(tp, ntp, gtp);
-            KGE_EMIT(4, q.g1, ri, dr, gr);
-            KGE_EMIT(5, q.g3, ri, dr, grp);
-            KGE_EMIT(0, q.g0, hi, de, gh);
-            KGE_EMIT(1, q.g0, ti, de, gt);
-            KGE_EMIT(2, q.g2, hi, de, ghp);
-            KGE_EMIT(3, q.g2, ti, de, gtp);
-        }
-    }
-}
-
-#undef KGE_EMIT
-
-// Reduction of per-triple gradient rows by target row, in SORTED key order: a wavefront walks 32
-// consecutive sorted entries, sums runs of equal keys in registers and flushes each run with one
-// atomic row-add -- a handful of atomics per chunk instead of one per (triple, dimension), and the
-// heavily shared relation rows (n_rel << B) stop serialising on the same addresses.
-template <int NE>
-__global__ __launch_bounds__(256) void segment_sum_kernel(const float *__restrict__ rows, int64_t ld, int d,
-                                                          const int64_t *__restrict__ k0, int64_t n0,
-                                                          const int64_t *__restrict__ k1, int64_t n1,
-                                                          const int64_t *__restrict__ perm,
-                                                          float *__restrict__ out, int64_t out_ld)
-{
-    constexpr int CH = 32, UN = 4;
-    const int64_t M = n0 + n1;
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    for (int64_t j0 = wave * CH; j0 < M; j0 += nwaves * CH) {
-        const int n = (int)min((int64_t)CH, M - j0);
-        // the chunk's (row, key) pairs: one coalesced load, then broadcast by shuffle
-        const int64_t jl = j0 + min(lane, n - 1);
-        const int64_t my_row = perm[jl], my_key = my_row < n0 ? k0[my_row] : k1[my_row - n0];
-        float acc[NE];
-#pragma unroll
-        for (int e = 0; e < NE; ++e) acc[e] = 0.f;
-        int64_t cur = __shfl(my_key, 0, 64);
-        for (int j = 0; j < n; j += UN) {
-            float v[UN][NE];
-            int64_t kk[UN];
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {      // UN independent row loads in flight
-                const int ju = min(j + u, n - 1);
-                kk[u] = __shfl(my_key, ju, 64);
-                const float *row = rows + __shfl(my_row, ju, 64) * ld;
-#pragma unroll
-                for (int e = 0; e < NE; ++e) {
-                    const int k = lane + 64 * e;
-                    v[u][e] = (k < d && j + u < n) ? row[k] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                if (j + u < n && kk[u] != cur) {    // wave-uniform
-#pragma unroll
-                    for (int e = 0; e < NE; ++e) {
-                        const int k = lane + 64 * e;
-                        if (k < d && acc[e] != 0.f) atomicAdd(out + cur * out_ld + k, acc[e]);
-                        acc[e] = 0.f;
-                    }
-                    cur = kk[u];
-                }
-#pragma unroll
-                for (int e = 0; e < NE; ++e) acc[e] += v[u][e];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const int k = lane + 64 * e;
-            if (k < d && acc[e] != 0.f) atomicAdd(out + cur * out_ld + k, acc[e]);
-        }
-    }
-}
-
-// counting sort of small-integer keys (entity / relation ids): histogram, (host: cumsum), scatter.
-// Atomics are aggregated per wavefront: one atomic per DISTINCT key among a wavefront's 64 keys.  Real
-// graphs are heavy-tailed (a hub entity / relation owns 10% of a batch) and same-address atomics
-// serialise at ~12 ns each past the L2s: 100 us per launch at B = 32768 on a Zipf batch before this.
-__device__ __forceinline__ int64_t readlane64(int64_t v, int src)
-{
-    const unsigned lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), src);
-    const unsigned hi = __builtin_amdgcn_readlane((int)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-__global__ void key_hist_kernel(const int64_t *__restrict__ k0, int64_t n0, const int64_t *__restrict__ k1, int64_t n1,
-                                int32_t *hist)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t n = n0 + n1, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t jb = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; jb < n; jb += stride) {   // wave-uniform trip count
-        const int64_t j = jb + lane;
-        const bool act = j < n;
-        const int64_t key = act ? (j < n0 ? k0[j] : k1[j - n0]) : -1;
-        unsigned long long todo = __ballot(act);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int64_t kl = readlane64(key, lead);
-            const unsigned long long same = __ballot(act && key == kl);
-            if (lane == lead) atomicAdd(&hist[kl], (int)__popcll(same));
-            todo &= ~same;
-        }
-    }
-}
-__global__ void key_scatter_kernel(const int64_t *__restrict__ k0, int64_t n0, const int64_t *__restrict__ k1,
-                                   int64_t n1, const int64_t *__restrict__ offsets, int32_t *cursor, int64_t *perm)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t n = n0 + n1, stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t jb = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; jb < n; jb += stride) {
-        const int64_t j = jb + lane;
-        const bool act = j < n;
-        const int64_t key = act ? (j < n0 ? k0[j] : k1[j - n0]) : -1;
-        unsigned long long todo = __ballot(act);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int64_t kl = readlane64(key, lead);
-            const unsigned long long same = __ballot(act && key == kl);
-            int base = 0;
-            if (lane == lead) base = atomicAdd(&cursor[kl], (int)__popcll(same));
-            base = __builtin_amdgcn_readlane(base, lead);
-            if (act && key == kl) perm[offsets[kl] + base + (int)__popcll(same & ((1ull << lane) - 1ull))] = j;
-            todo &= ~same;
-        }
+        float x[NR][NE];
+        gather_rows<KIND, VEC4, NE>(p, id[ID_H], id[ID_T], id[ID_R], lane, x);
+        bwd_rows<KIND, VEC4, NE>(q, i, id, go, lane, x);
     }
 }
 
@@ -667,6 +555,25 @@ inline int grid_for(int64_t B)
     int64_t blocks = (B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     static const int64_t cap = kge_env_int("KGE_K1_BLOCKS", 256 * 32); // one triple per wavefront up to B = 32768 (measured 7-15 % faster than 4 per wave), grid-stride beyond
     return (int)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);
+}
+
+// The kinds of this file as compile-time constants: f(std::integral_constant<int, KIND>) of the run-time kind
+template <typename F>
+int dispatch_kind(int kind, F f)
+{
+    switch (kind) {
+    case KGE_TRANSE_L1: return f(std::integral_constant<int, KGE_TRANSE_L1>{});
+    case KGE_TRANSE_L2: return f(std::integral_constant<int, KGE_TRANSE_L2>{});
+    case KGE_TRANSH: return f(std::integral_constant<int, KGE_TRANSH>{});
+    case KGE_TRANSD: return f(std::integral_constant<int, KGE_TRANSD>{});
+    case KGE_DISTMULT: return f(std::integral_constant<int, KGE_DISTMULT>{});
+    case KGE_COMPLEX: return f(std::integral_constant<int, KGE_COMPLEX>{});
+    case KGE_TORUSE_L1: return f(std::integral_constant<int, KGE_TORUSE_L1>{});
+    case KGE_TORUSE_TORUS_L1: return f(std::integral_constant<int, KGE_TORUSE_TORUS_L1>{});
+    case KGE_TORUSE_TORUS_L2: return f(std::integral_constant<int, KGE_TORUSE_TORUS_L2>{});
+    case KGE_TORUSE_TORUS_EL2: return f(std::integral_constant<int, KGE_TORUSE_TORUS_EL2>{});
+    default: return KGE_EINVAL;
+    }
 }
 
 template <typename P, typename KernelSel>
@@ -720,27 +627,13 @@ extern "C" int kge_score_triples(int kind, const float *t0, const float *t1, con
         constexpr int NE = decltype(ne)::value;
         constexpr bool PF = NE <= 8;    // two row sets in registers (6 rows x 16 floats x 2 would not fit)
         const dim3 grid(grid_for(b)), block(WAVES_PER_BLOCK * 64);
-#define KGE_FWD_CASE(K)                                                                                   \
-    case K:                                                                                               \
-        if (v4) hipLaunchKernelGGL((score_fwd_kernel<K, true, NE, PF>), grid, block, 0, s, pp);           \
-        else hipLaunchKernelGGL((score_fwd_kernel<K, false, NE, PF>), grid, block, 0, s, pp);             \
-        break;
-        switch (pp.kind) {
-            KGE_FWD_CASE(KGE_TRANSE_L1)
-            KGE_FWD_CASE(KGE_TRANSE_L2)
-            KGE_FWD_CASE(KGE_TRANSH)
-            KGE_FWD_CASE(KGE_TRANSD)
-            KGE_FWD_CASE(KGE_DISTMULT)
-            KGE_FWD_CASE(KGE_COMPLEX)
-            KGE_FWD_CASE(KGE_TORUSE_L1)
-            KGE_FWD_CASE(KGE_TORUSE_TORUS_L1)
-            KGE_FWD_CASE(KGE_TORUSE_TORUS_L2)
-            KGE_FWD_CASE(KGE_TORUSE_TORUS_EL2)
-        default: return KGE_EINVAL;
-        }
-#undef KGE_FWD_CASE
-        KGE_CHECK_LAUNCH();
-        return 0;
+        return dispatch_kind(pp.kind, [&](auto k) -> int {
+            constexpr int K = decltype(k)::value;
+            if (v4) hipLaunchKernelGGL((score_fwd_kernel<K, true, NE, PF>), grid, block, 0, s, pp);
+            else hipLaunchKernelGGL((score_fwd_kernel<K, false, NE, PF>), grid, block, 0, s, pp);
+            KGE_CHECK_LAUNCH();
+            return 0;
+        });
     };
     return dispatch_ne(p, d_ent, vec4, B, kge_s(stream), sel);
 }
@@ -766,52 +659,14 @@ extern "C" int kge_score_triples_bwd(int kind, const float *t0, const float *t1,
     const bool vec4 = tables_vec4(t0, t1, t2, t3, d_ent, d_rel);
     auto sel = [](const BwdParams &qq, auto ne, bool v4, int64_t b, hipStream_t s) -> int {
         constexpr int NE = decltype(ne)::value;
-        if (v4) hipLaunchKernelGGL((score_bwd_kernel<true, NE>), dim3(grid_for(b)), dim3(WAVES_PER_BLOCK * 64), 0, s, qq);
-        else hipLaunchKernelGGL((score_bwd_kernel<false, NE>), dim3(grid_for(b)), dim3(WAVES_PER_BLOCK * 64), 0, s, qq);
-        KGE_CHECK_LAUNCH();
-        return 0;
+        const dim3 grid(grid_for(b)), block(WAVES_PER_BLOCK * 64);
+        return dispatch_kind(qq.f.kind, [&](auto k) -> int {
+            constexpr int K = decltype(k)::value;
+            if (v4) hipLaunchKernelGGL((score_bwd_kernel<K, true, NE>), grid, block, 0, s, qq);
+            else hipLaunchKernelGGL((score_bwd_kernel<K, false, NE>), grid, block, 0, s, qq);
+            KGE_CHECK_LAUNCH();
+            return 0;
+        });
     };
     return dispatch_ne(q, d_ent, vec4, B, kge_s(stream), sel);
-}
-
-extern "C" int kge_segment_sum_rows(const float *rows, int64_t ld, int d, const int64_t *k0, int64_t n0,
-                                    const int64_t *k1, int64_t n1, const int64_t *perm, float *out, int64_t out_ld,
-                                    kge_stream_t stream)
-{
-    const int64_t M = n0 + n1;
-    if (n0 < 0 || n1 < 0 || d <= 0 || d > 1024 || ld < d || out_ld < d) return KGE_EINVAL;
-    if (M == 0) return 0;
-    if (!rows || (n0 > 0 && !k0) || (n1 > 0 && !k1) || !perm || !out) return KGE_EINVAL;
-    const int64_t chunks = (M + 31) / 32;
-    const int grid = (int)((chunks + 3) / 4 < 256 * 8 ? (chunks + 3) / 4 : 256 * 8);
-    hipStream_t s = kge_s(stream);
-    if (d <= 256) hipLaunchKernelGGL(segment_sum_kernel<4>, dim3(grid), dim3(256), 0, s, rows, ld, d, k0, n0, k1, n1, perm, out, out_ld);
-    else if (d <= 512) hipLaunchKernelGGL(segment_sum_kernel<8>, dim3(grid), dim3(256), 0, s, rows, ld, d, k0, n0, k1, n1, perm, out, out_ld);
-    else hipLaunchKernelGGL(segment_sum_kernel<16>, dim3(grid), dim3(256), 0, s, rows, ld, d, k0, n0, k1, n1, perm, out, out_ld);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int kge_key_hist(const int64_t *k0, int64_t n0, const int64_t *k1, int64_t n1, int32_t *hist,
-                            kge_stream_t stream)
-{
-    if (n0 < 0 || n1 < 0 || !hist || (n0 > 0 && !k0) || (n1 > 0 && !k1)) return KGE_EINVAL;
-    if (n0 + n1 == 0) return 0;
-    const int64_t n = n0 + n1;
-    hipLaunchKernelGGL(key_hist_kernel, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0,
-                       kge_s(stream), k0, n0, k1, n1, hist);
-    KGE_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int kge_key_scatter(const int64_t *k0, int64_t n0, const int64_t *k1, int64_t n1, const int64_t *offsets,
-                               int32_t *cursor, int64_t *perm, kge_stream_t stream)
-{
-    if (n0 < 0 || n1 < 0 || !offsets || !cursor || !perm || (n0 > 0 && !k0) || (n1 > 0 && !k1)) return KGE_EINVAL;
-    if (n0 + n1 == 0) return 0;
-    const int64_t n = n0 + n1;
-    hipLaunchKernelGGL(key_scatter_kernel, dim3((int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0,
-                       kge_s(stream), k0, n0, k1, n1, offsets, cursor, perm);
-    KGE_CHECK_LAUNCH();
-    return 0;
 }

@@ -1,7 +1,7 @@
 // kge_segment_sum_ordered (include/kge_hip_det.h): the segmented row sum of the backward with a FIXED summation order
 // and no float atomic -- the reduction behind torchkge_amd.set_deterministic(True).
 //
-// kge_segment_sum_rows (score_triples.hip) walks the sorted entries in chunks of 32 per wavefront and flushes every run
+// kge_segment_sum_rows (segment_sum_rows.hip) walks the sorted entries in chunks of 32 per wavefront and flushes every run
 // with an atomic row-add: runs that cross chunks are summed in arrival order.  Here the chunk walk is the same, but a
 // row of `out` is only ever written by ONE wavefront of ONE launch:
 //
@@ -154,8 +154,7 @@ __global__ __launch_bounds__(256) void segment_sum_ordered_kernel(const SegLevel
 template <int NE>
 void launch_level(const SegLevel &p, bool level0, hipStream_t s)
 {
-    const int64_t chunks = (p.m + KGE_DET_CH - 1) / KGE_DET_CH;
-    const int grid = (int)((chunks + 3) / 4 < 256 * 8 ? (chunks + 3) / 4 : 256 * 8);
+    const int grid = kge_seg_grid(p.m);
     if (level0) hipLaunchKernelGGL((segment_sum_ordered_kernel<NE, true>), dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((segment_sum_ordered_kernel<NE, false>), dim3(grid), dim3(256), 0, s, p);
 }
@@ -171,11 +170,10 @@ extern "C" int kge_segment_sum_ordered(const float *rows, int64_t ld, int d, con
                                        const int64_t *k1, int64_t n1, const int64_t *perm, float *out, int64_t out_ld,
                                        void *ws, size_t ws_bytes, kge_stream_t stream)
 {
-    if (n0 < 0 || n1 < 0 || d <= 0 || d > 1024 || ld < d || out_ld < d) return KGE_EINVAL;
+    const int todo = kge_seg_check_args(rows, ld, d, k0, n0, k1, n1, perm, out, out_ld);
+    if (todo <= 0) return todo < 0 ? KGE_EINVAL : 0;
     if (n0 > INT64_MAX - n1) return KGE_EINVAL;
     const int64_t M = n0 + n1;
-    if (M == 0) return 0;
-    if (!rows || (n0 > 0 && !k0) || (n1 > 0 && !k1) || !perm || !out) return KGE_EINVAL;
     const kge_det_plan plan = kge_det_make_plan(M, d);
     if (plan.n_levels == 0 || !ws || (reinterpret_cast<uintptr_t>(ws) & 7) || ws_bytes < plan.bytes) return KGE_EINVAL;
     int64_t *ws_keys = static_cast<int64_t *>(ws);
