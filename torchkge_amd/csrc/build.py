@@ -18,12 +18,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfma.hip', 'lp_split_operands.hip', 'lp_split_query.hip',
            'lp_split_recheck.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip', 'lp_l1_sad.hip', 'rank_filter.hip',
            'lp_pairs.hip', 'topk.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip', 'transr_xform.hip', 'analogy.hip', 'convkb.hip',
-           'triplet.hip', 'segment_sum_rows.hip', 'segment_sum_ordered.hip', 'relation_corrupt.hip', 'row_optim.hip', 'pair_loss.hip']
+           'triplet.hip', 'segment_sum_rows.hip', 'segment_sum_ordered.hip', 'relation_corrupt.hip', 'row_optim.hip', 'pair_loss.hip',
+           'redundancy.hip']
 HEADERS = ['kge_common.h', 'lp_pair_exact.h', 'rel_operator.h','lp_split_common.h', 'lp_hi_sweep.h', 'mask_scan.h', 'segment_levels.h', os.path.join('..', '..', 'include', 'kge_hip.h'),
            os.path.join('..', '..', 'include', 'kge_hip_analogy.h'), os.path.join('..', '..', 'include', 'kge_hip_convkb.h'),
            os.path.join('..', '..', 'include', 'kge_hip_triplet.h'), os.path.join('..', '..', 'include', 'kge_hip_det.h'),
            os.path.join('..', '..', 'include', 'kge_hip_relation.h'), os.path.join('..', '..', 'include', 'kge_hip_rows.h'),
-           os.path.join('..', '..', 'include', 'kge_hip_train.h')]
+           os.path.join('..', '..', 'include', 'kge_hip_train.h'), os.path.join('..', '..', 'include', 'kge_hip_redundancy.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
 # libkge_hip.so does not depend on librccl
