@@ -11,6 +11,7 @@ from .. import _hip
 from .. import _hip_analogy
 from ..rowgrad import is_row_gradients
 from ..utils.modeling import init_embedding
+from ..utils.one_vs_all import one_vs_all_loss
 from .interfaces import BilinearModel, _table_of
 from .translation import _ent_range
 
@@ -68,6 +69,21 @@ class DistMultModel(BilinearModel):
         else:
             candidates = R.view(1, self.n_rel, self.emb_dim).expand(b_size, self.n_rel, self.emb_dim)
         return h, t, r, candidates
+
+    def one_vs_all_loss(self, h_idx, t_idx, r_idx, side='both', label_smoothing=0.0, reduction='mean'):
+        """Softmax cross-entropy of every fact's true tail among ALL entities as tails of (h, r, ?) (``side='tail'``),
+        of its true head among all heads of (?, r, t) (``'head'``), or both as one problem of 2B queries, the tail side
+        first like ``lp_problem_both`` (``'both'``).  ``label_smoothing`` and ``reduction`` as torch's ``cross_entropy``.
+
+        The scores are those of ``inference_scoring_function`` on the RAW tables -- (e_h * r) . e_c -- exactly what the
+        evaluator ranks.  The per-triple L2 normalisation of h and t inside ``scoring_function`` is NOT applied: keep the
+        entity rows normalised with ``normalize_parameters()`` (OneVsAllTrainer does, per epoch).
+
+        The (B, N) score matrix is never written (torchkge_amd.utils.one_vs_all).  The gradient of ``ent_emb`` is dense
+        by nature -- every entity is a candidate of every query -- whatever ``row_gradients()`` says; so is
+        ``rel_emb``'s here.  The query rows' part of it is summed by the ordered reduction under ``deterministic()``,
+        the all-candidates part always in a fixed order."""
+        return one_vs_all_loss(self, h_idx, t_idx, r_idx, side, label_smoothing, reduction)
 
     def lp_problem(self, h_idx, t_idx, r_idx, side, ent_lo=0, ent_hi=None, exchange=None, qtabs=None, cols=None):
         ent_lo, ent_hi = _ent_range(self, ent_lo, ent_hi)
@@ -166,6 +182,19 @@ class ComplExModel(BilinearModel):
             cand = (Rre.view(1, self.n_rel, self.emb_dim).expand(*shape),
                     Rim.view(1, self.n_rel, self.emb_dim).expand(*shape))
         return h, t, r, cand
+
+    def one_vs_all_loss(self, h_idx, t_idx, r_idx, side='both', label_smoothing=0.0, reduction='mean'):
+        """Softmax cross-entropy of every fact's true tail among ALL entities as tails of (h, r, ?) (``side='tail'``),
+        of its true head among all heads of (?, r, t) (``'head'``), or both as one problem of 2B queries, the tail side
+        first like ``lp_problem_both`` (``'both'``).  ``label_smoothing`` and ``reduction`` as torch's ``cross_entropy``.
+
+        The scores are those of ``inference_scoring_function`` -- Re(<h, r, conj(c)>) as two segments over the
+        [Re | Im] tables -- exactly what the evaluator ranks.  The (B, N) score matrix is never written
+        (torchkge_amd.utils.one_vs_all).  The gradients of the entity tables are dense by nature -- every entity is a
+        candidate of every query -- whatever ``row_gradients()`` says; so are the relation tables' here.  The query
+        rows' part is summed by the ordered reduction under ``deterministic()``, the all-candidates part always in a
+        fixed order."""
+        return one_vs_all_loss(self, h_idx, t_idx, r_idx, side, label_smoothing, reduction)
 
     def lp_problem(self, h_idx, t_idx, r_idx, side, ent_lo=0, ent_hi=None, exchange=None, qtabs=None, cols=None):
         ent_lo, ent_hi = _ent_range(self, ent_lo, ent_hi)

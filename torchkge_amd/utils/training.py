@@ -17,6 +17,9 @@ What is the engine's own:
   * ``get_counter_examples()`` is None before ``run()`` and the last epoch's negatives after it (the reference's
     ``run`` asks its loader for them before the first iteration and raises).
 
+``OneVsAllTrainer`` is the engine's own: the same epochs without a sampler, on ``model.one_vs_all_loss`` (the softmax
+cross-entropy over all entities of torchkge_amd.utils.one_vs_all; DistMultModel and ComplExModel).
+
 The models live on the GPU: ``use_cuda`` is 'all' or 'batch'."""
 import contextlib
 
@@ -24,6 +27,7 @@ import torch
 
 from .. import optim
 from ..data_structures import SmallKG
+from ..models.interfaces import Model
 from ..rowgrad import row_gradients
 from ..sampling import BernoulliNegativeSampler, UniformNegativeSampler
 from .data import get_n_batches
@@ -195,3 +199,104 @@ class Trainer:
     def get_counter_examples(self):
         """The counter-examples of the last epoch as a ``SmallKG``; None before ``run()``."""
         return self.counter_examples
+
+
+class OneVsAllTrainer:
+    """1-vs-all training of a model with ``one_vs_all_loss`` (DistMultModel, ComplExModel): per batch the softmax
+    cross-entropy of the true tail / head among ALL entities (torchkge_amd.utils.one_vs_all), without the (B, N) score
+    matrix.  There is no sampler and no criterion; the epochs are ``Trainer``'s -- the facts in their order, the last
+    batch short, ``model.normalize_parameters()`` after each, the mean step loss in ``epoch_losses`` (``sync_free=True``:
+    the steps add into one device float per epoch, read back on first access).
+
+    The entity tables' gradient is dense in this regime, so the row-wise optimizers of ``torchkge_amd.optim`` are
+    refused: use a ``torch.optim`` optimizer."""
+
+    def __init__(self, model, kg_train, n_epochs, batch_size, optimizer, label_smoothing=0.0, side='both', use_cuda='all',
+                 *, sync_free=False, verbose=True):
+        if use_cuda not in ('all', 'batch'):
+            raise ValueError("OneVsAllTrainer: use_cuda must be 'all' or 'batch', got %r -- the engine's models live on the "
+                             "GPU, there is no CPU training path" % (use_cuda,))
+        if side not in ('both', 'tail', 'head'):
+            raise ValueError("OneVsAllTrainer: side is 'both', 'tail' or 'head', got %r" % (side,))
+        if isinstance(optimizer, (optim.RowSGD, optim.RowAdagrad, optim.RowAdam)):
+            raise ValueError('OneVsAllTrainer: %s updates the rows of a sparse row gradient, but the 1-vs-all gradient of '
+                             'an entity table is dense (every entity is a candidate of every query); use a torch.optim '
+                             'optimizer' % type(optimizer).__name__)
+        if type(model).one_vs_all_loss is Model.one_vs_all_loss:
+            model.one_vs_all_loss(None, None, None)     # raises NotImplementedError, naming the models that have it
+        self.model = model
+        self.kg_train = kg_train
+        self.use_cuda = use_cuda
+        self.n_epochs = n_epochs
+        self.optimizer = optimizer
+        self.batch_size = batch_size
+        self.label_smoothing = label_smoothing
+        self.side = side
+        self.n_triples = len(kg_train)
+        self.sync_free = sync_free
+        self.verbose = verbose
+        self._facts = None
+        self._epoch_losses = []
+        self._epoch_sums = None         # sync_free: (device vector of the epochs' loss sums, batches per epoch)
+
+    def _step(self, batch, acc=None):
+        """One training step; the loss as a device scalar, also added to the device float ``acc`` when given."""
+        self.optimizer.zero_grad()
+        loss = self.model.one_vs_all_loss(batch[0], batch[1], batch[2], side=self.side,
+                                          label_smoothing=self.label_smoothing, reduction='mean')
+        if acc is not None:
+            acc.add_(loss.detach())
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()
+
+    def _batches(self):
+        h, t, r = self._facts
+        for b in range(get_n_batches(len(h), self.batch_size)):
+            sl = slice(b * self.batch_size, (b + 1) * self.batch_size)
+            batch = (h[sl], t[sl], r[sl])
+            yield tuple(x.cuda() for x in batch) if self.use_cuda == 'batch' else batch
+
+    def run(self):
+        self.model.cuda()
+        epochs = range(self.n_epochs)
+        bar = None
+        if self.verbose:
+            try:
+                from tqdm.autonotebook import tqdm
+                epochs = bar = tqdm(epochs, unit='epoch')
+            except ImportError:
+                pass
+        if self._facts is None:         # kept: a later run() uploads nothing again
+            kg = self.kg_train
+            self._facts = (kg.head_idx, kg.tail_idx, kg.relations)
+            if self.use_cuda == 'all':
+                self._facts = tuple(x.cuda() for x in self._facts)
+        n_batches = get_n_batches(len(self._facts[0]), self.batch_size)
+        self._epoch_losses, self._epoch_sums = [], None
+        if self.sync_free:
+            device = next(self.model.parameters()).device
+            self._epoch_sums = (torch.zeros(self.n_epochs, dtype=torch.float32, device=device), n_batches)
+        for epoch in epochs:
+            if self.sync_free:
+                acc = self._epoch_sums[0][epoch]        # a view: the steps add into the vector's own element
+                for batch in self._batches():
+                    self._step(batch, acc)
+            else:
+                sum_ = 0
+                for batch in self._batches():
+                    sum_ += self._step(batch).item()
+                self._epoch_losses.append(sum_ / n_batches)
+                if bar is not None:
+                    bar.set_description('Epoch {} | mean loss: {:.5f}'.format(epoch + 1, self._epoch_losses[-1]))
+            self.model.normalize_parameters()
+
+    @property
+    def epoch_losses(self):
+        """The mean step loss of every epoch of the last ``run()``, as Python floats.  After a ``sync_free`` run the
+        first access reads the epoch sums back (one copy)."""
+        if self._epoch_sums is not None:
+            sums, n_batches = self._epoch_sums
+            self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
+        return self._epoch_losses
+
