@@ -17,6 +17,7 @@ import torch
 from oracle import kge_oracle as orc
 from tests import width_table as wt
 from tests.helpers import oracle_clib, fptr
+from tests.operand_ref import planar_halves
 from tests.test_gpu_parity import build_model
 from torchkge_amd import _hip as _hip_host
 
@@ -265,15 +266,6 @@ def test_count_routes_equal_the_chain_reference(hip, form, K, route):
     _run_route(hip, prob, guard, route, K, st, c['want'], '%s K=%d %s' % (form, K, route))
 
 
-def _planar_halves(hip, table, rows_p, units_p, frag):
-    """A one-product candidate table as [rows_p][units_p * 16] fp32 values (fragment-major: the 1-KiB block of a 32-row
-    group and a unit holds halves 0..7 of row l in lane l and halves 8..15 in lane 32 + l -- include/kge_hip.h)."""
-    h = table.view(torch.float16)
-    if frag:
-        h = h.view(rows_p // 32, units_p, 2, 32, 8).permute(0, 3, 1, 2, 4)
-    return h.reshape(rows_p, units_p * 16).float().cpu()
-
-
 @pytest.mark.parametrize('K', [13, 14, 15, 16, 17, 205, 206, 207, 510, 511])
 def test_one_product_table_carries_both_augmentation_columns(hip, K):
     """kge_lp_hi_rows / kge_lp_hi_rows_frag, L2 candidates: column K holds the f16 of -||e||^2 / 2 (scaled), column K + 1 the
@@ -288,7 +280,7 @@ def test_one_product_table_carries_both_augmentation_columns(hip, K):
     lib = hip.load_library()
     units_p, rows_p = int(lib.kge_lp_hi_units(K)), int(lib.kge_lp_split_rows_padded(N, 0))
     assert units_p * 16 >= K + 2
-    got = [_planar_halves(hip, hip.hi_table(dE, aug=en, frag=frag)[0], rows_p, units_p, frag) for frag in (False, True)]
+    got = [planar_halves(hip.hi_table(dE, aug=en, frag=frag)[0], rows_p, units_p, frag) for frag in (False, True)]
     assert torch.equal(got[0], got[1])
     H = got[0]
     scale = float(2.0 ** torch.round(torch.log2((H[:N, 0] / E[:, 0]).abs().median())))      # the operands' power-of-two scale

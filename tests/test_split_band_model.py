@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import oracle_clib, fptr
+from tests.operand_ref import hi_lo
 
 F = np.float32
 S = F(4096.0)                       # SPLIT_SCALE_LOG2 = 12
@@ -23,9 +24,7 @@ TWO24, TWO22 = F(2.0 ** -24), F(2.0 ** -22)
 
 def _split(x):
     """hi = f16(x * 2^12), lo = f16(x * 2^12 - hi)  (split_rows_kernel)."""
-    xs = (x.astype(F) * S).astype(F)
-    hi = xs.astype(np.float16)
-    lo = (xs - hi.astype(F)).astype(F).astype(np.float16)
+    hi, lo = hi_lo((x.astype(F) * S).astype(F))
     return hi.astype(np.float64), lo.astype(np.float64)
 
 

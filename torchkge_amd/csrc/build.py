@@ -20,7 +20,7 @@ SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfm
            'lp_pairs.hip', 'topk.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip', 'transr_xform.hip', 'analogy.hip', 'convkb.hip',
            'triplet.hip', 'segment_sum_rows.hip', 'segment_sum_ordered.hip', 'relation_corrupt.hip', 'row_optim.hip', 'pair_loss.hip',
            'redundancy.hip', 'lp_xent.hip']
-HEADERS = ['kge_common.h', 'lp_pair_exact.h', 'rel_operator.h','lp_split_common.h', 'lp_hi_sweep.h', 'mask_scan.h', 'segment_levels.h', os.path.join('..', '..', 'include', 'kge_hip.h'),
+HEADERS = ['kge_common.h', 'lp_pair_exact.h', 'rel_operator.h', 'lp_split_common.h', 'lp_operand_cells.h', 'lp_hi_sweep.h', 'mask_scan.h', 'segment_levels.h', os.path.join('..', '..', 'include', 'kge_hip.h'),
            os.path.join('..', '..', 'include', 'kge_hip_analogy.h'), os.path.join('..', '..', 'include', 'kge_hip_convkb.h'),
            os.path.join('..', '..', 'include', 'kge_hip_triplet.h'), os.path.join('..', '..', 'include', 'kge_hip_det.h'),
            os.path.join('..', '..', 'include', 'kge_hip_relation.h'), os.path.join('..', '..', 'include', 'kge_hip_rows.h'),

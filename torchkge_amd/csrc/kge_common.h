@@ -47,6 +47,22 @@ __device__ __forceinline__ void kge_atomic_max_u32(unsigned *addr, unsigned v)
     if (v > __builtin_nontemporal_load(addr)) atomicMax(addr, v);
 }
 
+// Maximum over the wavefront of BIT PATTERNS (non-negative floats sort like their bits, a NaN above +inf: it survives)
+__device__ __forceinline__ unsigned wave_max_u32(unsigned m)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    return m;
+}
+// ... over a block of 4 wavefronts, on every thread; sh[4] is the caller's (one barrier; reuse needs another in between)
+__device__ __forceinline__ unsigned block_max_u32(unsigned m, unsigned *sh)
+{
+    m = wave_max_u32(m);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+    __syncthreads();
+    return max(max(sh[0], sh[1]), max(sh[2], sh[3]));
+}
+
 __device__ __forceinline__ float wave_sum(float v)
 {
 #pragma unroll

@@ -8,6 +8,7 @@
 // floats) the engine keeps one scalar per (entity[,relation]).
 // One wavefront per row; all HBM-bound and tiny next to the scoring kernels.
 #include "lp_pair_exact.h"     // KGE_PS_KC / KGE_PS_LD, lp_pair_grid: the row kernels stage chunks of the same shape, 64 rows a wavefront
+#include "lp_operand_cells.h"  // the planar hi operand kge_lp_prep_hi emits
 
 namespace {
 
@@ -54,25 +55,19 @@ __global__ __launch_bounds__(WPB * 64) void lp_prep_kernel(const PrepParams p)
     const bool proj = p.side == KGE_SIDE_PROJ_H || p.side == KGE_SIDE_PROJ_T; // projection only, no relation term
     const int64_t nq = both ? 2 * p.B : p.B;
     const int hk = p.hi_units_p * 16;                       // f16 elements per row of Qh
-    const float hscale = 4096.0f;                           // (the L2 modes' fixed operand scale, SPLIT_SCALE_LOG2 = 12)
+    const float hscale = (float)(1 << SPLIT_SCALE_LOG2);    // (the L2 modes' fixed operand scale)
     float dn_acc = 0.f;
-    // one hi element: k < dr data, k == dr / dr + 1 the augmentation columns (1, 1), zeros behind
-    auto emit_hi = [&](_Float16 *qh, int k, float val) __attribute__((always_inline)) {
-        const float xs = val * hscale;
-        const _Float16 hh = (_Float16)xs;
-        const float dd = xs - (float)hh;
-        dn_acc = fmaf(dd, dd, dn_acc);
-        qh[k] = hh;
-    };
+    // one hi element of a query row (aug_mode 2): k < dr data, k == dr / dr + 1 the augmentation columns (1, 1), zeros behind
+    auto emit_hi = [&](_Float16 *qh, int k, float val) __attribute__((always_inline)) { qh[k] = cell_hi(val * hscale, dn_acc); };
     const int64_t n_rows = p.Qh ? p.Bp : nq;
     for (int64_t i = wave; i < n_rows; i += nwaves) {
-        _Float16 *qh = p.Qh ? p.Qh + i * hk : nullptr;
+        _Float16 *qh = p.Qh ? cell_row_planar(p.Qh, i, p.hi_units_p) : nullptr;
         if (i >= nq) {      // padding rows of the hi operand
             for (int k = lane; k < hk; k += 64) qh[k] = (_Float16)0.f;
             continue;
         }
         if (qh) {
-            for (int k = dr + lane; k < hk; k += 64) qh[k] = (_Float16)((k == dr || k == dr + 1) ? hscale : 0.f);
+            for (int k = dr + lane; k < hk; k += 64) qh[k] = (_Float16)((k == dr || k == dr + 1) ? aug_l2_query(1.0f, hscale) : 0.f);
             dn_acc = 0.f;
         }
         const bool tail = both ? i < p.B : p.side == KGE_SIDE_TAIL;
@@ -221,7 +216,7 @@ __global__ __launch_bounds__(WPB * 64) void lp_prep_kernel(const PrepParams p)
         }
         }
         if (qh && p.q_dn2) {    // ||q - hi(q)||^2, unscaled (a bound of the error band: any summation order, 1.0001 for it)
-            const float dn = wave_sum(dn_acc) * (1.0f / (hscale * hscale)) * 1.0001f;
+            const float dn = cell_resid_finish(wave_sum(dn_acc), hscale, RESID_SAFETY);
             if (lane == 0) p.q_dn2[i] = dn;
         }
     }
@@ -288,8 +283,7 @@ __global__ void row_sqnorm_kernel(const float *__restrict__ X, int64_t ld, int64
         big = __uint_as_float(max(__float_as_uint(big), __float_as_uint(acc)));
     }
     if (max_io) {
-        unsigned m = __float_as_uint(big);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+        const unsigned m = wave_max_u32(__float_as_uint(big));
         if ((threadIdx.x & 63) == 0) kge_atomic_max_u32(reinterpret_cast<unsigned *>(max_io), m);
     }
 }
@@ -354,8 +348,7 @@ __global__ __launch_bounds__(64 * NW) void row_sqnorm_staged_kernel(const float 
         }
     }
     if (max_io) {       // one atomic per block (same-address atomics serialise in the L2)
-        unsigned m = __float_as_uint(big);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+        const unsigned m = wave_max_u32(__float_as_uint(big));
         if (NW == 1) {
             if (lane == 0) kge_atomic_max_u32(reinterpret_cast<unsigned *>(max_io), m);
         } else {
@@ -417,12 +410,8 @@ __global__ __launch_bounds__(256) void row_sqnorm_any_kernel(const float *__rest
         }
     }
     if (max_io) {
-        unsigned m = __float_as_uint(big);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            kge_atomic_max_u32(reinterpret_cast<unsigned *>(max_io), max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
+        const unsigned m = block_max_u32(__float_as_uint(big), wmax);
+        if (threadIdx.x == 0) kge_atomic_max_u32(reinterpret_cast<unsigned *>(max_io), m);
     }
 }
 
@@ -559,8 +548,7 @@ __global__ __launch_bounds__(64 * NW) void proj_query_stats_kernel(const float *
 #undef KGE_QS_STORE
 #undef KGE_QS_FETCH
     if (qmax_io) {      // one atomic per block (same-address atomics serialise in the L2)
-        unsigned m = __float_as_uint(big);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+        const unsigned m = wave_max_u32(__float_as_uint(big));
         if (lane == 0) wmax[wv] = m;
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -1,10 +1,11 @@
 // Private to the four translation units of the certified f16-split prefilter -- lp_split_mfma.hip (error analysis,
 // thresholds, count sweep), lp_split_operands.hip (operand preparation), lp_split_query.hip (fused query side),
-// lp_split_recheck.hip (exact recheck): the tile geometry, the operand scale, and THE definition of each error band --
+// lp_split_recheck.hip (exact recheck): the tile geometry, THE definition of each error band (of the operands the bands
+// certify: lp_operand_cells.h) and the fold of per-block maxima into the device scalars the bands read --
 // the threshold kernel and the fused query pipelines call the same functions, so their thresholds agree bit for bit
 // (tests/test_gpu_parity.py::test_pipeline_thresholds_equal_the_threshold_kernel_bit_for_bit).
 #pragma once
-#include "kge_common.h"
+#include "lp_operand_cells.h"
 #ifndef KGE_BUILD_NO_SLP
 #error "build with -fno-slp-vectorize -DKGE_BUILD_NO_SLP=1 (torchkge_amd/csrc/build.py): SLP-packed v_pk_fma_f32 with a lane-crossing op_sel misreads beside co-executing MFMAs (profiles/r06/slp_bisect.txt)"
 #endif
@@ -13,17 +14,44 @@ namespace {
 
 constexpr int TQ = 192, TC = 256;               // 256 accumulator registers leave hipcc no slack: 4 x 3 tiles
 constexpr int GSETS = 4;                        // grouped columns: queries that share one query row (threshold sets per column)
-constexpr int SPLIT_SCALE_LOG2 = 12;
 constexpr int RR_ROWS = 32, RR_PANEL = 96;      // queries per region / per panel of the free-running sweep (lp_hi_stream.hip)
 
-// power-of-two scale that puts rows of squared norm <= norm2max just inside f16 range
-__device__ __forceinline__ float split_scale(float norm2max)
+// Per-block maxima left as plain stores by a producer kernel (bmax[2][n]; no same-address atomics, no zero-fill) -> the
+// two device scalars, folded into what those already hold (the guard vector is zeroed per evaluation, other shards may
+// add): EVERY block of a 256-thread consumer reduces them on its way in and gets (max0, max1), block 0 stores the
+// scalars.  s1 may be NULL: 0.  Values >= 0: ordered like their bits.  (A thread that reads a scalar after block 0 stored
+// it folds the same maximum in again.)
+__device__ __forceinline__ float2 split_fold_block_max2(const float *bmax, int n, float *s0, float *s1)
 {
-    const float m = sqrtf(norm2max);
-    if (!(m > 0.f) || !(m < INFINITY)) return 1.0f;
-    float e = floorf(log2f(16384.0f / m)) - 1.0f;      // one binade of slack for the roundings above
-    e = fminf(fmaxf(e, -100.0f), 100.0f);
-    return ldexpf(1.0f, (int)e);
+    __shared__ unsigned fold2[8];
+    unsigned m0 = 0u, m1 = 0u;
+    for (int j = threadIdx.x; j < n; j += 256) {
+        m0 = max(m0, __float_as_uint(bmax[j]));
+        m1 = max(m1, __float_as_uint(bmax[n + j]));
+    }
+    m0 = wave_max_u32(m0);
+    m1 = wave_max_u32(m1);
+    if ((threadIdx.x & 63) == 0) { fold2[threadIdx.x >> 6] = m0; fold2[4 + (threadIdx.x >> 6)] = m1; }
+    __syncthreads();
+    m0 = max(max(fold2[0], fold2[1]), max(fold2[2], fold2[3]));
+    m1 = max(max(fold2[4], fold2[5]), max(fold2[6], fold2[7]));
+    const float v0 = __uint_as_float(max(m0, __float_as_uint(*s0)));
+    const float v1 = s1 ? __uint_as_float(max(m1, __float_as_uint(*s1))) : 0.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *s0 = v0;
+        if (s1) *s1 = v1;
+    }
+    return make_float2(v0, v1);
+}
+// ... of one array bmax[n] into one scalar
+__device__ __forceinline__ float split_fold_block_max(const float *bmax, int n, float *s)
+{
+    __shared__ unsigned fold1[4];
+    unsigned m = 0u;
+    for (int j = threadIdx.x; j < n; j += 256) m = max(m, __float_as_uint(bmax[j]));
+    const float v = __uint_as_float(max(block_max_u32(m, fold1), __float_as_uint(*s)));
+    if (blockIdx.x == 0 && threadIdx.x == 0) *s = v;
+    return v;
 }
 
 // One step of the per-query magnitude sum: prefix += cell sum;  amag += sqrt(prefix * e2pref[u])

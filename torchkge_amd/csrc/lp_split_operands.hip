@@ -1,124 +1,104 @@
-// Operand preparation of the f16-split prefilter (lp_split_mfma.hip has the error analysis and the data layout): split
-// (hi, lo) rows, planar and fragment-major hi tables, the one-pass candidate-table preparations, and the maxima the
-// error bands are built from.
+// Operand preparation of the f16-split prefilter (lp_split_mfma.hip has the error analysis, lp_operand_cells.h the operand
+// formats every writer here is written on): split (hi, lo) rows, planar and fragment-major hi tables, the one-pass
+// candidate-table preparations, and the maxima the error bands are built from.
 #include "lp_split_common.h"
 
 namespace {
 
 struct SplitRowsParams {
-    const float *X0, *X1;     // segment 1 optional (ComplEx: [Re | Im])
-    int64_t ld0, ld1;
-    int K0, K1;
-    int64_t rows, rows_p;
-    int aug_mode;             // 0 none; 1: aug[row]*aug_mul (candidates, L2); 2: aug_mul (queries, L2);
-                              // 3: query guard column of the DOT mode; 4: 0 for real rows (candidates, DOT)
-    const float *aug;
-    float aug_mul;
-    const float *nmax0, *nmax1;   // device scalars: squared-norm maxima -> scale (NULL: 2^12)
+    RowSource s;
     int units_p;
     uint4 *out;
     float *cell_ss;           // optional [units_p][rows_p]: sum of squares of the cell's 16 data values (unscaled)
     const int64_t *row_index; // optional: output row r is built from source row row_index[r] of X0 / X1 / aug (gather)
 };
 
-// A block converts tiles of 16 rows x 16 k16 cells: 16 consecutive threads read one row's 1-KiB run (float4 loads where the
-// cell lies inside one K-segment and is 16-byte aligned) and write its 16 cells; the cells' sums of squares go through
-// LDS so that the unit-major cell_ss array is written in 64-byte runs as well (a thread-per-cell store there touches one
-// cache line per cell: it cost as much as the split table itself).
+// A block converts tiles of 16 rows x 16 k16 cells: 16 consecutive threads read one row's 1-KiB run (float4
+// loads where the cell lies inside one K-segment and is 16-byte aligned) and write its 16 cells; the cells' sums of squares
+// go through LDS so that the unit-major cell_ss array is written in 64-byte runs as well (a thread-per-cell store there
+// touches one cache line per cell: it cost as much as the split table itself).
 __global__ __launch_bounds__(256) void split_rows_kernel(const SplitRowsParams p)
 {
     __shared__ float ss_s[16][17];
     float scale = (float)(1 << SPLIT_SCALE_LOG2), nmax = 0.f;
-    if (p.nmax0) {
-        nmax = *p.nmax0 + (p.nmax1 ? *p.nmax1 : 0.f);
+    if (p.s.nmax0) {
+        nmax = *p.s.nmax0 + (p.s.nmax1 ? *p.s.nmax1 : 0.f);
         scale = split_scale(nmax);
     }
-    const int K = p.K0 + p.K1;
+    const int K = p.s.K0 + p.s.K1;
     const int tiles_u = (p.units_p + 15) / 16;
-    const int64_t n_tiles = (p.rows_p / 16) * tiles_u;          // rows_p is a multiple of the count kernel's tile
+    const int64_t n_tiles = (p.s.rows_p / 16) * tiles_u;          // rows_p is a multiple of the count kernel's tile
     const int tr_ = threadIdx.x >> 4, tu_ = threadIdx.x & 15;
-    const bool vec0 = (p.ld0 % 4 == 0) && ((size_t)p.X0 & 15) == 0;
-    const bool vec1 = p.X1 && (p.ld1 % 4 == 0) && ((size_t)p.X1 & 15) == 0 && (p.K0 % 4 == 0);
+    const bool vec0 = (p.s.ld0 % 4 == 0) && ((size_t)p.s.X0 & 15) == 0;
+    const bool vec1 = p.s.X1 && (p.s.ld1 % 4 == 0) && ((size_t)p.s.X1 & 15) == 0 && (p.s.K0 % 4 == 0);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t row = (tile / tiles_u) * 16 + tr_;
         const int u = (int)(tile % tiles_u) * 16 + tu_;
-        const int64_t srow = (p.row_index && row < p.rows) ? p.row_index[row] : row;    // (gathered source row)
+        const int64_t srow = (p.row_index && row < p.s.rows) ? p.row_index[row] : row;    // (gathered source row)
         float ss = 0.f;
         if (u < p.units_p) {
             const int k0 = u * 16;
             float xs[16];
 #pragma unroll
             for (int e = 0; e < 16; ++e) xs[e] = 0.f;
-            if (row < p.rows) {
-                if (k0 + 16 <= p.K0 && vec0) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X0 + srow * p.ld0 + k0);
+            if (row < p.s.rows) {
+                if (k0 + 16 <= p.s.K0 && vec0) {
+                    const float4 *src = reinterpret_cast<const float4 *>(p.s.X0 + srow * p.s.ld0 + k0);
 #pragma unroll
                     for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
-                } else if (k0 >= p.K0 && k0 + 16 <= K && vec1) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X1 + srow * p.ld1 + (k0 - p.K0));
+                } else if (k0 >= p.s.K0 && k0 + 16 <= K && vec1) {
+                    const float4 *src = reinterpret_cast<const float4 *>(p.s.X1 + srow * p.s.ld1 + (k0 - p.s.K0));
 #pragma unroll
                     for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int k = k0 + e;
-                        if (k < p.K0) xs[e] = p.X0[srow * p.ld0 + k];
-                        else if (k < K) xs[e] = p.X1[srow * p.ld1 + (k - p.K0)];
+                        if (k < p.s.K0) xs[e] = p.s.X0[srow * p.s.ld0 + k];
+                        else if (k < K) xs[e] = p.s.X1[srow * p.s.ld1 + (k - p.s.K0)];
                     }
                 }
             }
-            union { _Float16 h[16]; uint4 v[2]; } hi, lo;
+            Cell16 hi, lo;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int k = k0 + e;
                 float x = xs[e];
-                if (row < p.rows) {
+                if (row < p.s.rows) {
                     if (k < K) ss = fmaf(x, x, ss);
-                    else if (k == K && p.aug_mode == 1) x = p.aug[srow] * p.aug_mul;
-                    else if (k == K && p.aug_mode == 2) x = p.aug_mul;
-                    else if (k == K && p.aug_mode == 3) x = 0.25f * (sqrtf(p.aug[srow]) + sqrtf(nmax) * 0.00390625f);
+                    else if (k == K && p.s.aug_mode == 1) x = p.s.aug[srow] * p.s.aug_mul;
+                    else if (k == K && p.s.aug_mode == 2) x = p.s.aug_mul;
+                    else if (k == K && p.s.aug_mode == 3) x = 0.25f * (sqrtf(p.s.aug[srow]) + sqrtf(nmax) * 0.00390625f);
                 }
                 x *= scale;
-                if (row < p.rows && k == K && p.aug_mode == 3) x = fmaxf(x, 1.0f);
+                if (row < p.s.rows && k == K && p.s.aug_mode == 3) x = fmaxf(x, 1.0f);
                 _Float16 h = (_Float16)x;                   // round to nearest even
                 _Float16 l = (_Float16)(x - (float)h);      // x - hi is exact in fp32
-                if (row >= p.rows && k == K && (p.aug_mode == 1 || p.aug_mode == 4)) {
-                    // padding candidate: hi = lo = -65504 in the column that meets the queries' guard
-                    // column drives its accumulator below every threshold (L2: <= -2*65504*2^12 against
-                    // >= -16*2^24 for norm-guarded queries; DOT: <= -32752*S_q*||q|| against >= -16384*S_q*||q||)
-                    h = (_Float16)(-65504.f);
-                    l = (_Float16)(-65504.f);
+                if (row >= p.s.rows && k == K && (p.s.aug_mode == 1 || p.s.aug_mode == 4)) {
+                    h = (_Float16)AUG_PAD;                  // (can never count: lp_operand_cells.h)
+                    l = (_Float16)AUG_PAD;
                 }
                 hi.h[e] = h;
                 lo.h[e] = l;
             }
-            uint4 *o = p.out + (row * p.units_p + u) * 4;
+            uint4 *o = cell_addr_split(p.out, row, p.units_p, u);
             o[0] = hi.v[0]; o[1] = hi.v[1]; o[2] = lo.v[0]; o[3] = lo.v[1];
         }
         if (p.cell_ss) {        // (block-uniform)
             ss_s[tu_][tr_] = ss;
             __syncthreads();
             const int u2 = (int)(tile % tiles_u) * 16 + tr_;     // this thread now stores unit u2, row tu_ of the tile
-            if (u2 < p.units_p) p.cell_ss[(int64_t)u2 * p.rows_p + (tile / tiles_u) * 16 + tu_] = ss_s[tr_][tu_];
+            if (u2 < p.units_p) p.cell_ss[(int64_t)u2 * p.s.rows_p + (tile / tiles_u) * 16 + tu_] = ss_s[tr_][tu_];
             __syncthreads();
         }
     }
 }
 
 // ---- one-product level: PLANAR hi operands -----------------------------------------------------------------------
-// [rows_p][units_p][32 bytes]: the f16 hi parts of the 16 values of a k16 unit (units_p a multiple of 4: one 128-byte
-// row segment = one stage of the LV = 1 count kernel).  Two extra columns K, K+1: L2 candidates carry hi and lo of
-// -||e||^2/2 there (queries 1, 1), so the norm term keeps its 2^-22 precision; DOT queries their guard column at K.
-// Also emitted: dn2[row] = ||x - hi(x)||^2 (unscaled; the exact fp32 differences, summed) and its maximum.
+// The hi operand of lp_operand_cells.h (units_p a multiple of 4: one 128-byte row segment = one stage of the LV = 1 count
+// kernel), with dn2[row] = ||x - hi(x)||^2 (unscaled) and its maximum.
 struct HiRowsParams {
-    const float *X0, *X1;
-    int64_t ld0, ld1;
-    int K0, K1;
-    int64_t rows, rows_p;
-    int aug_mode;             // as SplitRowsParams
-    const float *aug;
-    float aug_mul;
-    const float *nmax0, *nmax1;
+    RowSource s;
     int units_p;
     uint4 *out;
     float *dn2;               // optional (rows)
@@ -130,10 +110,17 @@ struct HiRowsParams {
     const float *prev_nmax;   // hi_rows_frag_kernel<true> (r06, ONE pass over the table): the two squared-norm maxima a PREVIOUS
     float *nm_out;            //   evaluation measured fix the scale; this pass's maxima per block go to nm_out[2][gridDim.x] and
                               //   the consumer (dot_query_pipeline_kernel) raises the overflow flag if they ask for another scale
-    int frag;                 // 1: FRAGMENT-MAJOR output [rows_p / 32][units_p][64][16 B] -- chunk (row % 32) + 32 * k-half of
-                              // the 1-KiB block of (32-row group, unit): the A operand of v_mfma_f32_32x32x16_f16 in lane
-                              // order, one coalesced global_load_dwordx4 per block (lp_hi_stream.hip)
+    int frag;                 // 1: FRAGMENT-MAJOR output (lp_operand_cells.h), one coalesced global_load_dwordx4 per block of the
+                              // free-running sweep (lp_hi_stream.hip)
 };
+
+// the squared-norm maxima a norm pass left per block -> *nmax0 / *nmax1 (split_fold_block_max2) -> (scale, nmax)
+__device__ __forceinline__ float hi_rows_fold_scale(const HiRowsParams &p, float &nmax)
+{
+    const float2 n = split_fold_block_max2(p.nm_bmax, p.nm_blocks, const_cast<float *>(p.s.nmax0), const_cast<float *>(p.s.nmax1));
+    nmax = n.x + n.y;
+    return split_scale(nmax);
+}
 
 __global__ __launch_bounds__(256) void hi_rows_kernel(const HiRowsParams p)
 {
@@ -154,27 +141,27 @@ __global__ __launch_bounds__(256) void hi_rows_kernel(const HiRowsParams p)
         __syncthreads();
         m0 = max(max(red[0], red[1]), max(red[2], red[3]));
         m1 = max(max(red[4], red[5]), max(red[6], red[7]));
-        const float n0 = __uint_as_float(max(m0, __float_as_uint(*p.nmax0)));
-        const float n1 = p.nmax1 ? __uint_as_float(max(m1, __float_as_uint(*p.nmax1))) : 0.f;
+        const float n0 = __uint_as_float(max(m0, __float_as_uint(*p.s.nmax0)));
+        const float n1 = p.s.nmax1 ? __uint_as_float(max(m1, __float_as_uint(*p.s.nmax1))) : 0.f;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
-            *const_cast<float *>(p.nmax0) = n0;
-            if (p.nmax1) *const_cast<float *>(p.nmax1) = n1;
+            *const_cast<float *>(p.s.nmax0) = n0;
+            if (p.s.nmax1) *const_cast<float *>(p.s.nmax1) = n1;
         }
         nmax = n0 + n1;
         scale = split_scale(nmax);
-    } else if (p.nmax0) {
-        nmax = *p.nmax0 + (p.nmax1 ? *p.nmax1 : 0.f);
+    } else if (p.s.nmax0) {
+        nmax = *p.s.nmax0 + (p.s.nmax1 ? *p.s.nmax1 : 0.f);
         scale = split_scale(nmax);
     }
     const float inv2 = 1.0f / (scale * scale);
-    const int K = p.K0 + p.K1;
+    const int K = p.s.K0 + p.s.K1;
     const int tr_ = threadIdx.x >> 4, tu_ = threadIdx.x & 15;
-    const bool vec0 = (p.ld0 % 4 == 0) && ((size_t)p.X0 & 15) == 0;
-    const bool vec1 = p.X1 && (p.ld1 % 4 == 0) && ((size_t)p.X1 & 15) == 0 && (p.K0 % 4 == 0);
+    const bool vec0 = (p.s.ld0 % 4 == 0) && ((size_t)p.s.X0 & 15) == 0;
+    const bool vec1 = p.s.X1 && (p.s.ld1 % 4 == 0) && ((size_t)p.s.X1 & 15) == 0 && (p.s.K0 % 4 == 0);
     float dmax = 0.f;
-    for (int64_t r0 = (int64_t)blockIdx.x * 16; r0 < p.rows_p; r0 += (int64_t)gridDim.x * 16) {
+    for (int64_t r0 = (int64_t)blockIdx.x * 16; r0 < p.s.rows_p; r0 += (int64_t)gridDim.x * 16) {
         const int64_t row = r0 + tr_;
-        const bool real = row < p.rows;
+        const bool real = row < p.s.rows;
         const int64_t srow = (p.row_index && real) ? p.row_index[row] : row;
         float dn = 0.f;
         for (int u = tu_; u < p.units_p; u += 16) {
@@ -183,24 +170,24 @@ __global__ __launch_bounds__(256) void hi_rows_kernel(const HiRowsParams p)
 #pragma unroll
             for (int e = 0; e < 16; ++e) xs[e] = 0.f;
             if (real) {
-                if (k0 + 16 <= p.K0 && vec0) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X0 + srow * p.ld0 + k0);
+                if (k0 + 16 <= p.s.K0 && vec0) {
+                    const float4 *src = reinterpret_cast<const float4 *>(p.s.X0 + srow * p.s.ld0 + k0);
 #pragma unroll
                     for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
-                } else if (k0 >= p.K0 && k0 + 16 <= K && vec1) {
-                    const float4 *src = reinterpret_cast<const float4 *>(p.X1 + srow * p.ld1 + (k0 - p.K0));
+                } else if (k0 >= p.s.K0 && k0 + 16 <= K && vec1) {
+                    const float4 *src = reinterpret_cast<const float4 *>(p.s.X1 + srow * p.s.ld1 + (k0 - p.s.K0));
 #pragma unroll
                     for (int v = 0; v < 4; ++v) { const float4 t = src[v]; xs[4 * v] = t.x; xs[4 * v + 1] = t.y; xs[4 * v + 2] = t.z; xs[4 * v + 3] = t.w; }
                 } else if (k0 < K) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int k = k0 + e;
-                        if (k < p.K0) xs[e] = p.X0[srow * p.ld0 + k];
-                        else if (k < K) xs[e] = p.X1[srow * p.ld1 + (k - p.K0)];
+                        if (k < p.s.K0) xs[e] = p.s.X0[srow * p.s.ld0 + k];
+                        else if (k < K) xs[e] = p.s.X1[srow * p.s.ld1 + (k - p.s.K0)];
                     }
                 }
             }
-            union { _Float16 h[16]; uint4 v[2]; } hi;
+            Cell16 hi;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int k = k0 + e;
@@ -213,29 +200,23 @@ __global__ __launch_bounds__(256) void hi_rows_kernel(const HiRowsParams p)
                 if (k == K || k == K + 1) {                 // the augmentation columns
                     float a = 0.f;
                     if (real) {
-                        if (p.aug_mode == 1) {              // L2 candidates: hi (column K) and lo (column K + 1) of -||e||^2/2
-                            const float full = p.aug[srow] * p.aug_mul * scale;
+                        if (p.s.aug_mode == 1) {              // L2 candidates: hi (column K) and lo (column K + 1) of -||e||^2/2
+                            const float full = p.s.aug[srow] * p.s.aug_mul * scale;
                             const _Float16 fh = (_Float16)full;
                             a = k == K ? (float)fh : (float)(_Float16)(full - (float)fh);
-                        } else if (p.aug_mode == 2) {       // L2 queries: 1 against both
-                            a = p.aug_mul * scale;
-                        } else if (p.aug_mode == 3 && k == K) {   // DOT queries: the guard column (see split_rows_kernel)
-                            a = fmaxf(0.25f * (sqrtf(p.aug[srow]) + sqrtf(nmax) * 0.00390625f) * scale, 1.0f);
+                        } else if (p.s.aug_mode == 2) {       // L2 queries: 1 against both
+                            a = p.s.aug_mul * scale;
+                        } else if (p.s.aug_mode == 3 && k == K) {   // DOT queries: the guard column (see split_rows_kernel)
+                            a = aug_dot_guard(sqrtf(p.s.aug[srow]), sqrtf(nmax), scale);
                         }
-                    } else if ((p.aug_mode == 1 || (p.aug_mode == 4 && k == K))) {
-                        a = -65504.f;                       // padding candidate: can never count
+                    } else if ((p.s.aug_mode == 1 || (p.s.aug_mode == 4 && k == K))) {
+                        a = AUG_PAD;
                     }
                     h = (_Float16)a;
                 }
                 hi.h[e] = h;
             }
-            if (p.frag) {
-                uint4 *o = p.out + (((row >> 5) * p.units_p + u) << 6) + (row & 31);
-                o[0] = hi.v[0]; o[32] = hi.v[1];
-            } else {
-                uint4 *o = p.out + (row * p.units_p + u) * 2;
-                o[0] = hi.v[0]; o[1] = hi.v[1];
-            }
+            cell_store_hi(p.out, row, p.units_p, u, p.frag, hi);
         }
         dn += __shfl_xor(dn, 8, 64);    // the 16 lanes of a row sit in one aligned group of the wavefront
         dn += __shfl_xor(dn, 4, 64);
@@ -263,11 +244,12 @@ __global__ __launch_bounds__(256) void hi_rows_kernel(const HiRowsParams p)
 // fragment block 64 bytes at a time: at ComplEx d = 512 on 4.59 M entities it moves 28.8 GB in 8.9 ms (3.2 TB/s), the
 // address pipes being the limit, not HBM.  Here a block takes a 32-row group and walks the row in spans of 256 columns:
 // a wave reads 1 KiB of ONE row per instruction (lane l: columns 4 l .. 4 l + 3), converts, and leaves the f16 values in
-// an LDS tile laid out like the output -- [unit][k-half][row][16 B], a 16-byte pad per k-half block: the 16 lanes of a
+// an LDS tile laid out like the output's fragment blocks (lp_operand_cells.h) -- [unit][k-half][row][16 B], a 16-byte pad
+// per k-half block: the 16 lanes of a
 // write pass hit 16 different 8-byte bank pairs -- from which every wave then copies whole 1-KiB fragment blocks to the
 // table, one coalesced store per block.  Two LDS tiles, ONE barrier per span, the next span's loads in flight across it.
-// Same hi values as hi_rows_kernel (aug_mode 4: guard column K = 0 for real rows, -65504 for padding rows); the residual
-// sums are the same exact differences in another order (a bound input: any order, see the 1.0001 below).
+// Same hi values as hi_rows_kernel (aug_mode 4); the residual sums are the same exact differences in another order (a
+// bound input: any order, cell_resid_finish).
 // Needs float4-readable rows (K0, K1, ld % 4 == 0, 16-byte aligned bases).
 constexpr int HF_HST = 512 + 16, HF_UST = 2 * HF_HST;     // LDS strides of a k-half block / a unit
 
@@ -280,39 +262,19 @@ __global__ __launch_bounds__(256) void hi_rows_frag_kernel(const HiRowsParams p)
 {
     __shared__ __attribute__((aligned(16))) unsigned char tile[2][16 * HF_UST];
     __shared__ unsigned bmax[4], nbmax[8];
-    float scale, nmax;
+    const RowSource &src = p.s;
+    float nmax;
+    float scale;
     if (FUSED) {
         nmax = p.prev_nmax[0] + p.prev_nmax[1];
         scale = split_scale(nmax);
     } else {       // the block maxima of dot_table_norm_max_kernel -> the two scalars (as hi_rows_kernel)
-        __shared__ unsigned red[8];
-        unsigned m0 = 0u, m1 = 0u;
-        for (int j = threadIdx.x; j < p.nm_blocks; j += 256) {
-            m0 = max(m0, __float_as_uint(p.nm_bmax[j]));
-            m1 = max(m1, __float_as_uint(p.nm_bmax[p.nm_blocks + j]));
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = m0; red[4 + (threadIdx.x >> 6)] = m1; }
-        __syncthreads();
-        m0 = max(max(red[0], red[1]), max(red[2], red[3]));
-        m1 = max(max(red[4], red[5]), max(red[6], red[7]));
-        const float n0 = __uint_as_float(max(m0, __float_as_uint(*p.nmax0)));
-        const float n1 = p.nmax1 ? __uint_as_float(max(m1, __float_as_uint(*p.nmax1))) : 0.f;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            *const_cast<float *>(p.nmax0) = n0;
-            if (p.nmax1) *const_cast<float *>(p.nmax1) = n1;
-        }
-        nmax = n0 + n1;
-        scale = split_scale(nmax);
+        scale = hi_rows_fold_scale(p, nmax);
     }
-    const float inv2 = 1.0f / (scale * scale);
-    const int K = p.K0 + p.K1;
+    const int K = src.K0 + src.K1;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nspan = (p.units_p + 15) >> 4;
-    const int64_t ngroups = p.rows_p >> 5;
+    const int64_t ngroups = src.rows_p >> 5;
     const int wo = (lane >> 2) * HF_UST + ((lane >> 1) & 1) * HF_HST + (lane & 1) * 8;     // this lane's 8 bytes of a tile row
     const int ro = (lane >> 5) * HF_HST + (lane & 31) * 16;                                 // this lane's chunk of a fragment block
     float4 v[8];
@@ -326,9 +288,9 @@ __global__ __launch_bounds__(256) void hi_rows_frag_kernel(const HiRowsParams p)
         for (int j = 0; j < 8; ++j) {
             const int64_t row = g * 32 + wv * 8 + j;
             v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row < p.rows && col < K)
-                v[j] = col < p.K0 ? *reinterpret_cast<const float4 *>(p.X0 + row * p.ld0 + col)
-                                  : *reinterpret_cast<const float4 *>(p.X1 + row * p.ld1 + (col - p.K0));
+            if (row < src.rows && col < K)
+                v[j] = col < src.K0 ? *reinterpret_cast<const float4 *>(src.X0 + row * src.ld0 + col)
+                                  : *reinterpret_cast<const float4 *>(src.X1 + row * src.ld1 + (col - src.K0));
         }
     };
     int64_t g = blockIdx.x;
@@ -340,23 +302,16 @@ __global__ __launch_bounds__(256) void hi_rows_frag_kernel(const HiRowsParams p)
         const int col = s * 256 + 4 * lane;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const bool real = g * 32 + wv * 8 + j < p.rows;
+            const bool real = g * 32 + wv * 8 + j < src.rows;
             const float xs[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
             if (FUSED) {        // (padding lanes hold zeros)
                 const float ss = fmaf(xs[0], xs[0], fmaf(xs[1], xs[1], fmaf(xs[2], xs[2], xs[3] * xs[3])));
-                if (col < p.K0) nn0[j] += ss; else nn1[j] += ss;
+                if (col < src.K0) nn0[j] += ss; else nn1[j] += ss;
             }
             _Float16 h[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float x = xs[e] * scale;
-                h[e] = (_Float16)x;                         // round to nearest even
-                if (real && col < K) {                      // (K % 4 == 0: a float4 is data or padding as a whole)
-                    const float d = x - (float)h[e];        // exact in fp32
-                    dn[j] = fmaf(d, d, dn[j]);
-                }
-            }
-            if (col == K && !real) h[0] = (_Float16)(-65504.f);      // the guard column of a padding candidate: can never count
+            for (int e = 0; e < 4; ++e) h[e] = cell_hi(xs[e] * scale, dn[j]);   // (padding rows and columns hold zeros)
+            if (col == K && !real && aug_pad_column(4, 0)) h[0] = (_Float16)AUG_PAD;   // (K % 4 == 0: column K leads its float4)
             union { _Float16 hh[4]; uint2 u; } pk;
             pk.hh[0] = h[0]; pk.hh[1] = h[1]; pk.hh[2] = h[2]; pk.hh[3] = h[3];
             *reinterpret_cast<uint2 *>(tl + wo + (wv * 8 + j) * 16) = pk.u;
@@ -371,21 +326,19 @@ __global__ __launch_bounds__(256) void hi_rows_frag_kernel(const HiRowsParams p)
         for (int uu = 0; uu < 4; ++uu) {
             const int ul = wv * 4 + uu, u = s * 16 + ul;
             if (u < p.units_p)
-                p.out[((g * p.units_p + u) << 6) + lane] = *reinterpret_cast<const uint4 *>(tl + ul * HF_UST + ro);
+                cell_frag_block(p.out, g, p.units_p, u)[lane] = *reinterpret_cast<const uint4 *>(tl + ul * HF_UST + ro);
         }
         if (s == nspan - 1) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                float a = dn[j];
-                for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-                a *= inv2 * 1.0001f;    // (fp32 summation error: K * 2^-24 relative)
-                if (g * 32 + wv * 8 + j < p.rows) dmax = fmaxf(dmax, a);
+                float a = wave_sum(dn[j]);
+                a = cell_resid_finish(a, scale, RESID_SAFETY);
+                if (g * 32 + wv * 8 + j < src.rows) dmax = fmaxf(dmax, a);
                 dn[j] = 0.f;
                 if (FUSED) {
-                    float b0 = nn0[j], b1 = nn1[j];
-                    for (int off = 32; off > 0; off >>= 1) { b0 += __shfl_xor(b0, off, 64); b1 += __shfl_xor(b1, off, 64); }
-                    n0max = fmaxf(n0max, b0 * 1.0001f);     // (summation order: K * 2^-24 relative)
-                    n1max = fmaxf(n1max, b1 * 1.0001f);
+                    const float b0 = wave_sum(nn0[j]), b1 = wave_sum(nn1[j]);
+                    n0max = fmaxf(n0max, b0 * RESID_SAFETY);     // (summation order: K * 2^-24 relative)
+                    n1max = fmaxf(n1max, b1 * RESID_SAFETY);
                     nn0[j] = nn1[j] = 0.f;
                 }
             }
@@ -451,11 +404,7 @@ __global__ __launch_bounds__(256) void dot_table_norm_max_kernel(const float *__
         }
         if (sg) big1 = big; else big0 = big;
     }
-    unsigned m0 = __float_as_uint(big0), m1 = __float_as_uint(big1);
-    for (int off = 32; off > 0; off >>= 1) {
-        m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-        m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-    }
+    const unsigned m0 = wave_max_u32(__float_as_uint(big0)), m1 = wave_max_u32(__float_as_uint(big1));
     if ((threadIdx.x & 63) == 0) { wmax[threadIdx.x >> 6] = m0; wmax[4 + (threadIdx.x >> 6)] = m1; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -470,6 +419,7 @@ __global__ __launch_bounds__(256) void dot_table_norm_max_kernel(const float *__
 // ||e||^2 chains (row_sqnorm_kernel's: acc = fmaf(x_k, x_k, acc), k ascending -- the score contains en, same bits)
 // while all threads convert the data units to f16 hi parts (thread = row + 16 * unit: a unit's 16 rows are one 256-byte
 // run of the fragment-major table) and sum their residuals; the two augmentation columns follow once en is known.
+// The cells are lp_operand_cells.h's: aug_mode 1 on the fixed scale, aug = en, aug_mul = -0.5.
 struct TablePrepParams {
     const float *X;
     int64_t ld, rows, rows_p;
@@ -491,11 +441,8 @@ __global__ __launch_bounds__(256) void table_prep_l2_kernel(const TablePrepParam
     float *xs = tp_smem;                                    // [16][LDS_LD]
     float *dnp = xs + 16 * LDS_LD;                          // [16][17] partial residual sums
     float *ens = dnp + 16 * 17;                             // [16]
-    __shared__ unsigned bmax[2];
     const int tid = threadIdx.x, r = tid & 15, uu = tid >> 4;
     const float scale = (float)(1 << SPLIT_SCALE_LOG2);
-    const float inv2 = 1.0f / (scale * scale);
-    const int units_d = (K + 15) >> 4;                      // units that hold data columns
     float emax_b = 0.f, dmax_b = 0.f;
     for (int64_t r0 = (int64_t)blockIdx.x * 16; r0 < p.rows_p; r0 += (int64_t)gridDim.x * 16) {
         // stage the 16 rows (rows past the table: zeros)
@@ -530,18 +477,11 @@ __global__ __launch_bounds__(256) void table_prep_l2_kernel(const TablePrepParam
         for (int u = uu; u < p.units_p; u += 16) {
             const int k0 = u * 16;
             if (k0 + 16 <= K && !(p.dbg & 2)) {
-                union { _Float16 h[16]; uint4 v[2]; } hi;
+                Cell16 hi;
                 const float *x = xs + r * LDS_LD + k0;
 #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float xsj = x[e] * scale;
-                    const _Float16 h = (_Float16)xsj;
-                    const float d = xsj - (float)h;
-                    dn = fmaf(d, d, dn);
-                    hi.h[e] = h;
-                }
-                uint4 *o = p.out + (((row >> 5) * p.units_p + u) << 6) + (row & 31);
-                o[0] = hi.v[0]; o[32] = hi.v[1];
+                for (int e = 0; e < 16; ++e) hi.h[e] = cell_hi(x[e] * scale, dn);
+                cell_store_hi(p.out, row, p.units_p, u, true, hi);
             }
         }
         dnp[r * 17 + uu] = dn;
@@ -549,57 +489,44 @@ __global__ __launch_bounds__(256) void table_prep_l2_kernel(const TablePrepParam
         // units that straddle / follow K: data tail, the two augmentation columns (hi and lo of -||e||^2/2), zeros
         for (int u = (K >> 4) + uu; u < p.units_p; u += 16) {
             const int k0 = u * 16;
-            union { _Float16 h[16]; uint4 v[2]; } hi;
+            Cell16 hi;
             float dt = 0.f;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int k = k0 + e;
-                float a = 0.f;
+                _Float16 h = (_Float16)0.f;
                 if (k < K) {
-                    a = xs[r * LDS_LD + k] * scale;
-                    const float d = a - (float)(_Float16)a;
-                    dt = fmaf(d, d, dt);
-                } else if (k == K || k == K + 1) {
-                    if (real) {
-                        const float full = ens[r] * -0.5f * scale;
-                        const _Float16 fh = (_Float16)full;
-                        a = k == K ? (float)fh : (float)(_Float16)(full - (float)fh);
-                    } else {
-                        a = -65504.f;                       // padding candidate: can never count
-                    }
+                    h = cell_hi(xs[r * LDS_LD + k] * scale, dt);
+                } else if (k == K || k == K + 1) {          // (aug_mode 1)
+                    _Float16 lo;
+                    const _Float16 fh = cell_hi_lo(aug_l2_candidate(ens[r], -0.5f, scale), lo);
+                    h = real ? (k == K ? fh : lo) : (_Float16)AUG_PAD;
                 }
-                hi.h[e] = (_Float16)a;
+                hi.h[e] = h;
             }
             if (u == (K >> 4)) dnp[r * 17 + 16] = dt;           // (the one unit that may hold a data tail; always present)
-            uint4 *o = p.out + (((row >> 5) * p.units_p + u) << 6) + (row & 31);
-            o[0] = hi.v[0]; o[32] = hi.v[1];
+            cell_store_hi(p.out, row, p.units_p, u, true, hi);
         }
         __syncthreads();
         if (tid < 16 && real) {
             float t = 0.f;
             for (int j = 0; j < 17; ++j) t += dnp[r * 17 + j];
-            t *= inv2 * 1.0002f;                            // (fp32 summation error, any order: K * 2^-24 relative)
+            t = cell_resid_finish(t, scale, 1.0002f);       // (two levels of any-order fp32 sums)
             dmax_b = fmaxf(dmax_b, t);
         }
         __syncthreads();
     }
-    // one atomic per block for each maximum
+    // one store or atomic per block for each maximum (lanes 0..15 hold them, the other lanes 0)
     if (tid < 64) {
-        unsigned m0 = __float_as_uint(emax_b), m1 = __float_as_uint(dmax_b);
-        for (int off = 8; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if (tid == 0) { bmax[0] = m0; bmax[1] = m1; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        if (p.block_max) {
-            p.block_max[blockIdx.x] = __uint_as_float(bmax[0]);
-            p.block_max[gridDim.x + blockIdx.x] = __uint_as_float(bmax[1]);
-        } else {
-            if (p.en_max) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.en_max), bmax[0]);
-            if (p.dn2max) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.dn2max), bmax[1]);
+        const unsigned m0 = wave_max_u32(__float_as_uint(emax_b)), m1 = wave_max_u32(__float_as_uint(dmax_b));
+        if (tid == 0) {
+            if (p.block_max) {
+                p.block_max[blockIdx.x] = __uint_as_float(m0);
+                p.block_max[gridDim.x + blockIdx.x] = __uint_as_float(m1);
+            } else {
+                if (p.en_max) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.en_max), m0);
+                if (p.dn2max) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.dn2max), m1);
+            }
         }
     }
 }
@@ -622,8 +549,7 @@ __global__ __launch_bounds__(1024) void prefix_max_kernel(const float *__restric
         float prefix = 0.f;
         for (int u = 0; u < units_p; ++u) {
             if (r < rows) prefix += cell_ss[(int64_t)u * rows_p + r];
-            unsigned m = __float_as_uint(prefix);       // sums of squares: >= 0, ordered like their bit patterns
-            for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+            const unsigned m = wave_max_u32(__float_as_uint(prefix));       // sums of squares: >= 0, ordered like their bit patterns
             if (lane == 0) atomicMax(&smax[u], m);
         }
     }
@@ -653,13 +579,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ x
     } else {
         for (int64_t i = tid; i < n; i += nth) u = max(u, __float_as_uint(x[i]) & 0x7fffffffu);
     }
-    for (int off = 32; off > 0; off >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, off, 64));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = u;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
-        kge_atomic_max_u32(reinterpret_cast<unsigned *>(max_io), u);
-    }
+    u = block_max_u32(u, wmax);
+    if (threadIdx.x == 0) kge_atomic_max_u32(reinterpret_cast<unsigned *>(max_io), u);
 }
 
 // [X0 | X1] rows are float4-readable: column counts and row strides multiples of 4, 16-byte aligned bases
@@ -681,21 +602,38 @@ int row_operand_check(const float *X0, int64_t ld0, int K0, const float *X1, int
     return 0;
 }
 
-// The fields every hi table shares; the optional inputs and outputs start out absent (null).
-HiRowsParams hi_rows_params(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1, int64_t rows,
-                            int is_query, int aug_mode, const float *aug, float aug_mul, const float *nmax0,
-                            const float *nmax1, void *out, int frag)
+// The rows and the role of a table writer's input (both operand formats)
+RowSource row_source(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1, int64_t rows, int is_query,
+                     int aug_mode, const float *aug, float aug_mul, const float *nmax0, const float *nmax1)
+{
+    RowSource s;
+    s.X0 = X0; s.X1 = X1; s.ld0 = ld0; s.ld1 = ld1; s.K0 = K0; s.K1 = K1;
+    s.rows = rows;
+    s.rows_p = kge_lp_split_rows_padded(rows, is_query);
+    s.aug_mode = aug_mode; s.aug = aug; s.aug_mul = aug_mul;
+    s.nmax0 = nmax0; s.nmax1 = nmax1;
+    return s;
+}
+
+// A hi table of those rows; the optional inputs and outputs start out absent (null).
+HiRowsParams hi_rows_params(const RowSource &s, void *out, int frag)
 {
     HiRowsParams p = {};
-    p.X0 = X0; p.X1 = X1; p.ld0 = ld0; p.ld1 = ld1; p.K0 = K0; p.K1 = K1;
-    p.rows = rows;
-    p.rows_p = kge_lp_split_rows_padded(rows, is_query);
-    p.aug_mode = aug_mode; p.aug = aug; p.aug_mul = aug_mul;
-    p.nmax0 = nmax0; p.nmax1 = nmax1;
-    p.units_p = kge_lp_hi_units(K0 + K1);
+    p.s = s;
+    p.units_p = kge_lp_hi_units(s.K0 + s.K1);
     p.out = reinterpret_cast<uint4 *>(out);
     p.frag = frag;
     return p;
+}
+
+// The DOT candidate table of kge_lp_dot_table_prep / _fused (aug_mode 4), after their shared argument check
+int dot_table_source(const float *X0, int64_t ld0, int K0, const float *X1, int64_t ld1, int K1, int64_t rows,
+                     const float *nmax0, const float *nmax1, RowSource *s)
+{
+    if (rows <= 0 || K0 <= 0 || K1 < 0 || ld0 < K0 || (K1 > 0 && ld1 < K1)) return KGE_EINVAL;
+    if (!X0 || (K1 > 0 && !X1)) return KGE_EINVAL;
+    *s = row_source(X0, ld0, K0, K1 > 0 ? X1 : nullptr, ld1, K1, rows, 0, 4, nullptr, 0.f, nmax0, K1 > 0 ? nmax1 : nullptr);
+    return 0;
 }
 
 } // namespace
@@ -716,16 +654,12 @@ extern "C" int kge_lp_split_rows(const float *X0, int64_t ld0, int K0, const flo
     const int rc = row_operand_check(X0, ld0, K0, X1, ld1, K1, rows, is_query, 0, aug_mode, aug, out, &done);
     if (rc || done) return rc;
     SplitRowsParams p;
-    p.X0 = X0; p.X1 = X1; p.ld0 = ld0; p.ld1 = ld1; p.K0 = K0; p.K1 = K1;
-    p.rows = rows;
-    p.rows_p = kge_lp_split_rows_padded(rows, is_query);
-    p.aug_mode = aug_mode; p.aug = aug; p.aug_mul = aug_mul;
-    p.nmax0 = norm2max0; p.nmax1 = norm2max1;
+    p.s = row_source(X0, ld0, K0, X1, ld1, K1, rows, is_query, aug_mode, aug, aug_mul, norm2max0, norm2max1);
     p.units_p = kge_lp_split_units(K0 + K1, aug_mode != 0);
     p.out = reinterpret_cast<uint4 *>(out);
     p.cell_ss = cell_ss;
     p.row_index = row_index;
-    const int64_t total = (p.rows_p / 16) * ((p.units_p + 15) / 16);     // tiles of 16 rows x 16 cells
+    const int64_t total = (p.s.rows_p / 16) * ((p.units_p + 15) / 16);     // tiles of 16 rows x 16 cells
     if (total == 0) return 0;
     const int grid = (int)(total < 65536 ? total : 65536);
     hipLaunchKernelGGL(split_rows_kernel, dim3(grid), dim3(256), 0, kge_s(stream), p);
@@ -744,9 +678,10 @@ static int hi_rows_impl(const float *X0, int64_t ld0, int K0, const float *X1, i
     bool done;
     const int rc = row_operand_check(X0, ld0, K0, X1, ld1, K1, rows, is_query, 1, aug_mode, aug, out, &done);
     if (rc || done) return rc;
-    HiRowsParams p = hi_rows_params(X0, ld0, K0, X1, ld1, K1, rows, is_query, aug_mode, aug, aug_mul, norm2max0, norm2max1, out, frag);
+    HiRowsParams p = hi_rows_params(row_source(X0, ld0, K0, X1, ld1, K1, rows, is_query, aug_mode, aug, aug_mul, norm2max0,
+                                               norm2max1), out, frag);
     p.dn2 = dn2; p.dn2max = dn2max; p.row_index = row_index;
-    const int64_t blocks = p.rows_p / 16;
+    const int64_t blocks = p.s.rows_p / 16;
     if (blocks == 0) return 0;
     // every block ends with ONE same-address atomic (dn2max), and those serialise at ~20-30 ns each (measured r05 on the
     // fused table preparation: 1,824 of them cost 50 us): with a maximum to fold, two blocks per CU walk the rows
@@ -791,14 +726,14 @@ extern "C" int kge_lp_dot_table_prep(const float *X0, int64_t ld0, int K0, const
                                      int frag, float *norm2max0_io, float *norm2max1_io, void *out, float *dn_block_max,
                                      float *ws, kge_stream_t stream)
 {
-    if (rows <= 0 || K0 <= 0 || K1 < 0 || ld0 < K0 || (K1 > 0 && ld1 < K1)) return KGE_EINVAL;
-    if (!X0 || (K1 > 0 && (!X1 || !norm2max1_io)) || !norm2max0_io || !out || !dn_block_max || !ws) return KGE_EINVAL;
+    RowSource s;
+    if (int e = dot_table_source(X0, ld0, K0, X1, ld1, K1, rows, norm2max0_io, norm2max1_io, &s)) return e;
+    if ((K1 > 0 && !norm2max1_io) || !norm2max0_io || !out || !dn_block_max || !ws) return KGE_EINVAL;
     const int nb = kge_lp_dot_table_prep_blocks(rows, 0);
     hipLaunchKernelGGL(dot_table_norm_max_kernel, dim3(nb), dim3(256), 0, kge_s(stream), X0, ld0, K0,
                        K1 > 0 ? X1 : nullptr, ld1, K1, rows, ws);
     KGE_CHECK_LAUNCH();
-    HiRowsParams p = hi_rows_params(X0, ld0, K0, K1 > 0 ? X1 : nullptr, ld1, K1, rows, 0, 4, nullptr, 0.f, norm2max0_io,
-                                    K1 > 0 ? norm2max1_io : nullptr, out, frag ? 1 : 0);
+    HiRowsParams p = hi_rows_params(s, out, frag ? 1 : 0);
     p.nm_bmax = ws; p.nm_blocks = nb; p.dn_bmax = dn_block_max;
     // fragment-major tables of float4-readable rows: the coalesced kernel; unaligned or planar ones: the general one
     if (frag && rows_vec4(X0, ld0, K0, X1, ld1, K1))
@@ -820,10 +755,11 @@ extern "C" int kge_lp_dot_table_prep_fused(const float *X0, int64_t ld0, int K0,
                                            int64_t rows, const float *prev_nmax, void *out, float *dn_block_max,
                                            float *nm_block_max, kge_stream_t stream)
 {
-    if (rows <= 0 || K0 <= 0 || K1 < 0 || ld0 < K0 || (K1 > 0 && ld1 < K1)) return KGE_EINVAL;
-    if (!X0 || (K1 > 0 && !X1) || !prev_nmax || !out || !dn_block_max || !nm_block_max) return KGE_EINVAL;
+    RowSource s;
+    if (int e = dot_table_source(X0, ld0, K0, X1, ld1, K1, rows, nullptr, nullptr, &s)) return e;
+    if (!prev_nmax || !out || !dn_block_max || !nm_block_max) return KGE_EINVAL;
     if (!rows_vec4(X0, ld0, K0, X1, ld1, K1)) return KGE_EINVAL;
-    HiRowsParams p = hi_rows_params(X0, ld0, K0, K1 > 0 ? X1 : nullptr, ld1, K1, rows, 0, 4, nullptr, 0.f, nullptr, nullptr, out, 1);
+    HiRowsParams p = hi_rows_params(s, out, 1);
     p.dn_bmax = dn_block_max; p.prev_nmax = prev_nmax; p.nm_out = nm_block_max;
     hipLaunchKernelGGL(hi_rows_frag_kernel<true>, dim3(kge_lp_dot_table_prep_blocks(rows, 1)), dim3(256), 0, kge_s(stream), p);
     KGE_CHECK_LAUNCH();

@@ -1,5 +1,6 @@
-// Fused query side of the f16-split prefilter (lp_split_mfma.hip has the error analysis and the data layout): one launch
-// per batch writes the query rows, their norms, the exact true scores, the split operand and the thresholds.
+// Fused query side of the f16-split prefilter (lp_split_mfma.hip has the error analysis, lp_operand_cells.h the operand
+// formats): one launch per batch writes the query rows, their norms, the exact true scores, the split operand and the
+// thresholds.
 #include "lp_split_common.h"
 
 namespace {
@@ -36,7 +37,6 @@ struct QueryPipeParams {
                                     // that recomputes the thresholds: thr_ready = 0)
     const float *tp_bmax;           // optional [2][tp_blocks]: the block maxima kge_lp_table_prep_l2 left instead of its atomics:
     int tp_blocks;                  // every block reduces them (emax, de2max), block 0 stores the two scalars
-    float *emax_out, *de2max_out;
     int32_t *zero_i32;              // optional: zero_n int32 zeroed by this launch (the batch's rank counters)
     int64_t zero_n;
     int dbg;                        // env KGE_QP_DBG (timing probes, wrong results): 1 no chains, 2 no split cells, 4 no Q store,
@@ -58,29 +58,14 @@ __global__ __launch_bounds__(256) void query_pipeline_kernel(const QueryPipePara
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float *qs = qs_all + wv * QPW * LD, *ts = ts_all + wv * QPW * LD, *dnp = dnp_all + wv * QPW * 8;
     const int d = p.d, kpad = p.units_p * 16;
+    const float scale = (float)(1 << SPLIT_SCALE_LOG2);
     if (blockIdx.x == 0 && threadIdx.x == 0) *p.list_count = 0;
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.zero_n; j += (int64_t)gridDim.x * 256) p.zero_i32[j] = 0;
     float em, de2m = 0.f;
-    if (p.tp_bmax && !(p.dbg & 16)) {        // the table preparation's block maxima -> the two scalars (values >= 0: ordered like their bits)
-        __shared__ unsigned red[8];
-        unsigned m0 = 0u, m1 = 0u;
-        for (int j = threadIdx.x; j < p.tp_blocks; j += 256) {
-            m0 = max(m0, __float_as_uint(p.tp_bmax[j]));
-            m1 = max(m1, __float_as_uint(p.tp_bmax[p.tp_blocks + j]));
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            m0 = max(m0, (unsigned)__shfl_xor((int)m0, off, 64));
-            m1 = max(m1, (unsigned)__shfl_xor((int)m1, off, 64));
-        }
-        if (lane == 0) { red[wv] = m0; red[4 + wv] = m1; }
-        __syncthreads();
-        m0 = max(max(red[0], red[1]), max(red[2], red[3]));
-        m1 = max(max(red[4], red[5]), max(red[6], red[7]));
-        // (folded into what the scalars already hold -- the guard vector is zeroed per evaluation, other shards may add)
-        em = __uint_as_float(max(m0, __float_as_uint(*p.emax)));
-        de2m = __uint_as_float(max(m1, p.de2max ? __float_as_uint(*p.de2max) : 0u));
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0) { *p.emax_out = em; if (p.de2max_out) *p.de2max_out = de2m; }
+    if (p.tp_bmax && !(p.dbg & 16)) {        // the table preparation's block maxima -> the two scalars
+        const float2 m = split_fold_block_max2(p.tp_bmax, p.tp_blocks, const_cast<float *>(p.emax), const_cast<float *>(p.de2max));
+        em = m.x;
+        de2m = m.y;
     } else {
         em = *p.emax;
         if (p.level == 1) de2m = *p.de2max;
@@ -187,30 +172,25 @@ __global__ __launch_bounds__(256) void query_pipeline_kernel(const QueryPipePara
             for (int idx = lane; idx < QPW * ngr; idx += 64) {
                 const int rr = idx / ngr, gq = idx - rr * ngr;
                 const int64_t row = grp * QPW + rr;
-                union { _Float16 h[8]; uint4 v; } hi, lo;
+                Cell8 hi, lo;
                 float dsum = 0.f;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
+                for (int e = 0; e < 8; ++e) {       // (aug_mode 2, aug_mul 1: one augmentation column, level 1: two)
                     const int k = k0 + gq * 8 + e;
                     float xv = 0.f;
-                    if (row < p.B) xv = k < d ? qs[rr * LD + gq * 8 + e] : ((k == d || (p.level == 1 && k == d + 1)) ? 1.0f : 0.f);
-                    xv *= (float)(1 << SPLIT_SCALE_LOG2);
-                    const _Float16 hh = (_Float16)xv;
-                    hi.h[e] = hh;
-                    const float dd = xv - (float)hh;             // exact in fp32 (0 in the augmentation / padding columns)
-                    lo.h[e] = (_Float16)dd;
-                    dsum = fmaf(dd, dd, dsum);
+                    if (row < p.B) xv = k < d ? qs[rr * LD + gq * 8 + e] * scale : ((k == d || (p.level == 1 && k == d + 1)) ? aug_l2_query(1.0f, scale) : 0.f);
+                    hi.h[e] = cell_hi_lo(xv, lo.h[e]);
+                    cell_hi(xv, dsum);                           // (the differences are 0 in the augmentation / padding columns)
                 }
                 // level 1: the residual ||q - hi(q)||^2 is a BOUND of the error band (any summation order, 1.0001 for it):
                 // summed here on all 64 lanes -- on the chain lanes its 5 operations per element were 70 % of their work
                 if (p.level == 1) dnp[rr * 8 + gq] = dsum;
                 const int kk = k0 + gq * 8, u = kk >> 4, hf = (kk >> 3) & 1;
                 const int64_t dst = p.qs_row ? (row < p.B ? (int64_t)p.qs_row[row] : -1) : row;
-                if (dst >= 0 && p.level == 1) {      // planar hi operand: 32 bytes per unit
-                    uint4 *cell = reinterpret_cast<uint4 *>(p.Qs) + (dst * p.units_p + u) * 2;
-                    cell[hf] = hi.v;
+                if (dst >= 0 && p.level == 1) {      // planar hi operand
+                    cell_addr_planar(reinterpret_cast<uint4 *>(p.Qs), dst, p.units_p, u)[hf] = hi.v;
                 } else if (dst >= 0) {
-                    uint4 *cell = reinterpret_cast<uint4 *>(p.Qs) + (dst * p.units_p + u) * 4;
+                    uint4 *cell = cell_addr_split(reinterpret_cast<uint4 *>(p.Qs), dst, p.units_p, u);
                     cell[hf] = hi.v;
                     cell[2 + hf] = lo.v;
                 }
@@ -231,8 +211,7 @@ __global__ __launch_bounds__(256) void query_pipeline_kernel(const QueryPipePara
                     amag = -1.0f;
                 }
                 if (p.level == 1) {
-                    const float inv2 = 1.0f / ((float)(1 << SPLIT_SCALE_LOG2) * (float)(1 << SPLIT_SCALE_LOG2));
-                    const float dq2 = dn * inv2 * 1.0001f;
+                    const float dq2 = cell_resid_finish(dn, scale, RESID_SAFETY);
                     if (p.q_dn2) p.q_dn2[i] = dq2;
                     p.thr[i] = split_thr_l2_hi(qn, st, em, d, p.units, p.c_acc, p.eps_scale, dq2, de2m);
                 } else {
@@ -245,12 +224,8 @@ __global__ __launch_bounds__(256) void query_pipeline_kernel(const QueryPipePara
         }
     }
     if (p.qmax_io && !(p.dbg & 32)) {    // one atomic per block (same-address atomics serialise at ~12 ns each)
-        unsigned m = __float_as_uint(qbig);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if (lane == 0) wmax[wv] = m;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.qmax_io), max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
+        const unsigned m = block_max_u32(__float_as_uint(qbig), wmax);
+        if (threadIdx.x == 0) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.qmax_io), m);
     }
 }
 
@@ -344,21 +319,7 @@ __global__ __launch_bounds__(256) void dot_query_pipeline_kernel(const DotPipePa
             p.prev_nmax[1] = p.emax1 ? *p.emax1 : 0.f;
         }
     }
-    float de2m;
-    if (p.dn_bmax) {
-        __shared__ unsigned red[4];
-        unsigned m = 0u;
-        for (int j = threadIdx.x; j < p.dn_blocks; j += 256) m = max(m, __float_as_uint(p.dn_bmax[j]));
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if (lane == 0) red[wv] = m;
-        __syncthreads();
-        m = max(max(red[0], red[1]), max(red[2], red[3]));
-        de2m = __uint_as_float(max(m, __float_as_uint(*p.de2max)));
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0) *const_cast<float *>(p.de2max) = de2m;
-    } else {
-        de2m = *p.de2max;
-    }
+    const float de2m = p.dn_bmax ? split_fold_block_max(p.dn_bmax, p.dn_blocks, const_cast<float *>(p.de2max)) : *p.de2max;
     const float s_e = split_scale(em);
     if (blockIdx.x == 0 && threadIdx.x == 0 && !(em < INFINITY)) *p.overflow = 1.0f;
     float qbig = 0.f;
@@ -509,48 +470,41 @@ __global__ __launch_bounds__(256) void dot_query_pipeline_kernel(const DotPipePa
                 const float sc = sc_s[rr];
                 const float4 v0 = *reinterpret_cast<const float4 *>(qs + rr * LD + gq * 8);
                 const float4 v1 = *reinterpret_cast<const float4 *>(qs + rr * LD + gq * 8 + 4);
-                union { _Float16 h[8]; uint4 v; } hi;
+                Cell8 hi;
                 float dsum = 0.f;
-#define KGE_DP_CV(E, X)                                                                                      \
-    {                                                                                                        \
-        const float xsj = (X) * sc;                                                                          \
-        const _Float16 hh = (_Float16)xsj;                                                                   \
-        const float dd = xsj - (float)hh;                                                                    \
-        dsum = fmaf(dd, dd, dsum);                                                                           \
-        hi.h[E] = hh;                                                                                        \
-    }
+#define KGE_DP_CV(E, X) hi.h[E] = cell_hi((X) * sc, dsum);
                 KGE_DP_CV(0, v0.x) KGE_DP_CV(1, v0.y) KGE_DP_CV(2, v0.z) KGE_DP_CV(3, v0.w)
                 KGE_DP_CV(4, v1.x) KGE_DP_CV(5, v1.y) KGE_DP_CV(6, v1.z) KGE_DP_CV(7, v1.w)
 #undef KGE_DP_CV
                 dnp[rr * 8 + gq] = dsum;
                 const int kk = sg * d + k0 + gq * 8, u = kk >> 4, hf = (kk >> 3) & 1;
-                if (row < p.Bp) reinterpret_cast<uint4 *>(p.Qh)[(row * p.units_p + u) * 2 + hf] = hi.v;
+                if (row < p.Bp) cell_addr_planar(reinterpret_cast<uint4 *>(p.Qh), row, p.units_p, u)[hf] = hi.v;
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
             if (lane < QPW)
                 for (int gq = 0; gq < ngr; ++gq) dn += dnp[lane * 8 + gq];
         }
 #undef KGE_DP_FETCH
-        // the cells behind the data: the guard column at K (see hi_rows_kernel, aug_mode 3 -- with this row's own norm), zeros
+        // the cells behind the data: the guard column at K (aug_mode 3 -- from this row's own norm, twice), zeros
         const int ntail = (kpad - K) >> 3;
         for (int idx = lane; idx < QPW * ntail; idx += 64) {
             const int rr = idx / ntail, g = idx - rr * ntail;
             const int64_t row = grp * QPW + rr;
-            union { _Float16 h[8]; uint4 v; } hi;
+            Cell8 hi;
 #pragma unroll
             for (int e = 0; e < 8; ++e) hi.h[e] = (_Float16)0.f;
             if (g == 0 && row < p.B) {
                 const float qr = sqrtf(qn_s[rr]);
-                hi.h[0] = (_Float16)fmaxf(0.25f * (qr + qr * 0.00390625f) * sc_s[rr], 1.0f);
+                hi.h[0] = (_Float16)aug_dot_guard(qr, qr, sc_s[rr]);
             }
             const int kk = K + g * 8, u = kk >> 4, hf = (kk >> 3) & 1;
-            if (row < p.Bp) reinterpret_cast<uint4 *>(p.Qh)[(row * p.units_p + u) * 2 + hf] = hi.v;
+            if (row < p.Bp) cell_addr_planar(reinterpret_cast<uint4 *>(p.Qh), row, p.units_p, u)[hf] = hi.v;
         }
         if (lane < QPW && i < p.Bp) {
             if (valid) {
                 p.qn[i] = qn;
                 p.s_true[i] = acc;
-                const float dq2 = dn * (1.0f / (s_q * s_q)) * 1.0001f;
+                const float dq2 = cell_resid_finish(dn, s_q, RESID_SAFETY);
                 if (p.q_dn2) p.q_dn2[i] = dq2;
                 p.thr[i] = split_thr_dot_hi(qn, acc, em, K, p.units, p.c_acc, p.eps_scale, dq2, de2m, qn, s_q, s_e);
                 if (!(qn < INFINITY)) *p.overflow = 1.0f;
@@ -562,12 +516,8 @@ __global__ __launch_bounds__(256) void dot_query_pipeline_kernel(const DotPipePa
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // (qn_s / sc_s are rewritten by the next group)
     }
     if (p.qmax_io) {
-        unsigned m = __float_as_uint(qbig);
-        for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
-        if (lane == 0) wmax[wv] = m;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.qmax_io), max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
+        const unsigned m = block_max_u32(__float_as_uint(qbig), wmax);
+        if (threadIdx.x == 0) kge_atomic_max_u32(reinterpret_cast<unsigned *>(p.qmax_io), m);
     }
 }
 
@@ -602,7 +552,6 @@ extern "C" int kge_lp_query_pipeline(int side, const float *E, const float *R, i
     p.units = (d + 1 + 15) / 16; p.units_p = kge_lp_split_units(d, 1);
     p.level = level; p.de2max = de2max; p.q_dn2 = q_dn2;
     p.tp_bmax = tp_block_max; p.tp_blocks = tp_blocks;
-    p.emax_out = const_cast<float *>(emax); p.de2max_out = const_cast<float *>(de2max);
     if (tp_block_max && tp_blocks <= 0) return KGE_EINVAL;
     if (zero_n < 0 || (zero_n > 0 && !zero_i32)) return KGE_EINVAL;
     p.zero_i32 = zero_i32; p.zero_n = zero_n;
