@@ -25,7 +25,7 @@ HEADERS = ['kge_common.h', 'lp_pair_exact.h', 'rel_operator.h', 'lp_split_common
            os.path.join('..', '..', 'include', 'kge_hip_triplet.h'), os.path.join('..', '..', 'include', 'kge_hip_det.h'),
            os.path.join('..', '..', 'include', 'kge_hip_relation.h'), os.path.join('..', '..', 'include', 'kge_hip_rows.h'),
            os.path.join('..', '..', 'include', 'kge_hip_train.h'), os.path.join('..', '..', 'include', 'kge_hip_redundancy.h'),
-           os.path.join('..', '..', 'include', 'kge_hip_xent.h')]
+           os.path.join('..', '..', 'include', 'kge_hip_xent.h'), os.path.join('..', '..', 'include', 'kge_hip_plan.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
 # libkge_hip.so does not depend on librccl

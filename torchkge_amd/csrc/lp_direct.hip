@@ -24,6 +24,7 @@
 // group-of-four accumulation, and the reference's (b, N, d) broadcast is never
 // built.
 #include "kge_common.h"
+#include "../../include/kge_hip_plan.h"
 
 namespace {
 
@@ -42,6 +43,48 @@ struct DirectParams {
     const int64_t *rep;
     const int32_t *qmap;
 };
+
+// The work split, one definition for both kernels, both launchers and kge_lp_direct_plan (include/kge_hip_plan.h).
+// Launch side: about KGE_LP_TARGET_BLOCKS (default 16384) blocks, each ONE row panel x tiles_per_block consecutive
+// candidate tiles.
+struct DirectPlan {
+    int row_panels, col_tiles, tiles_per_block, col_chunks, grid;
+};
+inline DirectPlan direct_plan(int64_t B, int64_t N, int bm)
+{
+    DirectPlan pl;
+    pl.row_panels = (int)((B + bm - 1) / bm);
+    pl.col_tiles = (int)((N + BN - 1) / BN);
+    const int target_blocks = kge_env_int("KGE_LP_TARGET_BLOCKS", 16384);
+    int chunks = (target_blocks + pl.row_panels - 1) / pl.row_panels;
+    if (chunks > pl.col_tiles) chunks = pl.col_tiles;
+    if (chunks < 1) chunks = 1;
+    pl.tiles_per_block = (pl.col_tiles + chunks - 1) / chunks;
+    pl.col_chunks = (pl.col_tiles + pl.tiles_per_block - 1) / pl.tiles_per_block;
+    pl.grid = pl.row_panels * pl.col_chunks;
+    return pl;
+}
+inline int plan_launch(DirectParams &p, int bm)
+{
+    const DirectPlan pl = direct_plan(p.d.B, p.d.N, bm);
+    p.row_panels = pl.row_panels; p.col_tiles = pl.col_tiles;
+    p.tiles_per_block = pl.tiles_per_block; p.col_chunks = pl.col_chunks;
+    return pl.grid;
+}
+// Block side: block `bid` of `nb` takes slot lid -- blocks resident on one XCD (bid % 8) get adjacent slots -- that is
+// row panel lid % row_panels and the tiles [tile_begin, tile_end) of column chunk lid / row_panels.
+struct TileRange {
+    int rp, tile_begin, tile_end;
+};
+__host__ __device__ inline TileRange block_tiles(int nb, int bid, int row_panels, int tiles_per_block, int col_tiles)
+{
+    const int xq = nb >> 3, xr = nb & 7, xcd = bid & 7, loc = bid >> 3;
+    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + loc;
+    const int rp = lid % row_panels, cc = lid / row_panels;
+    const int tile_begin = cc * tiles_per_block;
+    const int tile_last = tile_begin + tiles_per_block;
+    return {rp, tile_begin, tile_last < col_tiles ? tile_last : col_tiles};
+}
 
 template <bool VEC4>
 __device__ __forceinline__ void g_load8(const float *__restrict__ base, int64_t ld, int64_t row,
@@ -84,14 +127,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void lp_direct_kernel(const DirectPara
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
 
-    const int nblk_grid = gridDim.x, bid = blockIdx.x;
-    const int xq = nblk_grid >> 3, xr = nblk_grid & 7, xcd = bid & 7, loc = bid >> 3;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + loc;
-    const int rp = lid % p.row_panels, cc = lid / p.row_panels;
-    const int64_t row0 = (int64_t)rp * BM;
-    const int tile_begin = cc * p.tiles_per_block;
-    const int tile_end = min(tile_begin + p.tiles_per_block, p.col_tiles);
-    const int ntiles = tile_end - tile_begin;
+    const TileRange range = block_tiles(gridDim.x, blockIdx.x, p.row_panels, p.tiles_per_block, p.col_tiles);
+    const int64_t row0 = (int64_t)range.rp * BM;
+    const int tile_begin = range.tile_begin;
+    const int ntiles = range.tile_end - tile_begin;
     if (ntiles <= 0) return;
 
     const int K = d.K0;
@@ -326,14 +365,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void lp_direct_pk_kernel(const DirectP
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
 
-    const int nblk_grid = gridDim.x, bid = blockIdx.x;
-    const int xq = nblk_grid >> 3, xr = nblk_grid & 7, xcd = bid & 7, loc = bid >> 3;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + loc;
-    const int rp = lid % p.row_panels, cc = lid / p.row_panels;
-    const int64_t row0 = (int64_t)rp * BM;
-    const int tile_begin = cc * p.tiles_per_block;
-    const int tile_end = min(tile_begin + p.tiles_per_block, p.col_tiles);
-    const int ntiles = tile_end - tile_begin;
+    const TileRange range = block_tiles(gridDim.x, blockIdx.x, p.row_panels, p.tiles_per_block, p.col_tiles);
+    const int64_t row0 = (int64_t)range.rp * BM;
+    const int tile_begin = range.tile_begin;
+    const int ntiles = range.tile_end - tile_begin;
     if (ntiles <= 0) return;
 
     const int K = d.K0;                 // K % 4 == 0 (the dispatcher checks)
@@ -558,16 +593,7 @@ int launch_pk(DirectParams &p, hipStream_t s)
     constexpr int BM = 16 * TM;
     constexpr int BUF_FLOATS = BM * LDS_LD * (AXPY ? 2 : 1) + BK * LDT_PK;
     constexpr int SMEM_BYTES = 2 * BUF_FLOATS * 4 + 2 * GS * BM * 4;
-    const kge_lp_desc &d = p.d;
-    p.row_panels = (int)((d.B + BM - 1) / BM);
-    p.col_tiles = (int)((d.N + BN - 1) / BN);
-    const int target_blocks = kge_env_int("KGE_LP_TARGET_BLOCKS", 16384);
-    int chunks = (target_blocks + p.row_panels - 1) / p.row_panels;
-    if (chunks > p.col_tiles) chunks = p.col_tiles;
-    if (chunks < 1) chunks = 1;
-    p.tiles_per_block = (p.col_tiles + chunks - 1) / chunks;
-    p.col_chunks = (p.col_tiles + p.tiles_per_block - 1) / p.tiles_per_block;
-    const int grid = p.row_panels * p.col_chunks;
+    const int grid = plan_launch(p, BM);
     auto k = lp_direct_pk_kernel<AXPY, COUNT, TM, GS>;
     static int attr_dev[16];    // per instantiation, per device
     if (int e = kge_ensure_dyn_smem(reinterpret_cast<const void *>(k), SMEM_BYTES, attr_dev)) return e;
@@ -583,17 +609,7 @@ int launch(DirectParams &p, hipStream_t s)
     constexpr int BM = 16 * TM;
     constexpr int BUF_FLOATS = BM * LDS_LD * (AXPY ? 2 : 1) + BN * LDS_LD;
     constexpr int SMEM_BYTES = 2 * BUF_FLOATS * 4 + 2 * BM * 4;
-    const kge_lp_desc &d = p.d;
-    p.row_panels = (int)((d.B + BM - 1) / BM);
-    p.col_tiles = (int)((d.N + BN - 1) / BN);
-    const int target_blocks = kge_env_int("KGE_LP_TARGET_BLOCKS", 16384);
-    int chunks = (target_blocks + p.row_panels - 1) / p.row_panels;
-    if (chunks > p.col_tiles) chunks = p.col_tiles;
-    if (chunks < 1) chunks = 1;
-    p.tiles_per_block = (p.col_tiles + chunks - 1) / chunks;
-    p.col_chunks = (p.col_tiles + p.tiles_per_block - 1) / p.tiles_per_block;
-    const int grid = p.row_panels * p.col_chunks;
-
+    const int grid = plan_launch(p, BM);
     auto k = lp_direct_kernel<VEC4, OP, AXPY, COUNT, TM>;
     static int attr_dev[16];    // per instantiation, per device
     if (int e = kge_ensure_dyn_smem(reinterpret_cast<const void *>(k), SMEM_BYTES, attr_dev)) return e;
@@ -626,6 +642,25 @@ int dispatch_torus_mode(DirectParams &p, bool count, hipStream_t s)
 }
 
 } // namespace
+
+extern "C" int kge_lp_direct_plan(int64_t B, int64_t N, int axpy, int64_t *plan, int64_t *blocks)
+{
+    static_assert(BN == KGE_LP_DIRECT_BN && 16 * 8 == KGE_LP_DIRECT_BM_PLAIN && 16 * 4 == KGE_LP_DIRECT_BM_AXPY,
+                  "kge_hip_plan.h publishes the tile sizes of launch / launch_pk (BM = 16 * TM, TM = AXPY ? 4 : 8)");
+    if (B < 0 || N < 0 || !plan) return KGE_EINVAL;
+    if (B == 0 || N == 0) {
+        plan[0] = plan[1] = plan[2] = plan[3] = 0;
+        return 0;
+    }
+    const DirectPlan pl = direct_plan(B, N, axpy ? KGE_LP_DIRECT_BM_AXPY : KGE_LP_DIRECT_BM_PLAIN);
+    plan[0] = pl.row_panels; plan[1] = pl.col_tiles; plan[2] = pl.tiles_per_block; plan[3] = pl.grid;
+    if (blocks)
+        for (int bid = 0; bid < pl.grid; ++bid) {
+            const TileRange r = block_tiles(pl.grid, bid, pl.row_panels, pl.tiles_per_block, pl.col_tiles);
+            blocks[3 * bid] = r.rp; blocks[3 * bid + 1] = r.tile_begin; blocks[3 * bid + 2] = r.tile_end;
+        }
+    return 0;
+}
 
 // Rank counts of a plain KGE_LP_L2_DIRECT problem over query COLUMNS (the packed-FMA kernel): rows [0, n_single_p) carry
 // one query each (col_q), rows [n_single_p, n_single_p + n_multi_p) up to 4 (members); row r is the query row rep[r].

@@ -28,12 +28,13 @@
 //  * rank counts live in registers across a range and are flushed with one
 //    LDS reduction + one global atomic per row when the row panel changes.
 #include "kge_common.h"
+#include "../../include/kge_hip_plan.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 32, LDS_LD = BK + 4;
+constexpr int BM = KGE_LP_GEMM_BM, BN = KGE_LP_GEMM_BN, BK = 32, LDS_LD = BK + 4;
 constexpr int TILE_FLOATS = BM * LDS_LD;                     // one operand tile
 constexpr int SMEM_BYTES = 4 * TILE_FLOATS * 4 + 6 * BM * 4; // 2 bufs x (A,B) + row counters, s_true, qn, (p, z, X row) of the PROJ modes
 
@@ -48,6 +49,22 @@ struct GemmParams {
     int dbg;           // env KGE_DBG: 1 = every block loads tile (0,0) (cache-ceiling probe, wrong results)
 };
 
+// The work split, one definition for the kernel and for kge_lp_gemm_plan (include/kge_hip_plan.h): block `bid` of `nb`
+// walks range number lid -- blocks resident on one XCD (bid % 8) get adjacent ranges -- of the nb contiguous, balanced
+// ranges [n_items * lid / nb, n_items * (lid + 1) / nb) of (row panel, tile) items.
+struct ItemRange {
+    int lid;
+    int64_t begin, end;
+};
+__host__ __device__ inline ItemRange block_items(int64_t n_items, int nb, int bid)
+{
+    const int xq = nb >> 3, xr = nb & 7, xcd = bid & 7, loc = bid >> 3;
+    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + loc;
+    return {lid, n_items * lid / nb, n_items * (lid + 1) / nb};
+}
+// 8-bit rank counters: a lane's byte gains at most NT per tile, so it is flushed every 255 / NT tiles of one panel
+__host__ __device__ constexpr int flush_interval(int nt) { return 255 / nt; }
+
 template <bool VEC4, bool COUNT, int MODE, int NWM, int NWN>
 __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN) / 2) void lp_gemm_kernel(const GemmParams p)
 {
@@ -61,12 +78,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN) / 2) void lp_gemm_kerne
     const int wr = wid / NWN, wc = wid % NWN;
     const int l31 = lane & 31, half = lane >> 5;
 
-    // contiguous, balanced range of (row panel, tile) items for this block;
-    // blocks resident on one XCD (bid % 8) get adjacent ranges
-    const int nb = gridDim.x, bid = blockIdx.x;
-    const int xq = nb >> 3, xr = nb & 7, xcd = bid & 7, loc = bid >> 3;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + loc;
-    const int64_t item_begin = p.n_items * lid / nb, item_end = p.n_items * (lid + 1) / nb;
+    // contiguous, balanced range of (row panel, tile) items for this block
+    const ItemRange range = block_items(p.n_items, gridDim.x, blockIdx.x);
+    const int64_t item_begin = range.begin, item_end = range.end;
     const int nitems = (int)(item_end - item_begin);
     if (nitems <= 0) return;
 
@@ -386,7 +400,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (NWM * NWN) / 2) void lp_gemm_kerne
                     else __syncthreads();
                     cur_row0 = next_row0;
                     load_panel(cur_row0);
-                } else if (COUNT && ++tiles_since_flush >= 255 / NT) { // 8-bit counters: +NT at most per tile
+                } else if (COUNT && ++tiles_since_flush >= flush_interval(NT)) { // 8-bit counters: +NT at most per tile
                     flush_counts(cur_row0);
                 }
             }
@@ -443,6 +457,38 @@ int num_cus()
 
 } // namespace
 
+// one balanced range per resident block slot: 2 blocks (75 KB LDS each) per CU
+static int launch_grid(int64_t n_items)
+{
+    const int slots = num_cus() * 2 * kge_env_int("KGE_LP_ROUNDS", 1);
+    return (int)(n_items < slots ? n_items : slots);
+}
+
+extern "C" int kge_lp_gemm_plan(int64_t B, int64_t N, int grid, int64_t *dims, int64_t *blocks)
+{
+    if (B < 0 || N < 0 || grid < 0) return KGE_EINVAL;
+    const int64_t row_panels = (B + BM - 1) / BM, col_tiles = (N + BN - 1) / BN;
+    if (row_panels > INT32_MAX || col_tiles > INT32_MAX || row_panels * col_tiles > INT32_MAX) return KGE_EINVAL;
+    const int64_t n_items = row_panels * col_tiles;
+    if (dims) { dims[0] = row_panels; dims[1] = col_tiles; }
+    if (n_items == 0) return 0;
+    if (grid == 0) grid = launch_grid(n_items);
+    if (blocks)
+        for (int bid = 0; bid < grid; ++bid) {
+            const ItemRange r = block_items(n_items, grid, bid);
+            blocks[3 * bid] = r.lid; blocks[3 * bid + 1] = r.begin; blocks[3 * bid + 2] = r.end;
+        }
+    return grid;
+}
+
+// both wave layouts kge_lp_gemm_run dispatches (2x2 and, under KGE_LP_WAVES=8, 4x2) have two waves along N
+constexpr int LAYOUT_NWN = 2;
+
+extern "C" int kge_lp_gemm_flush_interval(void)
+{
+    return flush_interval(BN / (32 * LAYOUT_NWN));  // NT of lp_gemm_kernel
+}
+
 // Internal entry shared by kge_lp_scores / kge_lp_count_ge for the MFMA modes.
 int kge_lp_gemm_run(const kge_lp_desc *d, float *out, int64_t ldo, const float *s_true,
                     int32_t *raw_count, hipStream_t s)
@@ -459,9 +505,7 @@ int kge_lp_gemm_run(const kge_lp_desc *d, float *out, int64_t ldo, const float *
     p.col_tiles = (int)((d->N + BN - 1) / BN);
     p.n_items = (int64_t)p.row_panels * p.col_tiles;
     p.dbg = kge_env_int("KGE_DBG", 0);
-    // one balanced range per resident block slot: 2 blocks (75 KB LDS each) per CU
-    const int slots = num_cus() * 2 * kge_env_int("KGE_LP_ROUNDS", 1);
-    const int grid = (int)(p.n_items < slots ? p.n_items : slots);
+    const int grid = launch_grid(p.n_items);
 
     bool vec4 = (d->K0 % 4 == 0) && (d->lda0 % 4 == 0) && (d->ldt0 % 4 == 0) &&
                 kge_aligned16(d->A0) && kge_aligned16(d->T0);
@@ -472,6 +516,6 @@ int kge_lp_gemm_run(const kge_lp_desc *d, float *out, int64_t ldo, const float *
     const bool count = raw_count != nullptr;
     // 4 waves (2x2 MFMA tiles each) measured ~1% ahead of 8 waves (1x2) on MI355X and has no spills
     if (kge_env_int("KGE_LP_WAVES", 4) == 4)
-        return count ? dispatch<true, 2, 2>(p, vec4, grid, s) : dispatch<false, 2, 2>(p, vec4, grid, s);
-    return count ? dispatch<true, 4, 2>(p, vec4, grid, s) : dispatch<false, 4, 2>(p, vec4, grid, s);
+        return count ? dispatch<true, 2, LAYOUT_NWN>(p, vec4, grid, s) : dispatch<false, 2, LAYOUT_NWN>(p, vec4, grid, s);
+    return count ? dispatch<true, 4, LAYOUT_NWN>(p, vec4, grid, s) : dispatch<false, 4, LAYOUT_NWN>(p, vec4, grid, s);
 }
