@@ -568,6 +568,13 @@ class Model(Module):
         raise NotImplementedError('torchkge_amd: %s has no one_vs_all_loss; DistMultModel and ComplExModel have it'
                                   % type(self).__name__)
 
+    def k_vs_all_loss(self, ent_idx, r_idx, labels, side, label_smoothing=0.0, reduction='mean'):
+        """K-vs-all training criterion (torchkge_amd.utils.k_vs_all).  DistMultModel and ComplExModel have it: the
+        other bilinear models need a backward of their query transforms, the translational ones the gradient of the
+        L2 epilogue."""
+        raise NotImplementedError('torchkge_amd: %s has no k_vs_all_loss; DistMultModel and ComplExModel have it'
+                                  % type(self).__name__)
+
     def normalize_parameters(self):
         raise NotImplementedError
 

@@ -18,7 +18,9 @@ What is the engine's own:
     ``run`` asks its loader for them before the first iteration and raises).
 
 ``OneVsAllTrainer`` is the engine's own: the same epochs without a sampler, on ``model.one_vs_all_loss`` (the softmax
-cross-entropy over all entities of torchkge_amd.utils.one_vs_all; DistMultModel and ComplExModel).
+cross-entropy over all entities of torchkge_amd.utils.one_vs_all; DistMultModel and ComplExModel).  ``KvsAllTrainer``
+is its multi-label counterpart: the distinct keys of the graph as queries, ``model.k_vs_all_loss`` (binary cross-entropy
+over all entities against each key's answer set, torchkge_amd.utils.k_vs_all) as the criterion.
 
 The models live on the GPU: ``use_cuda`` is 'all' or 'batch'."""
 import contextlib
@@ -300,3 +302,137 @@ class OneVsAllTrainer:
             self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
         return self._epoch_losses
 
+
+
+class KvsAllTrainer:
+    """K-vs-all training of a model with ``k_vs_all_loss`` (DistMultModel, ComplExModel): a query is a distinct key of
+    the training graph -- (h, r) on the tail side, (t, r) on the head side -- its label the whole set of known answers,
+    the criterion a binary cross-entropy with logits over ALL entities (torchkge_amd.utils.k_vs_all), without the (B, N)
+    score, label or gradient matrix.
+
+    The labels are two ``FilterIndex``es built once from ``kg_train``'s own triples (``from_triples_torch`` with the
+    bounds n_ent, n_rel, n_ent): (h, r) -> tails and (t, r) -> heads.  An epoch walks the distinct keys of the chosen
+    side(s) in index order -- ``side='both'``: the tail side's batches, then the head side's -- in batches of
+    ``batch_size`` keys, the last of a side short; a batch's segments are slices of the index's ``offsets`` and its
+    answers are read in place from the index's ``targets``.  There is no sampler and no criterion;
+    ``model.normalize_parameters()`` runs after each epoch, ``epoch_losses`` holds the mean step loss
+    (``sync_free=True``: the steps add into one device float per epoch, read back on first access).
+
+    The entity tables' gradient is dense in this regime, so the row-wise optimizers of ``torchkge_amd.optim`` are
+    refused: use a ``torch.optim`` optimizer."""
+
+    def __init__(self, model, kg_train, n_epochs, batch_size, optimizer, label_smoothing=0.0, side='both', use_cuda='all',
+                 *, sync_free=False, verbose=True):
+        if use_cuda not in ('all', 'batch'):
+            raise ValueError("KvsAllTrainer: use_cuda must be 'all' or 'batch', got %r -- the engine's models live on the "
+                             "GPU, there is no CPU training path" % (use_cuda,))
+        if side not in ('both', 'tail', 'head'):
+            raise ValueError("KvsAllTrainer: side is 'both', 'tail' or 'head', got %r" % (side,))
+        if isinstance(optimizer, (optim.RowSGD, optim.RowAdagrad, optim.RowAdam)):
+            raise ValueError('KvsAllTrainer: %s updates the rows of a sparse row gradient, but the K-vs-all gradient of '
+                             'an entity table is dense (every entity is a candidate of every query); use a torch.optim '
+                             'optimizer' % type(optimizer).__name__)
+        if type(model).k_vs_all_loss is Model.k_vs_all_loss:
+            model.k_vs_all_loss(None, None, None, None)     # raises NotImplementedError, naming the models that have it
+        self.model = model
+        self.kg_train = kg_train
+        self.use_cuda = use_cuda
+        self.n_epochs = n_epochs
+        self.optimizer = optimizer
+        self.batch_size = batch_size
+        self.label_smoothing = label_smoothing
+        self.side = side
+        self.n_triples = len(kg_train)
+        self.sync_free = sync_free
+        self.verbose = verbose
+        self._indexes = None            # {'tail': FilterIndex (h, r) -> tails, 'head': FilterIndex (t, r) -> heads}
+        self._targets = None            # the indexes' answer lists on the GPU
+        self._epoch_losses = []
+        self._epoch_sums = None         # sync_free: (device vector of the epochs' loss sums, batches per epoch)
+
+    @staticmethod
+    def key_batches(index, batch_size):
+        """The batches of one side: ``(ent_idx, r_idx, seg_lo, seg_hi)`` of the distinct keys ``index.keys`` in index
+        order, ``batch_size`` at a time -- pure index arithmetic on the index's own tensors, no lookup kernel."""
+        from ..filter_index import KEY2_SPAN
+        keys, offsets = index.keys, index.offsets
+        for b in range(get_n_batches(index.n_keys, batch_size)):
+            lo, hi = b * batch_size, min((b + 1) * batch_size, index.n_keys)
+            k = keys[lo:hi]
+            yield k // KEY2_SPAN, k % KEY2_SPAN, offsets[lo:hi], offsets[lo + 1:hi + 1]
+
+    def _sides(self):
+        return ('tail', 'head') if self.side == 'both' else (self.side,)
+
+    def n_batches(self):
+        """Steps of one epoch (after the indexes exist)."""
+        return sum(get_n_batches(self._indexes[s].n_keys, self.batch_size) for s in self._sides())
+
+    def _build_indexes(self):
+        from ..filter_index import FilterIndex
+        kg = self.kg_train
+        device = next(self.model.parameters()).device if self.use_cuda == 'all' else torch.device('cpu')
+        h, t, r = kg.head_idx, kg.tail_idx, kg.relations
+        self._indexes = {
+            'tail': FilterIndex.from_triples_torch(h, r, t, device, kg.n_ent, kg.n_rel, kg.n_ent),
+            'head': FilterIndex.from_triples_torch(t, r, h, device, kg.n_ent, kg.n_rel, kg.n_ent)}
+        self._targets = {s: ix.targets.cuda() for s, ix in self._indexes.items()}     # 'batch': the one upload of the labels
+
+    def _batches(self):
+        for side in self._sides():
+            for batch in self.key_batches(self._indexes[side], self.batch_size):
+                if self.use_cuda == 'batch':
+                    batch = tuple(x.cuda() for x in batch)
+                yield side, batch
+
+    def _step(self, side, batch, acc=None):
+        """One training step; the loss as a device scalar, also added to the device float ``acc`` when given."""
+        e, r, seg_lo, seg_hi = batch
+        self.optimizer.zero_grad()
+        loss = self.model.k_vs_all_loss(e, r, (seg_lo, seg_hi, self._targets[side]), side,
+                                        label_smoothing=self.label_smoothing, reduction='mean')
+        if acc is not None:
+            acc.add_(loss.detach())
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()
+
+    def run(self):
+        self.model.cuda()
+        epochs = range(self.n_epochs)
+        bar = None
+        if self.verbose:
+            try:
+                from tqdm.autonotebook import tqdm
+                epochs = bar = tqdm(epochs, unit='epoch')
+            except ImportError:
+                pass
+        if self._indexes is None:       # kept: a later run() builds and uploads nothing again
+            self._build_indexes()
+        n_batches = max(self.n_batches(), 1)
+        self._epoch_losses, self._epoch_sums = [], None
+        if self.sync_free:
+            device = next(self.model.parameters()).device
+            self._epoch_sums = (torch.zeros(self.n_epochs, dtype=torch.float32, device=device), n_batches)
+        for epoch in epochs:
+            if self.sync_free:
+                acc = self._epoch_sums[0][epoch]        # a view: the steps add into the vector's own element
+                for side, batch in self._batches():
+                    self._step(side, batch, acc)
+            else:
+                sum_ = 0
+                for side, batch in self._batches():
+                    sum_ += self._step(side, batch).item()
+                self._epoch_losses.append(sum_ / n_batches)
+                if bar is not None:
+                    bar.set_description('Epoch {} | mean loss: {:.5f}'.format(epoch + 1, self._epoch_losses[-1]))
+            self.model.normalize_parameters()
+
+    @property
+    def epoch_losses(self):
+        """The mean step loss of every epoch of the last ``run()``, as Python floats.  After a ``sync_free`` run the
+        first access reads the epoch sums back (one copy)."""
+        if self._epoch_sums is not None:
+            sums, n_batches = self._epoch_sums
+            self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
+        return self._epoch_losses
