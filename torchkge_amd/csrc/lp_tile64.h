@@ -22,6 +22,9 @@
 //
 // The parameter block P of a criterion carries at least: kge_lp_desc d; int chunks, col_tiles, row_panels;
 // float *ws_da ([chunks][B][K0 + K1]); float *o0, *o1; int64_t ldo0, ldo1 (the gradient group of the launch).
+//
+// The geometry (column slices, wave tiles per slice, staging steps, the chunk partition and the chunk-sum order) is held
+// to tests/tile64_table.py by tests/test_gpu_tile64_matrix.py, through both criteria.
 #ifndef KGE_LP_TILE64_H
 #define KGE_LP_TILE64_H
 
