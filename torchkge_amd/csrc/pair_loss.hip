@@ -5,17 +5,20 @@
 //                                consecutive pairs per turn (one 16-byte quad of each vector where its base allows it),
 //                                writes their gradients and keeps the sum of their terms in fp64; wavefront butterfly,
 //                                LDS across the block's four wavefronts.  G = 1 writes *loss itself.
-// pair_loss_final_kernel         one block: the G partials of the workspace, added the same way, rounded to fp32 once.
+// st_final_kernel                one block: the G partials of the workspace, added the same way, rounded to fp32 once.
+// The tree itself (the turns of a thread, the block sum, the final block), the quad accessors and softplus / sigma are
+// loss_common.h, shared with group_loss.hip.
 // Pure streaming: 8 bytes read and (GRAD) 8 bytes written per pair; at a training batch (n = 32,768: 0.5 MB) the cost is
 // the launches, which is why there are at most two.  -ffp-contract=off: the arithmetic is the source's.
 #include "kge_common.h"
 #include "../../include/kge_hip_train.h"
+#include "loss_common.h"
 
 namespace {
 
-constexpr int PL_THREADS = 256;
-constexpr int PL_CHUNK = KGE_PAIR_LOSS_CHUNK;   // pairs per block and turn
-constexpr int PL_MAX_BLOCKS = 1024;
+constexpr int PL_THREADS = ST_THREADS;          // the tree of loss_common.h: its blocks, turns and grid cap
+constexpr int PL_CHUNK = ST_CHUNK;              // pairs per block and turn
+constexpr int PL_MAX_BLOCKS = ST_MAX_BLOCKS;
 constexpr int64_t PL_MAX_N = 0x7fffffffll;
 constexpr float BCE_CAP = 100.f;
 static_assert(PL_CHUNK == 4 * PL_THREADS, "a thread owns one quad per turn");
@@ -32,42 +35,7 @@ struct PairLoss {
     int vec;            // VEC_* bits: which of the four vectors start on 16 bytes
 };
 
-inline int pl_grid(int64_t n)
-{
-    const int64_t g = (n + PL_CHUNK - 1) / PL_CHUNK;
-    return (int)(g < PL_MAX_BLOCKS ? g : PL_MAX_BLOCKS);
-}
-
-__device__ __forceinline__ void load_quad(const float *__restrict__ x, int64_t j, int64_t n, bool vec, float (&v)[4])
-{
-    if (vec && j + 4 <= n) {
-        const float4 q = *reinterpret_cast<const float4 *>(x + j);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = j + e < n ? x[j + e] : 0.f;
-    }
-}
-
-__device__ __forceinline__ void store_quad(float *__restrict__ x, int64_t j, int64_t n, bool vec, const float (&v)[4])
-{
-    if (vec && j + 4 <= n) {
-        *reinterpret_cast<float4 *>(x + j) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (j + e < n) x[j + e] = v[e];
-    }
-}
-
-// softplus(x) and sigma(x) from one e = exp(-|x|) in (0, 1]: no overflow, no inf / inf
-__device__ __forceinline__ void softplus_sigma(float x, float &sp, float &sg)
-{
-    const float e = expf(-fabsf(x));
-    sp = fmaxf(x, 0.f) + log1pf(e);
-    const float den = 1.f + e;
-    sg = (x >= 0.f ? 1.f : e) / den;
-}
+inline int pl_grid(int64_t n) { return st_grid(n); }
 
 template <int KIND>
 __device__ __forceinline__ float pair_term(float margin, float p, float q, float &gp, float &gq)
@@ -91,58 +59,22 @@ __device__ __forceinline__ float pair_term(float margin, float p, float q, float
     return sp + sq;
 }
 
-// the 256 fp64 values of a block, in the fixed order of the header; the result is valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__device__ __forceinline__ void write_loss(const PairLoss &a, double s)
-{
-    const float l = (float)s;
-    *a.loss = l;
-    if (a.acc_io) *a.acc_io = *a.acc_io + l;
-}
-
 template <int KIND, bool GRAD>
 __global__ __launch_bounds__(PL_THREADS) void pair_loss_kernel(const PairLoss a)
 {
     __shared__ double sh[PL_THREADS / 64];
-    double acc = 0.0;
-    const int64_t step = (int64_t)gridDim.x * PL_CHUNK;
-    for (int64_t j = (int64_t)blockIdx.x * PL_CHUNK + 4 * threadIdx.x; j < a.n; j += step) {
-        float p[4], q[4], gp[4], gq[4], t[4];
+    const double acc = st_thread_sum(a.n, [&](int64_t j, float (&t)[4]) {
+        float p[4], q[4], gp[4], gq[4];
         load_quad(a.pos, j, a.n, a.vec & VEC_POS, p);
         load_quad(a.neg, j, a.n, a.vec & VEC_NEG, q);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float term = pair_term<KIND>(a.margin, p[e], q[e], gp[e], gq[e]);
-            t[e] = j + e < a.n ? term : 0.f;
-        }
-        acc += ((double)t[0] + (double)t[1]) + ((double)t[2] + (double)t[3]);
+        for (int e = 0; e < 4; ++e) t[e] = pair_term<KIND>(a.margin, p[e], q[e], gp[e], gq[e]);
         if (GRAD) {
             store_quad(a.dpos, j, a.n, a.vec & VEC_DPOS, gp);
             store_quad(a.dneg, j, a.n, a.vec & VEC_DNEG, gq);
         }
-    }
-    const double s = block_sum(acc, sh);
-    if (threadIdx.x == 0) {
-        if (gridDim.x == 1) write_loss(a, s);
-        else a.part[blockIdx.x] = s;
-    }
-}
-
-__global__ __launch_bounds__(PL_THREADS) void pair_loss_final_kernel(const PairLoss a, int G)
-{
-    __shared__ double sh[PL_THREADS / 64];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < G; i += PL_THREADS) acc += a.part[i];
-    const double s = block_sum(acc, sh);
-    if (threadIdx.x == 0) write_loss(a, s);
+    });
+    st_finish_block(acc, sh, a.part, a.loss, a.acc_io);
 }
 
 template <int KIND>
@@ -190,7 +122,7 @@ extern "C" int kge_pair_loss(int kind, float margin, const float *pos, const flo
     else launch_stage1<KGE_LOSS_BCE>(a, G, grad, s);
     KGE_CHECK_LAUNCH();
     if (G > 1) {
-        hipLaunchKernelGGL(pair_loss_final_kernel, dim3(1), dim3(PL_THREADS), 0, s, a, G);
+        hipLaunchKernelGGL(st_final_kernel, dim3(1), dim3(ST_THREADS), 0, s, a.part, G, a.loss, a.acc_io);
         KGE_CHECK_LAUNCH();
     }
     return 0;

@@ -2,7 +2,7 @@
 """Negative samplers with the reference's interface (torchkge/sampling.py:16-592):
 ``NegativeSampler``, ``UniformNegativeSampler``, ``BernoulliNegativeSampler``
 (``.bern_probs``, ``.corrupt_batch(heads, tails, relations, n_neg=None)``,
-``.corrupt_kg(batch_size, use_cuda, which, on_device=False)``), ``PositionalNegativeSampler``
+``.corrupt_kg(batch_size, use_cuda, which, on_device=False, n_neg=1)``), ``PositionalNegativeSampler``
 (``.possible_heads / .possible_tails / .n_poss_heads / .n_poss_tails``),
 ``BernoulliRelationNegativeSampler`` (``.bern_probs``, ``.rel_share``; three
 vectors out) and ``get_possible_heads_tails``.
@@ -35,6 +35,13 @@ from .utils.data import DataLoader
 from .utils.operations import get_bernoulli_probs
 
 
+def _check_block(sampler, neg, facts, n_neg):
+    """A corrupt_batch that ignores ``n_neg`` (one negative per fact whatever it is asked) cannot serve corrupt_kg(n_neg > 1)."""
+    if n_neg != 1 and neg.shape[0] != n_neg * facts.shape[0]:
+        raise ValueError('%s.corrupt_batch returned %d negatives for %d facts with n_neg = %d: this sampler draws one '
+                         'negative per fact' % (type(sampler).__name__, neg.shape[0], facts.shape[0], n_neg))
+
+
 class NegativeSampler:
     """Interface (sampling.py:16-138)."""
 
@@ -61,11 +68,15 @@ class NegativeSampler:
         raise NotYetImplementedError('NegativeSampler is just an interface, please consider using '
                                      'a child class where this is implemented.')
 
-    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False):
-        """Corrupt a whole graph batch by batch with n_neg=1 (sampling.py:76-138): the reference's driver, host tensors
+    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False, *, n_neg=1):
+        """Corrupt a whole graph batch by batch with n_neg=1 by default (sampling.py:76-138): the reference's driver, host tensors
         out.  ``on_device=True`` takes the graph's vectors to the GPU once, corrupts slices of them and returns the two
         negative vectors as device tensors: nothing goes through the host (what TrainDataLoader with use_cuda='all' and
-        TripletClassificationEvaluator use)."""
+        TripletClassificationEvaluator use).
+
+        ``n_neg`` (the engine's own, keyword only): negatives per fact.  The output is the batches laid end to end, the
+        block of a batch of B_b facts being its ``n_neg * B_b`` positions in tile order (negative k of the batch's fact i at
+        ``k * B_b + i``, as ``corrupt_batch`` returns them).  1 is the reference's output and random stream."""
         assert which in ['main', 'train', 'test', 'val']
         if which == 'val':
             assert self.n_facts_val > 0
@@ -78,14 +89,16 @@ class NegativeSampler:
             h, t, r = self._device_graph(kg)
             for lo in range(0, h.shape[0], batch_size):
                 sl = slice(lo, lo + batch_size)
-                neg_heads, neg_tails = self.corrupt_batch(h[sl], t[sl], r[sl], n_neg=1)
+                neg_heads, neg_tails = self.corrupt_batch(h[sl], t[sl], r[sl], n_neg=n_neg)
+                _check_block(self, neg_heads, h[sl], n_neg)
                 corr_heads.append(neg_heads)
                 corr_tails.append(neg_tails)
             return cat(corr_heads).long(), cat(corr_tails).long()
         tmp_cuda = 'batch' if use_cuda else None
         dataloader = DataLoader(kg, batch_size=batch_size, use_cuda=tmp_cuda)
         for batch in dataloader:
-            neg_heads, neg_tails = self.corrupt_batch(batch[0], batch[1], batch[2], n_neg=1)
+            neg_heads, neg_tails = self.corrupt_batch(batch[0], batch[1], batch[2], n_neg=n_neg)
+            _check_block(self, neg_heads, batch[0], n_neg)
             corr_heads.append(neg_heads)
             corr_tails.append(neg_tails)
         if use_cuda:
@@ -353,9 +366,10 @@ class BernoulliRelationNegativeSampler(NegativeSampler):
         return _hip_relation.relation_corrupt(heads, tails, relations, mask_ent.to(torch.uint8), mask_head.to(torch.uint8),
                                               draws_r, draws_h, draws_t, n_neg)
 
-    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False):
-        """(neg_heads, neg_tails, neg_rels) of a whole graph, batch by batch with n_neg = 1: host tensors, or with
-        ``on_device=True`` device tensors from vectors that never leave the GPU."""
+    def corrupt_kg(self, batch_size, use_cuda, which='main', on_device=False, *, n_neg=1):
+        """(neg_heads, neg_tails, neg_rels) of a whole graph, batch by batch with n_neg = 1 by default: host tensors, or
+        with ``on_device=True`` device tensors from vectors that never leave the GPU.  ``n_neg``: negatives per fact, every
+        batch's block in tile order (NegativeSampler.corrupt_kg)."""
         assert which in ['main', 'train', 'test', 'val']
         if which == 'val':
             assert self.n_facts_val > 0
@@ -370,7 +384,7 @@ class BernoulliRelationNegativeSampler(NegativeSampler):
         else:
             batches = DataLoader(kg, batch_size=batch_size, use_cuda='batch' if use_cuda else None)
         for batch in batches:
-            for lst, neg in zip(out, self.corrupt_batch(batch[0], batch[1], batch[2], n_neg=1)):
+            for lst, neg in zip(out, self.corrupt_batch(batch[0], batch[1], batch[2], n_neg=n_neg)):
                 lst.append(neg)
         empty = torch.zeros(0, dtype=torch.int64)
         out = tuple(cat(lst).long() if lst else empty for lst in out)

@@ -14,6 +14,9 @@ What is the engine's own:
   * ``sync_free=True``: ``run()`` reads nothing back -- the sampler draws without its host read, the steps add their loss
     into one device float per epoch, ``epoch_losses`` fetches the epoch sums on first access;
   * ``sampler=``: any object with a ``corrupt_kg`` instead of the two built-in samplers;
+  * ``n_neg=K``: K negatives per fact -- the loader hands every batch its ``K * B_b`` negatives in tile order and
+    ``Model.forward`` repeats the positives; a criterion of ``utils/group_losses.py`` (self-adversarial, sampled softmax)
+    weighs the K negatives of a fact against each other in one kge_group_loss, any pairwise criterion sees K pairs per fact;
   * ``get_counter_examples()`` is None before ``run()`` and the last epoch's negatives after it (the reference's
     ``run`` asks its loader for them before the first iteration and raises).
 
@@ -34,6 +37,7 @@ from ..rowgrad import row_gradients
 from ..sampling import BernoulliNegativeSampler, UniformNegativeSampler
 from .data import get_n_batches
 from .fused_losses import fused_for
+from .group_losses import _GroupCriterion
 
 
 class TrainDataLoader:
@@ -43,12 +47,19 @@ class TrainDataLoader:
     ``use_cuda``: None (host tensors), 'batch' (each batch is moved when it is returned) or 'all' (the graph's vectors
     move once, the negatives are drawn on the device and the batches are slices: nothing goes through the host).
     ``sampler``: an object with ``corrupt_kg(batch_size, use_cuda, on_device=...)``; ``sampling_type`` ('unif' / 'bern')
-    is then ignored.  ``sync_free=True`` sets the sampler's ``sync_free`` flag."""
+    is then ignored.  ``sync_free=True`` sets the sampler's ``sync_free`` flag.
 
-    def __init__(self, kg, batch_size, sampling_type, use_cuda=None, *, sampler=None, sync_free=False):
+    ``n_neg``: negatives per fact.  Above 1 the sampler's ``corrupt_kg`` is asked for ``n_neg=`` (a sampler with the old
+    signature serves ``n_neg=1`` only) and batch b of B_b facts gets the ``n_neg * B_b`` negatives of its own block, in
+    the tile order ``Model.forward`` expects: ``nh[k * B_b + i]`` is the k-th negative of the batch's fact i."""
+
+    def __init__(self, kg, batch_size, sampling_type, use_cuda=None, *, sampler=None, sync_free=False, n_neg=1):
         self.h, self.t, self.r = kg.head_idx, kg.tail_idx, kg.relations
         self.use_cuda = use_cuda
         self.b_size = batch_size
+        if int(n_neg) < 1:
+            raise ValueError('n_neg must be at least 1, got %r' % (n_neg,))
+        self.n_neg = int(n_neg)
         self.iterator = None
         if sampler is not None:
             self.sampler = sampler
@@ -72,19 +83,26 @@ class TrainDataLoader:
         return self.iterator
 
     def get_counter_examples(self):
-        """``SmallKG(nh, nt, r)`` of the latest ``__iter__``; None before the first."""
+        """``SmallKG(nh, nt, r)`` of the latest ``__iter__``; None before the first.  With ``n_neg > 1`` the relations are
+        tiled batch by batch to match the negatives' blocks."""
         if self.iterator is None:
             return None
-        return SmallKG(self.iterator.nh, self.iterator.nt, self.iterator.r)
+        it = self.iterator
+        r = it.r
+        if self.n_neg > 1:
+            r = torch.cat([r[lo:lo + self.b_size].repeat(self.n_neg) for lo in range(0, len(r), self.b_size)])
+        return SmallKG(it.nh, it.nt, r)
 
 
 class TrainDataLoaderIter:
     def __init__(self, loader):
         self.h, self.t, self.r = loader.h, loader.t, loader.r
+        self.n_neg = loader.n_neg
+        more = {'n_neg': self.n_neg} if self.n_neg > 1 else {}      # (a sampler with the old signature serves n_neg = 1)
         if loader.use_cuda == 'all':
-            self.nh, self.nt = loader.sampler.corrupt_kg(loader.b_size, True, on_device=True)
+            self.nh, self.nt = loader.sampler.corrupt_kg(loader.b_size, True, on_device=True, **more)
         else:
-            self.nh, self.nt = loader.sampler.corrupt_kg(loader.b_size, loader.tmp_cuda)
+            self.nh, self.nt = loader.sampler.corrupt_kg(loader.b_size, loader.tmp_cuda, **more)
         if loader.use_cuda:
             self.nh, self.nt = self.nh.cuda(), self.nt.cuda()
         self.use_cuda = loader.use_cuda
@@ -97,7 +115,11 @@ class TrainDataLoaderIter:
             raise StopIteration
         sl = slice(self.current_batch * self.b_size, (self.current_batch + 1) * self.b_size)
         self.current_batch += 1
-        batch = {'h': self.h[sl], 't': self.t[sl], 'r': self.r[sl], 'nh': self.nh[sl], 'nt': self.nt[sl]}
+        if self.n_neg > 1:      # the batch's own block of n_neg * B_b negatives (the last batch is short)
+            nsl = slice(self.n_neg * sl.start, self.n_neg * min(sl.stop, len(self.h)))
+        else:
+            nsl = sl
+        batch = {'h': self.h[sl], 't': self.t[sl], 'r': self.r[sl], 'nh': self.nh[nsl], 'nt': self.nt[nsl]}
         if self.use_cuda == 'batch':
             batch = {k: v.cuda() for k, v in batch.items()}
         return batch
@@ -111,7 +133,7 @@ class Trainer:
     ``model.normalize_parameters()``; the mean loss of every epoch is kept in ``epoch_losses``."""
 
     def __init__(self, model, criterion, kg_train, n_epochs, batch_size, optimizer, sampling_type='bern', use_cuda=None,
-                 *, fused=True, sync_free=False, sampler=None, verbose=True):
+                 *, fused=True, sync_free=False, sampler=None, verbose=True, n_neg=1):
         if use_cuda not in ('all', 'batch'):
             raise ValueError("Trainer: use_cuda must be 'all' or 'batch', got %r -- the engine's models live on the GPU, "
                              "there is no CPU training path" % (use_cuda,))
@@ -129,6 +151,16 @@ class Trainer:
         self.sampler = sampler
         self.verbose = verbose
         self.counter_examples = None
+        if int(n_neg) < 1:
+            raise ValueError('Trainer: n_neg must be at least 1, got %r' % (n_neg,))
+        self.n_neg = int(n_neg)
+        self._grouped = isinstance(criterion, _GroupCriterion)
+        if self._grouped:
+            if criterion.n_neg is None:
+                criterion.n_neg = self.n_neg
+            elif criterion.n_neg != self.n_neg:
+                raise ValueError('Trainer: the criterion groups %d negatives per fact, the Trainer draws %d'
+                                 % (criterion.n_neg, self.n_neg))
         self._fused_criterion = fused_for(criterion) if fused else None
         self._row_mode = isinstance(optimizer, (optim.RowSGD, optim.RowAdagrad, optim.RowAdam))
         self._loader = None
@@ -142,6 +174,8 @@ class Trainer:
             p, n = self.model(batch['h'], batch['t'], batch['r'], batch['nh'], batch['nt'])
             if self._fused_criterion is not None:
                 loss = self._fused_criterion(p, n, acc)
+            elif self._grouped:
+                loss = self.criterion(p, n, acc)
             else:
                 loss = self.criterion(p, n)
                 if acc is not None:
@@ -168,7 +202,8 @@ class Trainer:
                 pass
         if self._loader is None:        # kept: a later run() uploads nothing again
             self._loader = TrainDataLoader(self.kg_train, batch_size=self.batch_size, sampling_type=self.sampling_type,
-                                           use_cuda=self.use_cuda, sampler=self.sampler, sync_free=self.sync_free)
+                                           use_cuda=self.use_cuda, sampler=self.sampler, sync_free=self.sync_free,
+                                           n_neg=self.n_neg)
         data_loader = self._loader
         self._epoch_losses, self._epoch_sums = [], None
         if self.sync_free:
