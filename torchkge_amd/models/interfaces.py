@@ -532,6 +532,10 @@ class Model(Module):
     def _hip_kind(self):
         return self._kind
 
+    def _triple_kind(self):
+        """The kind ``scoring_function`` scores triples with (TorusE: its own, not the kind of its query rows)."""
+        return self._hip_kind()
+
     # ---- reference API ----------------------------------------------------
     def forward(self, heads, tails, relations, negative_heads, negative_tails,
                 negative_relations=None):
@@ -549,6 +553,49 @@ class Model(Module):
         scores = self.scoring_function(torch.cat([heads, negative_heads]), torch.cat([tails, negative_tails]),
                                        torch.cat([relations, negative_relations]))
         pos, neg = scores[:b], scores[b:]
+        if n_neg > 1:
+            pos = pos.repeat(n_neg)
+        return pos, neg
+
+    def forward_grouped(self, heads, tails, relations, negative_heads, negative_tails, negative_relations=None, *,
+                        check=True):
+        """``forward`` for K negatives per fact in tile order (``negative_heads[k * B + i]`` is the k-th negative of fact
+        i), through the grouped scorer (include/kge_hip_factgroup.h): a fact's rows are gathered and normalised once,
+        each negative loads only the replaced entity's row(s), and the backward emits one gradient row per fact row and
+        one per replaced row -- K + 3 per fact for TransE against the 3 (K + 1) of ``forward``.  Returns ``(pos, neg)``
+        with the shapes and the BITS of ``forward``: every criterion takes them unchanged.
+
+        The contract: a negative differs from its fact in at most one of head and tail, which every sampler of the
+        package guarantees.  ``check=True`` verifies it with one host read and raises ValueError; ``check=False`` reads
+        nothing back, and a negative that breaks the contract is then scored as (negative head, relation, the fact's
+        tail).
+
+        The gradients are dense tables summed through the ordered or the atomic row reduction (default and deterministic
+        mode) or, inside ``row_gradients()``, uncoalesced sparse gradients with B (K + 2) rows per entity table.
+
+        Falls back to ``forward``, with the same values: a model kind the grouped kernels do not serve (RESCAL, HolE,
+        TransR, ANALOGY, ConvKB, a model without an engine kind), rows wider than 512 floats, and
+        ``negative_relations`` given.  A row-sharded model raises, as ``scoring_function`` does."""
+        from .. import _hip_factgroup
+        self._check_unsharded('forward_grouped')
+        b = heads.shape[0]
+        kind = self._triple_kind()
+        if negative_relations is not None or kind not in _hip_factgroup.KINDS or b == 0 or \
+                negative_heads.shape[0] % b != 0 or negative_heads.shape[0] != negative_tails.shape[0]:
+            return self.forward(heads, tails, relations, negative_heads, negative_tails, negative_relations)
+        n_neg = negative_heads.shape[0] // b
+        tables = self._tables()
+        _hip.require_cuda(heads, tails, relations, negative_heads, negative_tails, *tables)
+        if check:
+            both = (negative_heads != heads.repeat(n_neg)) & (negative_tails != tails.repeat(n_neg))
+            if bool(both.any()):
+                raise ValueError('torchkge_amd: forward_grouped needs negatives that differ from their fact in at most one '
+                                 'of head and tail; %d of %d differ in both' % (int(both.sum()), both.shape[0]))
+        try:
+            pos, neg = _hip_factgroup.ScoreFactGroups.apply(kind, self._d_ent, self._d_rel, heads, tails, relations,
+                                                            negative_heads, negative_tails, *tables)
+        except _hip_factgroup.Unsupported:
+            return self.forward(heads, tails, relations, negative_heads, negative_tails)
         if n_neg > 1:
             pos = pos.repeat(n_neg)
         return pos, neg

@@ -207,6 +207,14 @@ class TorusEModel(TranslationModel):
         return _ScoreTriples.apply(self._SCORE_KIND[self.dissimilarity_type], self.emb_dim, self.emb_dim, h_idx, t_idx,
                                    r_idx, *tables)
 
+    def _triple_kind(self):
+        return self._SCORE_KIND[self.dissimilarity_type]
+
+    def forward_grouped(self, *args, **kwargs):
+        """``Model.forward_grouped``; as ``scoring_function`` it marks the tables as no longer normalised."""
+        object.__setattr__(self, 'normalized', False)
+        return super().forward_grouped(*args, **kwargs)
+
     def normalize_parameters(self):
         """Project the embeddings on the torus: frac_ of both tables in place (translation.py:723-728, kge_frac_rows)."""
         for emb in (self.ent_emb, self.rel_emb):

@@ -17,6 +17,9 @@ What is the engine's own:
   * ``n_neg=K``: K negatives per fact -- the loader hands every batch its ``K * B_b`` negatives in tile order and
     ``Model.forward`` repeats the positives; a criterion of ``utils/group_losses.py`` (self-adversarial, sampled softmax)
     weighs the K negatives of a fact against each other in one kge_group_loss, any pairwise criterion sees K pairs per fact;
+  * ``trainer.grouped_forward = True`` (an attribute, off by default): the scores come from
+    ``Model.forward_grouped`` -- a fact's rows gathered once for its K negatives, K + 3 instead of 3 (K + 1) gradient rows
+    per fact for TransE -- with the bits of ``Model.forward``;
   * ``get_counter_examples()`` is None before ``run()`` and the last epoch's negatives after it (the reference's
     ``run`` asks its loader for them before the first iteration and raises).
 
@@ -130,7 +133,18 @@ class TrainDataLoaderIter:
 
 class Trainer:
     """The reference's training procedure: per epoch a fresh corruption of ``kg_train``, one step per batch,
-    ``model.normalize_parameters()``; the mean loss of every epoch is kept in ``epoch_losses``."""
+    ``model.normalize_parameters()``; the mean loss of every epoch is kept in ``epoch_losses``.
+
+    ``grouped_forward`` is an attribute, False by default (the constructor's parameters are those of the release before
+    it): set ``trainer.grouped_forward = True`` before ``run()`` and every batch is scored with
+    ``model.forward_grouped`` instead of ``model.forward`` -- the same score bits, fewer gathered and emitted rows (models
+    and widths the grouped kernels do not serve take ``forward`` inside it).  That path needs negatives that differ from
+    their fact in at most one of head and tail.  The package's own samplers guarantee it and are not checked.  A
+    ``sampler=`` from elsewhere is checked on every step, one host read each -- unless ``sync_free``, which reads nothing
+    back: THEN THE CONTRACT IS THE CALLER'S, and a negative that breaks it is scored as (negative head, relation, the
+    fact's tail)."""
+
+    grouped_forward = False     # True: Model.forward_grouped scores the batches (set it on the instance)
 
     def __init__(self, model, criterion, kg_train, n_epochs, batch_size, optimizer, sampling_type='bern', use_cuda=None,
                  *, fused=True, sync_free=False, sampler=None, verbose=True, n_neg=1):
@@ -154,6 +168,8 @@ class Trainer:
         if int(n_neg) < 1:
             raise ValueError('Trainer: n_neg must be at least 1, got %r' % (n_neg,))
         self.n_neg = int(n_neg)
+        own_sampler = sampler is None or type(sampler).__module__ == BernoulliNegativeSampler.__module__
+        self._check_negatives = not own_sampler and not sync_free      # grouped_forward: one host read per step
         self._grouped = isinstance(criterion, _GroupCriterion)
         if self._grouped:
             if criterion.n_neg is None:
@@ -171,7 +187,11 @@ class Trainer:
         """One training step; the loss as a device scalar, also added to the device float ``acc`` when given."""
         with row_gradients() if self._row_mode else contextlib.nullcontext():
             self.optimizer.zero_grad()
-            p, n = self.model(batch['h'], batch['t'], batch['r'], batch['nh'], batch['nt'])
+            if self.grouped_forward:
+                p, n = self.model.forward_grouped(batch['h'], batch['t'], batch['r'], batch['nh'], batch['nt'],
+                                                  check=self._check_negatives)
+            else:
+                p, n = self.model(batch['h'], batch['t'], batch['r'], batch['nh'], batch['nt'])
             if self._fused_criterion is not None:
                 loss = self._fused_criterion(p, n, acc)
             elif self._grouped:
