@@ -102,15 +102,26 @@ def test_library_exports_every_symbol_the_header_declares():
 
 
 def test_one_score_tile_behind_both_criteria():
-    """score_tile() and the gradient walk are defined once, in lp_tile64.h; both criteria include it."""
+    """score_tile(), the two walks, the chunk arithmetic and the host half of the entries are defined once, in
+    lp_tile64.h; both criteria include it, and neither includes the other's header."""
     from torchkge_amd.csrc import build as hb
     src = {n: open(os.path.join(hb.HERE, n)).read() for n in ('lp_tile64.h', 'lp_xent.hip', 'lp_bce.hip')}
     for fn in ('score_tile', 'grad_walk', 'sum_chunks'):
         assert len(re.findall(r'void %s\(' % fn, src['lp_tile64.h'])) == 1
         for n in ('lp_xent.hip', 'lp_bce.hip'):
             assert not re.search(r'void %s\(' % fn, src[n]), (fn, n)
+    for fn in ('void stats_walk', 'void chunk_tiles', 'int chunk_count', 'int setup', 'int launch_fwd', 'int launch_bwd'):
+        assert len(re.findall(r'\b%s\(' % fn, src['lp_tile64.h'])) == 1, fn
+        for n in ('lp_xent.hip', 'lp_bce.hip'):
+            assert not re.search(r'\b%s\(' % fn, src[n]), (fn, n)
     for n in ('lp_xent.hip', 'lp_bce.hip'):
-        assert '#include "lp_tile64.h"' in src[n] and 'mfma' not in re.sub(r'//[^\n]*', '', src[n]).lower()
+        code = re.sub(r'//[^\n]*', '', src[n])
+        assert '#include "lp_tile64.h"' in src[n] and 'mfma' not in code.lower()
+        # the chunk partition is written in the skeleton alone, and the skeleton's users all go through chunk_tiles()
+        assert not re.search(r'col_tiles\s*\*', code) and 'hipLaunchKernelGGL' not in code, n
+    assert len(re.findall(r'col_tiles\s*\*', re.sub(r'//[^\n]*', '', src['lp_tile64.h']))) == 2      # t0 and t1, once
+    assert 'kge_hip_xent.h' not in src['lp_bce.hip'] and 'kge_hip_bce.h' not in src['lp_xent.hip']
+    assert 'kge_hip_xent.h' not in src['lp_tile64.h'] and 'kge_hip_bce.h' not in src['lp_tile64.h']
 
 
 def test_ctypes_signatures_match_the_header_prototypes():

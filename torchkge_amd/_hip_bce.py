@@ -11,49 +11,31 @@ import ctypes
 
 import torch
 
-from . import _hip
-from ._hip import _vp, _i64, _int, _check, _on, _stream, _p
+from . import _hip, _hip_tile64
+from ._hip import _vp, _i64, _check, _on, _stream, _p
+from ._hip_tile64 import _size, _f32, BM, BN, MIN_TILES_PER_CHUNK, MAX_CHUNKS, MAX_K, KSLICE     # noqa: F401 (KGE_BCE_*)
 
-_size = ctypes.c_size_t
-_f32 = ctypes.c_float
 _SIGNATURES = {
     'kge_lp_bce_fwd': [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _size, _vp],
     'kge_lp_bce_bwd': [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _size, _vp],
 }
 _WS_SIZES = ('kge_lp_bce_ws_bytes',)        # size_t f(int64_t B, int64_t N, int K0, int K1)
 _WS_BYTES = {}      # (B, N, K0, K1) -> workspace bytes
-# the constants of the header
-BM, BN = 64, 64                 # KGE_BCE_BM, KGE_BCE_BN: queries per row panel, candidates per tile
-MIN_TILES_PER_CHUNK = 4         # KGE_BCE_MIN_TILES_PER_CHUNK
-MAX_CHUNKS = 32                 # KGE_BCE_MAX_CHUNKS
-MAX_K = 1024                    # KGE_BCE_MAX_K
-KSLICE = 512                    # KGE_BCE_KSLICE
 
 
 def load_library():
     """The handle of _hip.load_library() with the argtypes of this header bound."""
-    lib = _hip.bind(_SIGNATURES, _WS_SIZES, (_i64, _i64, _int, _int), _size)
-    lib.kge_lp_bce_chunks.argtypes, lib.kge_lp_bce_chunks.restype = [_i64], _int
-    return lib
+    return _hip_tile64.load_library(_SIGNATURES, _WS_SIZES, 'kge_lp_bce_chunks')
 
 
 def ws_bytes(B, N, K0, K1=0):
     """kge_lp_bce_ws_bytes: host arithmetic, cached per shape."""
-    key = (B, N, K0, K1)
-    nb = _WS_BYTES.get(key)
-    if nb is None:
-        nb = _WS_BYTES[key] = int(load_library().kge_lp_bce_ws_bytes(B, N, K0, K1))
-    return nb
+    return _hip_tile64.ws_bytes(_WS_BYTES, load_library, 'kge_lp_bce_ws_bytes', B, N, K0, K1)
 
 
 def chunks(N):
     """kge_lp_bce_chunks: candidate chunks of an N-candidate problem (a function of N alone, capped at MAX_CHUNKS)."""
     return int(load_library().kge_lp_bce_chunks(N))
-
-
-def _workspace(prob):
-    d = prob.desc
-    return torch.empty(max(ws_bytes(int(d.B), int(d.N), int(d.K0), int(d.K1)), 16), dtype=torch.uint8, device=prob.device)
 
 
 def _labels(prob, labels):
@@ -83,7 +65,7 @@ def bce_fwd(prob, labels, label_smoothing=0.0):
     lib = load_library()
     seg_lo, seg_hi, targets = _labels(prob, labels)
     row_loss = torch.empty(prob.B, dtype=torch.float32, device=prob.device)
-    ws = _workspace(prob)
+    ws = _hip_tile64.workspace(prob, ws_bytes)
     with _on(prob.device):
         _check(lib.kge_lp_bce_fwd(ctypes.byref(prob.desc), _p(seg_lo), _p(seg_hi), _p(targets), label_smoothing,
                                   _p(row_loss), _p(ws), ws.numel(), _stream()), 'kge_lp_bce_fwd')
@@ -95,25 +77,11 @@ def bce_bwd(prob, labels, label_smoothing, g, want_queries=True, want_tables=Tru
     a group that is not wanted: its kernels are not launched.  ``g``: the float32 weight of every row's loss."""
     lib = load_library()
     seg_lo, seg_hi, targets = _labels(prob, labels)
-    d, dev = prob.desc, prob.device
-    segs = [int(d.K0)] + ([int(d.K1)] if d.K1 else [])
-    dA = [torch.empty(prob.B, k, dtype=torch.float32, device=dev) for k in segs] if want_queries else None
-    dT = [torch.empty(prob.N, k, dtype=torch.float32, device=dev) for k in segs] if want_tables else None
-    if not (want_queries or want_tables) or prob.B == 0:
-        for grp in (dA, dT):
-            for x in grp or ():
-                x.zero_()
-        return dA, dT
-    ws = _workspace(prob)
-
-    def args(grp):
-        out = []
-        for j in range(2):
-            x = grp[j] if grp is not None and j < len(grp) else None
-            out += [_p(x), 0 if x is None else x.stride(0)]
-        return out
-
-    with _on(dev):
-        _check(lib.kge_lp_bce_bwd(ctypes.byref(d), _p(seg_lo), _p(seg_hi), _p(targets), label_smoothing, _p(_hip.f32c(g)),
-                                  *(args(dA) + args(dT) + [_p(ws), ws.numel(), _stream()])), 'kge_lp_bce_bwd')
+    dA, dT, launch = _hip_tile64.grad_groups(prob, want_queries, want_tables)
+    if launch:
+        ws = _hip_tile64.workspace(prob, ws_bytes)
+        with _on(prob.device):
+            _check(lib.kge_lp_bce_bwd(ctypes.byref(prob.desc), _p(seg_lo), _p(seg_hi), _p(targets), label_smoothing,
+                                      _p(_hip.f32c(g)), *(_hip_tile64.group_args(dA, dT) + [_p(ws), ws.numel(), _stream()])),
+                   'kge_lp_bce_bwd')
     return dA, dT

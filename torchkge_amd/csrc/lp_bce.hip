@@ -2,31 +2,32 @@
 // over all N candidates against a CSR of true candidates, and its gradients, without the (B, N) score, label or gradient
 // matrix (gfx950).
 //
-// The skeleton is lp_tile64.h's, shared with lp_xent.hip: the bit-defined 64 x 64 score tile, the gradient walk and the
-// chunk sum of dA.  What is this criterion's own:
+// The skeleton is lp_tile64.h's, shared with lp_xent.hip: the bit-defined 64 x 64 score tile, the chunk arithmetic, the
+// statistics walk, the gradient walk, the chunk sum of dA, the entries' shared checks and the two launch sequences; the
+// kernels here are one-line bodies around it.  What is this criterion's own:
 //  * LabelCursor: a row's position in its sorted label segment.  Where a block walks candidate tiles in ascending order
 //    (the stats sweep, dA) it is set by ONE lower_bound at the block's first tile and then only advances; in dT, where a
 //    block owns one tile and walks the row panels, every (row, tile) takes one binary search.  The next label is kept in
 //    a register, so a tile without labels of the row costs no load, and a hub segment costs O(log len + labels in the
 //    tile), never O(len).  Both run BEFORE score_tile(), so the loads retire under its staging and MFMAs;
-//  * bce_stats_kernel: block = (row panel, candidate chunk); the S tile goes through LDS to a row-wise pass (4 threads
-//    per row, 16 candidates each; each keeps the row's cursor and its 64-bit membership mask of the tile in registers)
-//    that adds softplus(s), s over the labels and s over all candidates in fp64; one partial per (row, chunk);
+//  * BceStat (stats_walk's functor): each of a row's four threads keeps the row's cursor and its 64-bit membership mask
+//    of the tile in registers and adds softplus(s), s over the labels and s over all candidates of its 16 in fp64; the
+//    four meet in LDS in one partial per (row, chunk);
 //  * bce_finish_kernel: adds the chunks in ascending order, combines in fp64, rounds once;
 //  * BceCrit: G(i, c) = g_i (sigma(s) - y(i, c)); one thread per row writes the tile's 64-bit membership mask to LDS
-//    (64 x 8 bytes), the MFMA-layout epilogue reads it.
+//    (64 x 8 bytes), the MFMA-layout epilogue reads it;
+//  * the parameter block, the workspace layout and the four extern "C" entries.
 // No read-modify-write on global memory anywhere: every output element and every partial has one writer.
 #include "kge_common.h"
 #include "../../include/kge_hip_bce.h"
-#include "../../include/kge_hip_xent.h"
 #include "lp_tile64.h"
 
 namespace {
 
 using namespace tile64;
-static_assert(BM == KGE_BCE_BM && BN == KGE_BCE_BN && KSLICE == KGE_BCE_KSLICE, "the geometry the header publishes");
-static_assert(KGE_BCE_MIN_TILES_PER_CHUNK == KGE_XENT_MIN_TILES_PER_CHUNK && KGE_BCE_MAX_CHUNKS == KGE_XENT_MAX_CHUNKS &&
-              KGE_BCE_MAX_K == KGE_XENT_MAX_K, "kge_lp_bce_chunks is kge_lp_xent_chunks");
+static_assert(BM == KGE_BCE_BM && BN == KGE_BCE_BN && KSLICE == KGE_BCE_KSLICE &&
+              MIN_TILES_PER_CHUNK == KGE_BCE_MIN_TILES_PER_CHUNK && MAX_CHUNKS == KGE_BCE_MAX_CHUNKS &&
+              MAX_K == KGE_BCE_MAX_K, "the geometry the header publishes");
 
 typedef unsigned long long u64;
 
@@ -84,57 +85,39 @@ __device__ __forceinline__ float sigmoid_f(float s)
     return (s >= 0.f ? 1.f : e) / (1.f + e);
 }
 
-template <bool VEC4>
-__global__ __launch_bounds__(NTHREADS) void bce_stats_kernel(const BceParams p)
-{
-    __shared__ __attribute__((aligned(16))) float As[BM * LDS_LD];
-    __shared__ __attribute__((aligned(16))) float Bs[BN * LDS_LD];
-    __shared__ float Ss[BM * G_LD];
-    __shared__ double sum_s[3][BM * 4];
-    const kge_lp_desc &d = p.d;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wr = wid >> 1, wc = wid & 1, l31 = lane & 31, half = lane >> 5;
-    const int chunk = blockIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.y * BM;
-    const int t0 = (int)((int64_t)p.col_tiles * chunk / p.chunks), t1 = (int)((int64_t)p.col_tiles * (chunk + 1) / p.chunks);
-
-    const int prow = tid >> 2, pq = tid & 3;      // row-wise pass: candidates 16 pq .. 16 pq + 15 of row prow
-    const int64_t row = row0 + prow;
+// the multi-label statistics of stats_walk(): three fp64 sums per thread, the row's cursor and the tile's mask
+struct BceStat {
+    const BceParams &p;
+    double (*sum_s)[BM * 4];
     LabelCursor lc;     // (the four threads of a row walk the same cursor: the same addresses in one wave)
-    lc.start(p.labels, row < d.B ? p.seg_lo[row] : 0, row < d.B ? p.seg_hi[row] : 0, (int64_t)t0 * BN);
-    double sp = 0.0, spos = 0.0, sall = 0.0;
-
-    for (int t = t0; t < t1; ++t) {
-        const int64_t col0 = (int64_t)t * BN;
-        const u64 mask = lc.take(p.labels, col0);   // issued before the tile: retires under its loads and MFMAs
-        f32x16 acc;
-        score_tile<VEC4>(d, row0, col0, As, Bs, acc);
+    u64 mask;
+    double sp, spos, sall;
+    __device__ __forceinline__ void start(int64_t row, bool ok, int64_t col0)
+    {
+        lc.start(p.labels, ok ? p.seg_lo[row] : 0, ok ? p.seg_hi[row] : 0, col0);
+        sp = 0.0; spos = 0.0; sall = 0.0;
+    }
+    // issued before the tile: retires under its loads and MFMAs
+    __device__ __forceinline__ void tile(int64_t col0) { mask = lc.take(p.labels, col0); }
+    __device__ __forceinline__ void add(const float *s, int64_t, int64_t, int c_lo, int cnt)
+    {
+        const unsigned mine = (unsigned)(mask >> c_lo) & 0xffffu;
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-            Ss[(wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * G_LD + wc * 32 + l31] = acc[r];
-        __syncthreads();
-        const int nvalid = (int)min((int64_t)BN, d.N - col0), c_lo = pq * 16;
-        if (c_lo < nvalid) {    // candidates >= N never enter
-            const int cnt = min(16, nvalid - c_lo);
-            const unsigned mine = (unsigned)(mask >> c_lo) & 0xffffu;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float v = Ss[prow * G_LD + c_lo + e];
-                if (e < cnt) {
-                    // the two terms of softplus enter the fp64 sum one by one: rounded together to fp32, log1pf(.) would
-                    // lose its low bits beside a large s -- which the label sum then cancels
-                    sp += (double)fmaxf(v, 0.f);
-                    sp += (double)log1pf(expf(-fabsf(v)));
-                    sall += (double)v;
-                    if ((mine >> e) & 1u) spos += (double)v;
-                }
+        for (int e = 0; e < 16; ++e) {
+            const float v = s[c_lo + e];
+            if (e < cnt) {
+                // the two terms of softplus enter the fp64 sum one by one: rounded together to fp32, log1pf(.) would
+                // lose its low bits beside a large s -- which the label sum then cancels
+                sp += (double)fmaxf(v, 0.f);
+                sp += (double)log1pf(expf(-fabsf(v)));
+                sall += (double)v;
+                if ((mine >> e) & 1u) spos += (double)v;
             }
         }
-        // (the next score_tile synchronises before anything overwrites Ss)
     }
-    sum_s[0][tid] = sp; sum_s[1][tid] = spos; sum_s[2][tid] = sall;
-    __syncthreads();
-    if (pq == 0 && row < d.B) {
+    __device__ __forceinline__ void publish(int tid) { sum_s[0][tid] = sp; sum_s[1][tid] = spos; sum_s[2][tid] = sall; }
+    __device__ __forceinline__ void write(int64_t row, int chunk, int tid) const
+    {
         double r[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) r[k] = ((sum_s[k][tid] + sum_s[k][tid + 1]) + sum_s[k][tid + 2]) + sum_s[k][tid + 3];
@@ -142,6 +125,17 @@ __global__ __launch_bounds__(NTHREADS) void bce_stats_kernel(const BceParams p)
         p.ws_spos[row * p.chunks + chunk] = r[1];
         p.ws_sall[row * p.chunks + chunk] = r[2];
     }
+};
+
+template <bool VEC4>
+__global__ __launch_bounds__(NTHREADS) void bce_stats_kernel(const BceParams p)
+{
+    __shared__ __attribute__((aligned(16))) float As[BM * LDS_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[BN * LDS_LD];
+    __shared__ float Ss[BM * G_LD];
+    __shared__ double sum_s[3][BM * 4];
+    BceStat stat = {p, sum_s};
+    stats_walk<VEC4>(p, stat, As, Bs, Ss);
 }
 
 __global__ __launch_bounds__(BM) void bce_finish_kernel(const BceParams p)
@@ -201,50 +195,36 @@ __global__ __launch_bounds__(NTHREADS) void bce_grad_kernel(const BceParams p)
 
 __global__ __launch_bounds__(256) void bce_sum_chunks_kernel(const BceParams p) { sum_chunks(p); }
 
-// shared validation of both entries; fills the geometry and the workspace pointers
+// validation of both entries (tile64::setup) and what is this criterion's own of the parameter block
 int bce_setup(const kge_lp_desc *d, const int64_t *seg_lo, const int64_t *seg_hi, const int32_t *labels, float eps, void *ws,
-              size_t ws_bytes, BceParams &p, bool &vec4)
+              size_t ws_bytes, BceParams &p)
 {
-    if (!d) return KGE_EINVAL;
-    if (d->mode != KGE_LP_DOT || d->c_base != 0) return KGE_EUNSUPPORTED;
-    if (int e = kge_lp_desc_check(d)) return e;
-    if ((int64_t)d->K0 + d->K1 > KGE_BCE_MAX_K) return KGE_EUNSUPPORTED;
-    if (d->B >= ((int64_t)1 << 31) || d->N >= ((int64_t)1 << 31) || d->B > (int64_t)65535 * BM) return KGE_EUNSUPPORTED;
-    if (!(eps >= 0.f && eps <= 1.f)) return KGE_EINVAL;
+    if (int e = setup(d, seg_lo && seg_hi && labels, eps, ws, ws_bytes, kge_lp_bce_ws_bytes, p)) return e;
     if (d->B == 0) return 0;
-    if (d->N <= 0 || !seg_lo || !seg_hi || !labels) return KGE_EINVAL;
-    if (d->lda0 < d->K0 && d->B > 1) return KGE_EINVAL;
-    const size_t need = kge_lp_bce_ws_bytes(d->B, d->N, d->K0, d->K1);
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15) || need == 0 || ws_bytes < need) return KGE_EINVAL;
-    p.d = *d;
     p.seg_lo = seg_lo;
     p.seg_hi = seg_hi;
     p.labels = labels;
     p.eps = eps;
     p.y_neg = eps / (float)d->N;
     p.y_pos = (1.0f - eps) + p.y_neg;
-    p.chunks = kge_lp_bce_chunks(d->N);
-    p.col_tiles = (int)((d->N + BN - 1) / BN);
-    p.row_panels = (int)((d->B + BM - 1) / BM);
     const size_t part = (size_t)8 * d->B * p.chunks;
     char *w = static_cast<char *>(ws);
     p.ws_sp = reinterpret_cast<double *>(w);
     p.ws_spos = reinterpret_cast<double *>(w + part);
     p.ws_sall = reinterpret_cast<double *>(w + 2 * part);
     p.ws_da = reinterpret_cast<float *>(w + 3 * part);
-    vec4 = operands_vec4(d);
     return 0;
 }
 
 } // namespace
 
-extern "C" int kge_lp_bce_chunks(int64_t N) { return kge_lp_xent_chunks(N); }
+extern "C" int kge_lp_bce_chunks(int64_t N) { return chunk_count(N); }
 
 extern "C" size_t kge_lp_bce_ws_bytes(int64_t B, int64_t N, int K0, int K1)
 {
-    if (B <= 0 || N <= 0 || K0 <= 0 || K1 < 0 || (int64_t)K0 + K1 > KGE_BCE_MAX_K) return 0;
+    if (B <= 0 || N <= 0 || K0 <= 0 || K1 < 0 || (int64_t)K0 + K1 > MAX_K) return 0;
     if (B >= ((int64_t)1 << 31) || N >= ((int64_t)1 << 31)) return 0;
-    const size_t chunks = (size_t)kge_lp_bce_chunks(N);
+    const size_t chunks = (size_t)chunk_count(N);
     return (size_t)24 * B * chunks + (size_t)4 * chunks * B * (size_t)(K0 + K1);
 }
 
@@ -252,19 +232,10 @@ extern "C" int kge_lp_bce_fwd(const kge_lp_desc *desc, const int64_t *seg_lo, co
                               float label_smoothing, float *row_loss, void *ws, size_t ws_bytes, kge_stream_t stream)
 {
     BceParams p = {};
-    bool vec4 = false;
     if (!row_loss) return KGE_EINVAL;
-    if (int e = bce_setup(desc, seg_lo, seg_hi, labels, label_smoothing, ws, ws_bytes, p, vec4)) return e;
-    if (desc->B == 0) return 0;
+    if (int e = bce_setup(desc, seg_lo, seg_hi, labels, label_smoothing, ws, ws_bytes, p)) return e;
     p.row_loss = row_loss;
-    hipStream_t s = kge_s(stream);
-    const dim3 grid(p.chunks, p.row_panels);
-    if (vec4) hipLaunchKernelGGL(bce_stats_kernel<true>, grid, dim3(NTHREADS), 0, s, p);
-    else hipLaunchKernelGGL(bce_stats_kernel<false>, grid, dim3(NTHREADS), 0, s, p);
-    KGE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bce_finish_kernel, dim3(p.row_panels), dim3(BM), 0, s, p);
-    KGE_CHECK_LAUNCH();
-    return 0;
+    return launch_fwd(bce_stats_kernel<false>, bce_stats_kernel<true>, bce_finish_kernel, p, kge_s(stream));
 }
 
 extern "C" int kge_lp_bce_bwd(const kge_lp_desc *desc, const int64_t *seg_lo, const int64_t *seg_hi, const int32_t *labels,
@@ -273,31 +244,10 @@ extern "C" int kge_lp_bce_bwd(const kge_lp_desc *desc, const int64_t *seg_lo, co
                               kge_stream_t stream)
 {
     BceParams p = {};
-    bool vec4 = false;
     if (!g) return KGE_EINVAL;
-    if (int e = bce_setup(desc, seg_lo, seg_hi, labels, label_smoothing, ws, ws_bytes, p, vec4)) return e;
-    if (int e = grad_groups_check(desc, dA0, ldda0, dA1, ldda1, dT0, lddt0, dT1, lddt1)) return e;
-    const bool want_a = dA0 != nullptr, want_t = dT0 != nullptr;
-    if (desc->B == 0) return 0;
+    if (int e = bce_setup(desc, seg_lo, seg_hi, labels, label_smoothing, ws, ws_bytes, p)) return e;
     p.g = g;
-    hipStream_t s = kge_s(stream);
-    const int slices = (desc->K0 + desc->K1 + KSLICE - 1) / KSLICE;
-    if (want_t) {
-        p.o0 = dT0; p.ldo0 = lddt0; p.o1 = dT1; p.ldo1 = lddt1;
-        const dim3 grid(p.col_tiles, 1, slices);
-        if (vec4) hipLaunchKernelGGL((bce_grad_kernel<true, true>), grid, dim3(NTHREADS), 0, s, p);
-        else hipLaunchKernelGGL((bce_grad_kernel<false, true>), grid, dim3(NTHREADS), 0, s, p);
-        KGE_CHECK_LAUNCH();
-    }
-    if (want_a) {
-        p.o0 = dA0; p.ldo0 = ldda0; p.o1 = dA1; p.ldo1 = ldda1;
-        const dim3 grid(p.chunks, p.row_panels, slices);
-        if (vec4) hipLaunchKernelGGL((bce_grad_kernel<true, false>), grid, dim3(NTHREADS), 0, s, p);
-        else hipLaunchKernelGGL((bce_grad_kernel<false, false>), grid, dim3(NTHREADS), 0, s, p);
-        KGE_CHECK_LAUNCH();
-        const int64_t n = desc->B * (int64_t)(desc->K0 + desc->K1);
-        hipLaunchKernelGGL(bce_sum_chunks_kernel, dim3(grid1d(n, 256)), dim3(256), 0, s, p);
-        KGE_CHECK_LAUNCH();
-    }
-    return 0;
+    return launch_bwd(bce_grad_kernel<false, true>, bce_grad_kernel<true, true>, bce_grad_kernel<false, false>,
+                      bce_grad_kernel<true, false>, bce_sum_chunks_kernel, p, dA0, ldda0, dA1, ldda1, dT0, lddt0, dT1, lddt1,
+                      kge_s(stream));
 }

@@ -2,13 +2,16 @@
 // all N candidates, and its gradients, without the (B, N) score matrix (gfx950).
 //
 // Every kernel recomputes the score tile it needs with score_tile() of lp_tile64.h -- the skeleton this criterion shares
-// with lp_bce.hip: the bit-defined 64 x 64 score tile, the gradient walk (S tile -> G tile in LDS -> MFMA operand, dA per
-// (row panel, chunk, column slice) into the workspace, dT per (candidate tile, column slice) stored once) and the chunk
-// sum of dA.  What is this criterion's own:
-//  * xent_stats_kernel: block = (row panel, candidate chunk); the S tile goes through LDS to a row-wise pass (4 threads
-//    per row, 16 candidates each) that keeps (m, l, sum s) online across the chunk; one partial per (row, chunk);
+// with lp_bce.hip: the bit-defined 64 x 64 score tile, the chunk arithmetic, the statistics walk (block = (row panel,
+// candidate chunk), S tile through LDS to a row-wise pass, one partial per (row, chunk)), the gradient walk (S tile -> G
+// tile in LDS -> MFMA operand, dA per (row panel, chunk, column slice) into the workspace, dT per (candidate tile, column
+// slice) stored once), the chunk sum of dA, the entries' shared checks and the two launch sequences.  The kernels here
+// are one-line bodies around it.  What is this criterion's own:
+//  * XentStat: a thread's 16 candidates of a row keep (m, l, sum s) online across the chunk; the row's four threads
+//    merge in LDS into the (row, chunk) partial; the thread that meets the target writes s(i, t_i);
 //  * xent_finish_kernel: one block per panel merges the chunks in ascending order, writes lse / row_loss;
-//  * XentCrit: G(i, c) = g_i (expf(s - lse_i) - q(i, c)) from the panel's (lse, g, target) in LDS.
+//  * XentCrit: G(i, c) = g_i (expf(s - lse_i) - q(i, c)) from the panel's (lse, g, target) in LDS;
+//  * the parameter block, the workspace layout and the four extern "C" entries.
 #include "kge_common.h"
 #include "../../include/kge_hip_xent.h"
 #include "lp_tile64.h"
@@ -16,7 +19,9 @@
 namespace {
 
 using namespace tile64;
-static_assert(BM == KGE_XENT_BM && BN == KGE_XENT_BN && KSLICE == KGE_XENT_KSLICE, "the geometry the header publishes");
+static_assert(BM == KGE_XENT_BM && BN == KGE_XENT_BN && KSLICE == KGE_XENT_KSLICE &&
+              MIN_TILES_PER_CHUNK == KGE_XENT_MIN_TILES_PER_CHUNK && MAX_CHUNKS == KGE_XENT_MAX_CHUNKS &&
+              MAX_K == KGE_XENT_MAX_K, "the geometry the header publishes");
 
 struct XentParams {
     kge_lp_desc d;
@@ -44,69 +49,64 @@ __device__ __forceinline__ void merge_ml(const float *m, const float *l, int n, 
     for (int q = 0; q < n; ++q) L += l[q] * expf(m[q] - M);     // an empty partial is (-inf, 0): adds 0
 }
 
-template <bool VEC4>
-__global__ __launch_bounds__(NTHREADS) void xent_stats_kernel(const XentParams p)
-{
-    __shared__ __attribute__((aligned(16))) float As[BM * LDS_LD];
-    __shared__ __attribute__((aligned(16))) float Bs[BN * LDS_LD];
-    __shared__ float Ss[BM * G_LD];
-    __shared__ float m_s[BM * 4], l_s[BM * 4];
-    __shared__ double ss_s[BM * 4];
-    const kge_lp_desc &d = p.d;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wr = wid >> 1, wc = wid & 1, l31 = lane & 31, half = lane >> 5;
-    const int chunk = blockIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.y * BM;
-    const int t0 = (int)((int64_t)p.col_tiles * chunk / p.chunks), t1 = (int)((int64_t)p.col_tiles * (chunk + 1) / p.chunks);
-
-    const int prow = tid >> 2, pq = tid & 3;      // row-wise pass: candidates 16 pq .. 16 pq + 15 of row prow
-    const int64_t row = row0 + prow;
-    const int64_t tgt = row < d.B ? p.target[row] : -1;
-    float m = -INFINITY, l = 0.f;
-    double ss = 0.0;
-
-    for (int t = t0; t < t1; ++t) {
-        const int64_t col0 = (int64_t)t * BN;
-        f32x16 acc;
-        score_tile<VEC4>(d, row0, col0, As, Bs, acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            Ss[(wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * G_LD + wc * 32 + l31] = acc[r];
-        __syncthreads();
-        const int nvalid = (int)min((int64_t)BN, d.N - col0), c_lo = pq * 16;
-        if (c_lo < nvalid) {    // candidates >= N never enter
-            const int cnt = min(16, nvalid - c_lo);
-            float v[16];
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                v[e] = Ss[prow * G_LD + c_lo + e];
-                if (e < cnt) tmax = fmaxf(tmax, v[e]);
-            }
-            const float mn = fmaxf(m, tmax);
-            float sum = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (e < cnt) {
-                    sum += expf(v[e] - mn);
-                    ss += (double)v[e];
-                }
-            l = l * expf(m - mn) + sum;
-            m = mn;
-            const int64_t tc = tgt - col0;
-            if (tc >= c_lo && tc < c_lo + cnt) p.ws_st[row] = Ss[prow * G_LD + (int)tc];
-        }
-        // (the next score_tile synchronises before anything overwrites Ss)
+// the softmax statistics of stats_walk(): (m, l) online and the fp64 sum of the scores, per thread
+struct XentStat {
+    const XentParams &p;
+    float *m_s, *l_s;
+    double *ss_s;
+    int64_t tgt;
+    float m, l;
+    double ss;
+    __device__ __forceinline__ void start(int64_t row, bool ok, int64_t)
+    {
+        tgt = ok ? p.target[row] : -1;
+        m = -INFINITY; l = 0.f; ss = 0.0;
     }
-    m_s[tid] = m; l_s[tid] = l; ss_s[tid] = ss;
-    __syncthreads();
-    if (pq == 0 && row < d.B) {
+    __device__ __forceinline__ void tile(int64_t) {}
+    __device__ __forceinline__ void add(const float *s, int64_t row, int64_t col0, int c_lo, int cnt)
+    {
+        float v[16];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            v[e] = s[c_lo + e];
+            if (e < cnt) tmax = fmaxf(tmax, v[e]);
+        }
+        const float mn = fmaxf(m, tmax);
+        float sum = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            if (e < cnt) {
+                sum += expf(v[e] - mn);
+                ss += (double)v[e];
+            }
+        l = l * expf(m - mn) + sum;
+        m = mn;
+        const int64_t tc = tgt - col0;
+        if (tc >= c_lo && tc < c_lo + cnt) p.ws_st[row] = s[(int)tc];
+    }
+    __device__ __forceinline__ void publish(int tid) { m_s[tid] = m; l_s[tid] = l; ss_s[tid] = ss; }
+    __device__ __forceinline__ void write(int64_t row, int chunk, int tid) const
+    {
         float M, L;
         merge_ml(m_s + tid, l_s + tid, 4, M, L);
         const double SS = ((ss_s[tid] + ss_s[tid + 1]) + ss_s[tid + 2]) + ss_s[tid + 3];
         p.ws_ml[row * p.chunks + chunk] = make_float2(M, L);
         p.ws_ss[row * p.chunks + chunk] = SS;
     }
+};
+
+// (NTHREADS, 4): the block's LDS lets four blocks share a CU -- four waves per SIMD -- and the registers are held to that
+template <bool VEC4>
+__global__ __launch_bounds__(NTHREADS, 4) void xent_stats_kernel(const XentParams p)
+{
+    __shared__ __attribute__((aligned(16))) float As[BM * LDS_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[BN * LDS_LD];
+    __shared__ float Ss[BM * G_LD];
+    __shared__ float m_s[BM * 4], l_s[BM * 4];
+    __shared__ double ss_s[BM * 4];
+    XentStat stat = {p, m_s, l_s, ss_s};
+    stats_walk<VEC4>(p, stat, As, Bs, Ss);
 }
 
 __global__ __launch_bounds__(BM) void xent_finish_kernel(const XentParams p)
@@ -172,53 +172,33 @@ __global__ __launch_bounds__(NTHREADS) void xent_grad_kernel(const XentParams p)
 
 __global__ __launch_bounds__(256) void xent_sum_chunks_kernel(const XentParams p) { sum_chunks(p); }
 
-// shared validation of both entries; fills the geometry and the workspace pointers
-int xent_setup(const kge_lp_desc *d, const int64_t *target, float eps, void *ws, size_t ws_bytes, XentParams &p, bool &vec4)
+// validation of both entries (tile64::setup) and what is this criterion's own of the parameter block
+int xent_setup(const kge_lp_desc *d, const int64_t *target, float eps, void *ws, size_t ws_bytes, XentParams &p)
 {
-    if (!d) return KGE_EINVAL;
-    if (d->mode != KGE_LP_DOT || d->c_base != 0) return KGE_EUNSUPPORTED;
-    if (int e = kge_lp_desc_check(d)) return e;
-    if ((int64_t)d->K0 + d->K1 > KGE_XENT_MAX_K) return KGE_EUNSUPPORTED;
-    if (d->B >= ((int64_t)1 << 31) || d->N >= ((int64_t)1 << 31) || d->B > (int64_t)65535 * BM) return KGE_EUNSUPPORTED;
-    if (!(eps >= 0.f && eps <= 1.f)) return KGE_EINVAL;
+    if (int e = setup(d, target != nullptr, eps, ws, ws_bytes, kge_lp_xent_ws_bytes, p)) return e;
     if (d->B == 0) return 0;
-    if (d->N <= 0 || !target) return KGE_EINVAL;
-    if (d->lda0 < d->K0 && d->B > 1) return KGE_EINVAL;
-    const size_t need = kge_lp_xent_ws_bytes(d->B, d->N, d->K0, d->K1);
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15) || need == 0 || ws_bytes < need) return KGE_EINVAL;
-    p.d = *d;
     p.target = target;
     p.eps = eps;
     p.one_m_eps = 1.0f - eps;
     p.eps_n = eps / (float)d->N;
     p.q_t = p.one_m_eps + p.eps_n;
-    p.chunks = kge_lp_xent_chunks(d->N);
-    p.col_tiles = (int)((d->N + BN - 1) / BN);
-    p.row_panels = (int)((d->B + BM - 1) / BM);
     char *w = static_cast<char *>(ws);
     p.ws_ss = reinterpret_cast<double *>(w);
     p.ws_ml = reinterpret_cast<float2 *>(w + (size_t)8 * d->B * p.chunks);
     p.ws_st = reinterpret_cast<float *>(w + (size_t)16 * d->B * p.chunks);
     p.ws_da = reinterpret_cast<float *>(w + (size_t)16 * d->B * p.chunks + align16((size_t)4 * d->B));
-    vec4 = operands_vec4(d);
     return 0;
 }
 
 } // namespace
 
-extern "C" int kge_lp_xent_chunks(int64_t N)
-{
-    if (N <= 0) return 0;
-    const int64_t tiles = (N + BN - 1) / BN;
-    const int64_t c = (tiles + KGE_XENT_MIN_TILES_PER_CHUNK - 1) / KGE_XENT_MIN_TILES_PER_CHUNK;
-    return (int)(c < KGE_XENT_MAX_CHUNKS ? c : KGE_XENT_MAX_CHUNKS);
-}
+extern "C" int kge_lp_xent_chunks(int64_t N) { return chunk_count(N); }
 
 extern "C" size_t kge_lp_xent_ws_bytes(int64_t B, int64_t N, int K0, int K1)
 {
-    if (B <= 0 || N <= 0 || K0 <= 0 || K1 < 0 || (int64_t)K0 + K1 > KGE_XENT_MAX_K) return 0;
+    if (B <= 0 || N <= 0 || K0 <= 0 || K1 < 0 || (int64_t)K0 + K1 > MAX_K) return 0;
     if (B >= ((int64_t)1 << 31) || N >= ((int64_t)1 << 31)) return 0;
-    const size_t chunks = (size_t)kge_lp_xent_chunks(N);
+    const size_t chunks = (size_t)chunk_count(N);
     return (size_t)16 * B * chunks + align16((size_t)4 * B) + (size_t)4 * chunks * B * (size_t)(K0 + K1);
 }
 
@@ -226,20 +206,11 @@ extern "C" int kge_lp_xent_fwd(const kge_lp_desc *desc, const int64_t *target, f
                                float *row_loss, void *ws, size_t ws_bytes, kge_stream_t stream)
 {
     XentParams p = {};
-    bool vec4 = false;
     if (!lse || !row_loss) return KGE_EINVAL;
-    if (int e = xent_setup(desc, target, label_smoothing, ws, ws_bytes, p, vec4)) return e;
-    if (desc->B == 0) return 0;
+    if (int e = xent_setup(desc, target, label_smoothing, ws, ws_bytes, p)) return e;
     p.lse = lse;
     p.row_loss = row_loss;
-    hipStream_t s = kge_s(stream);
-    const dim3 grid(p.chunks, p.row_panels);
-    if (vec4) hipLaunchKernelGGL(xent_stats_kernel<true>, grid, dim3(NTHREADS), 0, s, p);
-    else hipLaunchKernelGGL(xent_stats_kernel<false>, grid, dim3(NTHREADS), 0, s, p);
-    KGE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(xent_finish_kernel, dim3(p.row_panels), dim3(BM), 0, s, p);
-    KGE_CHECK_LAUNCH();
-    return 0;
+    return launch_fwd(xent_stats_kernel<false>, xent_stats_kernel<true>, xent_finish_kernel, p, kge_s(stream));
 }
 
 extern "C" int kge_lp_xent_bwd(const kge_lp_desc *desc, const int64_t *target, float label_smoothing, const float *lse,
@@ -247,32 +218,11 @@ extern "C" int kge_lp_xent_bwd(const kge_lp_desc *desc, const int64_t *target, f
                                int64_t lddt0, float *dT1, int64_t lddt1, void *ws, size_t ws_bytes, kge_stream_t stream)
 {
     XentParams p = {};
-    bool vec4 = false;
     if (!lse || !g) return KGE_EINVAL;
-    if (int e = xent_setup(desc, target, label_smoothing, ws, ws_bytes, p, vec4)) return e;
-    if (int e = grad_groups_check(desc, dA0, ldda0, dA1, ldda1, dT0, lddt0, dT1, lddt1)) return e;
-    const bool want_a = dA0 != nullptr, want_t = dT0 != nullptr;
-    if (desc->B == 0) return 0;
+    if (int e = xent_setup(desc, target, label_smoothing, ws, ws_bytes, p)) return e;
     p.lse_in = lse;
     p.g = g;
-    hipStream_t s = kge_s(stream);
-    const int slices = (desc->K0 + desc->K1 + KGE_XENT_KSLICE - 1) / KGE_XENT_KSLICE;
-    if (want_t) {
-        p.o0 = dT0; p.ldo0 = lddt0; p.o1 = dT1; p.ldo1 = lddt1;
-        const dim3 grid(p.col_tiles, 1, slices);
-        if (vec4) hipLaunchKernelGGL((xent_grad_kernel<true, true>), grid, dim3(NTHREADS), 0, s, p);
-        else hipLaunchKernelGGL((xent_grad_kernel<false, true>), grid, dim3(NTHREADS), 0, s, p);
-        KGE_CHECK_LAUNCH();
-    }
-    if (want_a) {
-        p.o0 = dA0; p.ldo0 = ldda0; p.o1 = dA1; p.ldo1 = ldda1;
-        const dim3 grid(p.chunks, p.row_panels, slices);
-        if (vec4) hipLaunchKernelGGL((xent_grad_kernel<true, false>), grid, dim3(NTHREADS), 0, s, p);
-        else hipLaunchKernelGGL((xent_grad_kernel<false, false>), grid, dim3(NTHREADS), 0, s, p);
-        KGE_CHECK_LAUNCH();
-        const int64_t n = desc->B * (int64_t)(desc->K0 + desc->K1);
-        hipLaunchKernelGGL(xent_sum_chunks_kernel, dim3(grid1d(n, 256)), dim3(256), 0, s, p);
-        KGE_CHECK_LAUNCH();
-    }
-    return 0;
+    return launch_bwd(xent_grad_kernel<false, true>, xent_grad_kernel<true, true>, xent_grad_kernel<false, false>,
+                      xent_grad_kernel<true, false>, xent_sum_chunks_kernel, p, dA0, ldda0, dA1, ldda1, dT0, lddt0, dT1, lddt1,
+                      kge_s(stream));
 }

@@ -19,10 +19,11 @@ ranks.  There is no fallback: tensors that are not on the GPU raise."""
 import torch
 
 from .. import _hip, _hip_bce
-from .one_vs_all import _QueryRows, _problem
+from . import all_candidates
+from .all_candidates import REDUCTIONS      # noqa: F401
+from .one_vs_all import _QueryRows
 
 SIDES = ('tail', 'head')
-REDUCTIONS = ('mean', 'sum', 'none')
 
 
 class _AllCandidatesBce(torch.autograd.Function):
@@ -32,39 +33,16 @@ class _AllCandidatesBce(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, seg_lo, seg_hi, targets, label_smoothing, n_seg, *ops):
-        ops = [_hip.f32rows(x.detach()) for x in ops]
-        prob = _problem(ops[:n_seg], ops[n_seg:])
+        ops, prob = all_candidates.forward_problem(ctx, label_smoothing, n_seg, ops)
         row_loss = _hip_bce.bce_fwd(prob, (seg_lo, seg_hi, targets), label_smoothing)
-        ctx.eps, ctx.n_seg = label_smoothing, n_seg
         ctx.save_for_backward(seg_lo, seg_hi, targets, *ops)
         return row_loss
 
     @staticmethod
     def backward(ctx, grad_rows):
-        labels = ctx.saved_tensors[:3]
-        ops = ctx.saved_tensors[3:]
-        n = ctx.n_seg
-        needs = ctx.needs_input_grad[5:]
-        want_q, want_t = any(needs[:n]), any(needs[n:])
-        if not (want_q or want_t):
-            return (None,) * (5 + 2 * n)
-        prob = _problem(ops[:n], ops[n:])
-        g = grad_rows.contiguous() if grad_rows.dtype == torch.float32 else grad_rows.float().contiguous()
-        dA, dT = _hip_bce.bce_bwd(prob, labels, ctx.eps, g, want_queries=want_q, want_tables=want_t)
-        grads = list(dA or [None] * n) + list(dT or [None] * n)
-        return (None,) * 5 + tuple(x if need else None for x, need in zip(grads, needs))
-
-
-def _segments(x, what):
-    xs = (x,) if isinstance(x, torch.Tensor) else tuple(x)
-    if not 1 <= len(xs) <= 2:
-        raise ValueError('all_candidates_bce: %s is one matrix or a pair of them, got %d' % (what, len(xs)))
-    _hip.require_cuda(*xs)
-    for m in xs:
-        if m.dtype != torch.float32 or m.dim() != 2:
-            raise RuntimeError('torchkge_amd: all_candidates_bce expects float32 matrices, got %s of %d dimensions for the %s'
-                               % (m.dtype, m.dim(), what))
-    return xs
+        def bwd(prob, labels, g, **want):
+            return _hip_bce.bce_bwd(prob, labels, ctx.eps, g, **want)
+        return all_candidates.backward(ctx, grad_rows, 5, 3, bwd)
 
 
 def all_candidates_bce(queries, tables, labels, label_smoothing=0.0, reduction='mean'):
@@ -78,22 +56,11 @@ def all_candidates_bce(queries, tables, labels, label_smoothing=0.0, reduction='
     sums over the candidates, 'sum' their sum, 'mean' the sum divided by B * N (torch's definition).  Differentiable in
     the queries and the tables; the table gradient is dense, (N, K).  Deterministic whatever
     ``torchkge_amd.determinism`` says: no float atomic, a fixed order."""
-    if reduction not in REDUCTIONS:
-        raise ValueError("all_candidates_bce: reduction is 'mean', 'sum' or 'none', got %r" % (reduction,))
-    if not 0.0 <= label_smoothing <= 1.0:
-        raise ValueError('all_candidates_bce: label_smoothing must lie in [0, 1], got %r' % (label_smoothing,))
+    all_candidates.check_options('all_candidates_bce', label_smoothing, reduction)
     if not isinstance(labels, (tuple, list)) or len(labels) != 3:
         raise ValueError('all_candidates_bce: labels are (seg_lo, seg_hi, targets), got %r' % (type(labels).__name__,))
-    qs, ts = _segments(queries, 'queries'), _segments(tables, 'tables')
-    _hip.require_cuda(*labels)
-    if len(qs) != len(ts) or any(q.shape[1] != t.shape[1] for q, t in zip(qs, ts)):
-        raise ValueError('all_candidates_bce: queries and tables need the same segments, got widths %s and %s'
-                         % ([q.shape[1] for q in qs], [t.shape[1] for t in ts]))
-    if any(q.shape[0] != qs[0].shape[0] for q in qs) or any(t.shape[0] != ts[0].shape[0] for t in ts):
-        raise ValueError('all_candidates_bce: the segments of one operand need the same number of rows')
+    qs, ts = all_candidates.check_operands('all_candidates_bce', queries, tables, labels)
     B, N = qs[0].shape[0], ts[0].shape[0]
-    if N < 1:
-        raise ValueError('all_candidates_bce: no candidates')
     seg_lo, seg_hi, targets = labels
     if seg_lo.dim() != 1 or seg_hi.dim() != 1 or seg_lo.shape[0] != B or seg_hi.shape[0] != B:
         raise ValueError('all_candidates_bce: one label segment per query row: %d rows, seg_lo %s, seg_hi %s'

@@ -11,9 +11,10 @@ ranks.  There is no fallback: tensors that are not on the GPU raise."""
 import torch
 
 from .. import _hip, _hip_det, _hip_xent
+from . import all_candidates
+from .all_candidates import REDUCTIONS      # noqa: F401
 
 SIDES = ('both', 'tail', 'head')
-REDUCTIONS = ('mean', 'sum', 'none')
 
 
 class _AllCandidatesXent(torch.autograd.Function):
@@ -23,44 +24,16 @@ class _AllCandidatesXent(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, target, label_smoothing, n_seg, *ops):
-        ops = [_hip.f32rows(x.detach()) for x in ops]
-        prob = _problem(ops[:n_seg], ops[n_seg:])
+        ops, prob = all_candidates.forward_problem(ctx, label_smoothing, n_seg, ops)
         lse, row_loss = _hip_xent.xent_fwd(prob, target, label_smoothing)
-        ctx.eps, ctx.n_seg = label_smoothing, n_seg
         ctx.save_for_backward(target, lse, *ops)
         return row_loss
 
     @staticmethod
     def backward(ctx, grad_rows):
-        target, lse = ctx.saved_tensors[:2]
-        ops = ctx.saved_tensors[2:]
-        n = ctx.n_seg
-        needs = ctx.needs_input_grad[3:]
-        want_q, want_t = any(needs[:n]), any(needs[n:])
-        if not (want_q or want_t):
-            return (None,) * (3 + 2 * n)
-        prob = _problem(ops[:n], ops[n:])
-        g = grad_rows.contiguous() if grad_rows.dtype == torch.float32 else grad_rows.float().contiguous()
-        dA, dT = _hip_xent.xent_bwd(prob, target, ctx.eps, lse, g, want_queries=want_q, want_tables=want_t)
-        grads = list(dA or [None] * n) + list(dT or [None] * n)
-        return (None, None, None) + tuple(x if need else None for x, need in zip(grads, needs))
-
-
-def _problem(queries, tables):
-    return _hip.LpProblem(_hip.LP_DOT, queries[0], tables[0], A1=queries[1] if len(queries) > 1 else None,
-                          T1=tables[1] if len(tables) > 1 else None)
-
-
-def _segments(x, what):
-    xs = (x,) if isinstance(x, torch.Tensor) else tuple(x)
-    if not 1 <= len(xs) <= 2:
-        raise ValueError('all_candidates_cross_entropy: %s is one matrix or a pair of them, got %d' % (what, len(xs)))
-    _hip.require_cuda(*xs)
-    for m in xs:
-        if m.dtype != torch.float32 or m.dim() != 2:
-            raise RuntimeError('torchkge_amd: all_candidates_cross_entropy expects float32 matrices, got %s of %d dimensions '
-                               'for the %s' % (m.dtype, m.dim(), what))
-    return xs
+        def bwd(prob, saved, g, **want):
+            return _hip_xent.xent_bwd(prob, saved[0], ctx.eps, saved[1], g, **want)
+        return all_candidates.backward(ctx, grad_rows, 3, 2, bwd)
 
 
 def all_candidates_cross_entropy(queries, tables, target, label_smoothing=0.0, reduction='mean'):
@@ -70,19 +43,8 @@ def all_candidates_cross_entropy(queries, tables, target, label_smoothing=0.0, r
     (N, K0), (N, K1) -- the score is the sum over the segments, K0 + K1 <= 1024.  ``target``: int64 in [0, N) per row (a
     precondition; nothing checks it on the device).  Differentiable in the queries and the tables; the table gradient is
     dense, (N, K).  Deterministic whatever ``torchkge_amd.determinism`` says: no float atomic, a fixed order."""
-    if reduction not in REDUCTIONS:
-        raise ValueError("all_candidates_cross_entropy: reduction is 'mean', 'sum' or 'none', got %r" % (reduction,))
-    if not 0.0 <= label_smoothing <= 1.0:
-        raise ValueError('all_candidates_cross_entropy: label_smoothing must lie in [0, 1], got %r' % (label_smoothing,))
-    qs, ts = _segments(queries, 'queries'), _segments(tables, 'tables')
-    _hip.require_cuda(target)
-    if len(qs) != len(ts) or any(q.shape[1] != t.shape[1] for q, t in zip(qs, ts)):
-        raise ValueError('all_candidates_cross_entropy: queries and tables need the same segments, got widths %s and %s'
-                         % ([q.shape[1] for q in qs], [t.shape[1] for t in ts]))
-    if any(q.shape[0] != qs[0].shape[0] for q in qs) or any(t.shape[0] != ts[0].shape[0] for t in ts):
-        raise ValueError('all_candidates_cross_entropy: the segments of one operand need the same number of rows')
-    if ts[0].shape[0] < 1:
-        raise ValueError('all_candidates_cross_entropy: no candidates')
+    all_candidates.check_options('all_candidates_cross_entropy', label_smoothing, reduction)
+    qs, ts = all_candidates.check_operands('all_candidates_cross_entropy', queries, tables, (target,))
     rows = _AllCandidatesXent.apply(target, float(label_smoothing), len(qs), *(qs + ts))
     if reduction == 'none':
         return rows

@@ -131,7 +131,74 @@ class TrainDataLoaderIter:
         return self
 
 
-class Trainer:
+class _EpochLoop:
+    """The epochs of the three trainers, written once: ``run()`` and ``epoch_losses``.  A trainer supplies ``_step(batch,
+    acc=None)`` -- one training step, its loss as a device scalar, also added to the device float ``acc`` when given --
+    and the hooks below.  It reads ``model``, ``n_epochs``, ``sync_free`` and ``verbose`` of the instance."""
+
+    _epoch_sums = None          # sync_free: (device vector of the epochs' loss sums, batches per epoch)
+
+    def _prepare(self):
+        """Called by every ``run()`` behind ``model.cuda()``: builds and uploads what the batches are cut from, once --
+        a later ``run()`` finds it kept."""
+
+    def _batches(self):
+        """The batches of one epoch, as ``_step`` takes them."""
+        raise NotImplementedError
+
+    def _n_batches(self):
+        """The divisor of an epoch's loss sum (after ``_prepare``)."""
+        raise NotImplementedError
+
+    def _host_loss(self, batch):
+        """One step without ``sync_free``; its loss as a Python float (the step's one host read)."""
+        return self._step(batch).item()
+
+    def _after_epoch(self):
+        """Called behind ``model.normalize_parameters()``."""
+
+    def run(self):
+        self.model.cuda()
+        self._prepare()
+        epochs = range(self.n_epochs)
+        bar = None
+        if self.verbose:
+            try:
+                from tqdm.autonotebook import tqdm
+                epochs = bar = tqdm(epochs, unit='epoch')
+            except ImportError:
+                pass
+        n_batches = self._n_batches()
+        self._epoch_losses, self._epoch_sums = [], None
+        if self.sync_free:
+            device = next(self.model.parameters()).device
+            self._epoch_sums = (torch.zeros(self.n_epochs, dtype=torch.float32, device=device), n_batches)
+        for epoch in epochs:
+            if self.sync_free:
+                acc = self._epoch_sums[0][epoch]        # a view: the steps add into the vector's own element
+                for batch in self._batches():
+                    self._step(batch, acc)
+            else:
+                sum_ = 0
+                for batch in self._batches():
+                    sum_ += self._host_loss(batch)
+                self._epoch_losses.append(sum_ / n_batches)
+                if bar is not None:
+                    bar.set_description('Epoch {} | mean loss: {:.5f}'.format(epoch + 1, self._epoch_losses[-1]))
+            self.model.normalize_parameters()
+            self._after_epoch()
+
+    @property
+    def epoch_losses(self):
+        """The mean step loss of every epoch of the last ``run()``, as Python floats.  After a ``sync_free`` run the
+        first access reads the epoch sums back (one copy)."""
+        if self._epoch_sums is not None:
+            sums, n_batches = self._epoch_sums
+            self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
+        return self._epoch_losses
+
+
+class Trainer(_EpochLoop):
     """The reference's training procedure: per epoch a fresh corruption of ``kg_train``, one step per batch,
     ``model.normalize_parameters()``; the mean loss of every epoch is kept in ``epoch_losses``.
 
@@ -181,7 +248,6 @@ class Trainer:
         self._row_mode = isinstance(optimizer, (optim.RowSGD, optim.RowAdagrad, optim.RowAdam))
         self._loader = None
         self._epoch_losses = []
-        self._epoch_sums = None         # sync_free: (device vector of the epochs' loss sums, batches per epoch)
 
     def _step(self, batch, acc=None):
         """One training step; the loss as a device scalar, also added to the device float ``acc`` when given."""
@@ -208,79 +274,49 @@ class Trainer:
         """One step on a batch of the loader; its loss as a Python float (the step's one host read)."""
         return self._step(current_batch).item()
 
-    def run(self):
-        self.model.cuda()
+    def _host_loss(self, batch):
+        return self.process_batch(batch)
+
+    def _prepare(self):
         if isinstance(self.criterion, torch.nn.Module):
             self.criterion.cuda()
-        epochs = range(self.n_epochs)
-        bar = None
-        if self.verbose:
-            try:
-                from tqdm.autonotebook import tqdm
-                epochs = bar = tqdm(epochs, unit='epoch')
-            except ImportError:
-                pass
         if self._loader is None:        # kept: a later run() uploads nothing again
             self._loader = TrainDataLoader(self.kg_train, batch_size=self.batch_size, sampling_type=self.sampling_type,
                                            use_cuda=self.use_cuda, sampler=self.sampler, sync_free=self.sync_free,
                                            n_neg=self.n_neg)
-        data_loader = self._loader
-        self._epoch_losses, self._epoch_sums = [], None
-        if self.sync_free:
-            device = next(self.model.parameters()).device
-            self._epoch_sums = (torch.zeros(self.n_epochs, dtype=torch.float32, device=device), len(data_loader))
-        for epoch in epochs:
-            if self.sync_free:
-                acc = self._epoch_sums[0][epoch]        # a view: the steps add into the vector's own element
-                for batch in data_loader:
-                    self._step(batch, acc)
-            else:
-                sum_ = 0
-                for batch in data_loader:
-                    sum_ += self.process_batch(batch)
-                self._epoch_losses.append(sum_ / len(data_loader))
-                if bar is not None:
-                    bar.set_description('Epoch {} | mean loss: {:.5f}'.format(epoch + 1, self._epoch_losses[-1]))
-            self.model.normalize_parameters()
-            self.counter_examples = data_loader.get_counter_examples()
 
-    @property
-    def epoch_losses(self):
-        """The mean step loss of every epoch of the last ``run()``, as Python floats.  After a ``sync_free`` run the
-        first access reads the epoch sums back (one copy)."""
-        if self._epoch_sums is not None:
-            sums, n_batches = self._epoch_sums
-            self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
-        return self._epoch_losses
+    def _batches(self):
+        return self._loader     # every iteration corrupts the graph anew
+
+    def _n_batches(self):
+        return len(self._loader)
+
+    def _after_epoch(self):
+        self.counter_examples = self._loader.get_counter_examples()
 
     def get_counter_examples(self):
         """The counter-examples of the last epoch as a ``SmallKG``; None before ``run()``."""
         return self.counter_examples
 
 
-class OneVsAllTrainer:
-    """1-vs-all training of a model with ``one_vs_all_loss`` (DistMultModel, ComplExModel): per batch the softmax
-    cross-entropy of the true tail / head among ALL entities (torchkge_amd.utils.one_vs_all), without the (B, N) score
-    matrix.  There is no sampler and no criterion; the epochs are ``Trainer``'s -- the facts in their order, the last
-    batch short, ``model.normalize_parameters()`` after each, the mean step loss in ``epoch_losses`` (``sync_free=True``:
-    the steps add into one device float per epoch, read back on first access).
-
-    The entity tables' gradient is dense in this regime, so the row-wise optimizers of ``torchkge_amd.optim`` are
-    refused: use a ``torch.optim`` optimizer."""
+class _DenseGradientTrainer(_EpochLoop):
+    """What OneVsAllTrainer and KvsAllTrainer share: the constructor and its checks.  ``_REGIME`` names the regime in the
+    messages, ``_LOSS`` the model method it trains on."""
 
     def __init__(self, model, kg_train, n_epochs, batch_size, optimizer, label_smoothing=0.0, side='both', use_cuda='all',
                  *, sync_free=False, verbose=True):
+        name = type(self).__name__
         if use_cuda not in ('all', 'batch'):
-            raise ValueError("OneVsAllTrainer: use_cuda must be 'all' or 'batch', got %r -- the engine's models live on the "
-                             "GPU, there is no CPU training path" % (use_cuda,))
+            raise ValueError("%s: use_cuda must be 'all' or 'batch', got %r -- the engine's models live on the "
+                             "GPU, there is no CPU training path" % (name, use_cuda))
         if side not in ('both', 'tail', 'head'):
-            raise ValueError("OneVsAllTrainer: side is 'both', 'tail' or 'head', got %r" % (side,))
+            raise ValueError("%s: side is 'both', 'tail' or 'head', got %r" % (name, side))
         if isinstance(optimizer, (optim.RowSGD, optim.RowAdagrad, optim.RowAdam)):
-            raise ValueError('OneVsAllTrainer: %s updates the rows of a sparse row gradient, but the 1-vs-all gradient of '
+            raise ValueError('%s: %s updates the rows of a sparse row gradient, but the %s gradient of '
                              'an entity table is dense (every entity is a candidate of every query); use a torch.optim '
-                             'optimizer' % type(optimizer).__name__)
-        if type(model).one_vs_all_loss is Model.one_vs_all_loss:
-            model.one_vs_all_loss(None, None, None)     # raises NotImplementedError, naming the models that have it
+                             'optimizer' % (name, type(optimizer).__name__, self._REGIME))
+        if getattr(type(model), self._LOSS) is getattr(Model, self._LOSS):
+            getattr(model, self._LOSS)(None, None, None, None)      # raises NotImplementedError, naming those that have it
         self.model = model
         self.kg_train = kg_train
         self.use_cuda = use_cuda
@@ -292,74 +328,58 @@ class OneVsAllTrainer:
         self.n_triples = len(kg_train)
         self.sync_free = sync_free
         self.verbose = verbose
-        self._facts = None
         self._epoch_losses = []
-        self._epoch_sums = None         # sync_free: (device vector of the epochs' loss sums, batches per epoch)
+
+    def _loss(self, batch):
+        raise NotImplementedError
 
     def _step(self, batch, acc=None):
         """One training step; the loss as a device scalar, also added to the device float ``acc`` when given."""
         self.optimizer.zero_grad()
-        loss = self.model.one_vs_all_loss(batch[0], batch[1], batch[2], side=self.side,
-                                          label_smoothing=self.label_smoothing, reduction='mean')
+        loss = self._loss(batch)
         if acc is not None:
             acc.add_(loss.detach())
         loss.backward()
         self.optimizer.step()
         return loss.detach()
 
-    def _batches(self):
-        h, t, r = self._facts
-        for b in range(get_n_batches(len(h), self.batch_size)):
-            sl = slice(b * self.batch_size, (b + 1) * self.batch_size)
-            batch = (h[sl], t[sl], r[sl])
-            yield tuple(x.cuda() for x in batch) if self.use_cuda == 'batch' else batch
 
-    def run(self):
-        self.model.cuda()
-        epochs = range(self.n_epochs)
-        bar = None
-        if self.verbose:
-            try:
-                from tqdm.autonotebook import tqdm
-                epochs = bar = tqdm(epochs, unit='epoch')
-            except ImportError:
-                pass
+class OneVsAllTrainer(_DenseGradientTrainer):
+    """1-vs-all training of a model with ``one_vs_all_loss`` (DistMultModel, ComplExModel): per batch the softmax
+    cross-entropy of the true tail / head among ALL entities (torchkge_amd.utils.one_vs_all), without the (B, N) score
+    matrix.  There is no sampler and no criterion; the epochs are ``Trainer``'s -- the facts in their order, the last
+    batch short, ``model.normalize_parameters()`` after each, the mean step loss in ``epoch_losses`` (``sync_free=True``:
+    the steps add into one device float per epoch, read back on first access).
+
+    The entity tables' gradient is dense in this regime, so the row-wise optimizers of ``torchkge_amd.optim`` are
+    refused: use a ``torch.optim`` optimizer."""
+
+    _REGIME, _LOSS = '1-vs-all', 'one_vs_all_loss'
+    _facts = None
+
+    def _loss(self, batch):
+        return self.model.one_vs_all_loss(batch[0], batch[1], batch[2], side=self.side, label_smoothing=self.label_smoothing,
+                                          reduction='mean')
+
+    def _prepare(self):
         if self._facts is None:         # kept: a later run() uploads nothing again
             kg = self.kg_train
             self._facts = (kg.head_idx, kg.tail_idx, kg.relations)
             if self.use_cuda == 'all':
                 self._facts = tuple(x.cuda() for x in self._facts)
-        n_batches = get_n_batches(len(self._facts[0]), self.batch_size)
-        self._epoch_losses, self._epoch_sums = [], None
-        if self.sync_free:
-            device = next(self.model.parameters()).device
-            self._epoch_sums = (torch.zeros(self.n_epochs, dtype=torch.float32, device=device), n_batches)
-        for epoch in epochs:
-            if self.sync_free:
-                acc = self._epoch_sums[0][epoch]        # a view: the steps add into the vector's own element
-                for batch in self._batches():
-                    self._step(batch, acc)
-            else:
-                sum_ = 0
-                for batch in self._batches():
-                    sum_ += self._step(batch).item()
-                self._epoch_losses.append(sum_ / n_batches)
-                if bar is not None:
-                    bar.set_description('Epoch {} | mean loss: {:.5f}'.format(epoch + 1, self._epoch_losses[-1]))
-            self.model.normalize_parameters()
 
-    @property
-    def epoch_losses(self):
-        """The mean step loss of every epoch of the last ``run()``, as Python floats.  After a ``sync_free`` run the
-        first access reads the epoch sums back (one copy)."""
-        if self._epoch_sums is not None:
-            sums, n_batches = self._epoch_sums
-            self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
-        return self._epoch_losses
+    def _n_batches(self):
+        return get_n_batches(len(self._facts[0]), self.batch_size)
+
+    def _batches(self):
+        h, t, r = self._facts
+        for b in range(self._n_batches()):
+            sl = slice(b * self.batch_size, (b + 1) * self.batch_size)
+            batch = (h[sl], t[sl], r[sl])
+            yield tuple(x.cuda() for x in batch) if self.use_cuda == 'batch' else batch
 
 
-
-class KvsAllTrainer:
+class KvsAllTrainer(_DenseGradientTrainer):
     """K-vs-all training of a model with ``k_vs_all_loss`` (DistMultModel, ComplExModel): a query is a distinct key of
     the training graph -- (h, r) on the tail side, (t, r) on the head side -- its label the whole set of known answers,
     the criterion a binary cross-entropy with logits over ALL entities (torchkge_amd.utils.k_vs_all), without the (B, N)
@@ -376,34 +396,9 @@ class KvsAllTrainer:
     The entity tables' gradient is dense in this regime, so the row-wise optimizers of ``torchkge_amd.optim`` are
     refused: use a ``torch.optim`` optimizer."""
 
-    def __init__(self, model, kg_train, n_epochs, batch_size, optimizer, label_smoothing=0.0, side='both', use_cuda='all',
-                 *, sync_free=False, verbose=True):
-        if use_cuda not in ('all', 'batch'):
-            raise ValueError("KvsAllTrainer: use_cuda must be 'all' or 'batch', got %r -- the engine's models live on the "
-                             "GPU, there is no CPU training path" % (use_cuda,))
-        if side not in ('both', 'tail', 'head'):
-            raise ValueError("KvsAllTrainer: side is 'both', 'tail' or 'head', got %r" % (side,))
-        if isinstance(optimizer, (optim.RowSGD, optim.RowAdagrad, optim.RowAdam)):
-            raise ValueError('KvsAllTrainer: %s updates the rows of a sparse row gradient, but the K-vs-all gradient of '
-                             'an entity table is dense (every entity is a candidate of every query); use a torch.optim '
-                             'optimizer' % type(optimizer).__name__)
-        if type(model).k_vs_all_loss is Model.k_vs_all_loss:
-            model.k_vs_all_loss(None, None, None, None)     # raises NotImplementedError, naming the models that have it
-        self.model = model
-        self.kg_train = kg_train
-        self.use_cuda = use_cuda
-        self.n_epochs = n_epochs
-        self.optimizer = optimizer
-        self.batch_size = batch_size
-        self.label_smoothing = label_smoothing
-        self.side = side
-        self.n_triples = len(kg_train)
-        self.sync_free = sync_free
-        self.verbose = verbose
-        self._indexes = None            # {'tail': FilterIndex (h, r) -> tails, 'head': FilterIndex (t, r) -> heads}
-        self._targets = None            # the indexes' answer lists on the GPU
-        self._epoch_losses = []
-        self._epoch_sums = None         # sync_free: (device vector of the epochs' loss sums, batches per epoch)
+    _REGIME, _LOSS = 'K-vs-all', 'k_vs_all_loss'
+    _indexes = None             # {'tail': FilterIndex (h, r) -> tails, 'head': FilterIndex (t, r) -> heads}
+    _targets = None             # the indexes' answer lists on the GPU
 
     @staticmethod
     def key_batches(index, batch_size):
@@ -423,7 +418,12 @@ class KvsAllTrainer:
         """Steps of one epoch (after the indexes exist)."""
         return sum(get_n_batches(self._indexes[s].n_keys, self.batch_size) for s in self._sides())
 
-    def _build_indexes(self):
+    def _n_batches(self):
+        return max(self.n_batches(), 1)
+
+    def _prepare(self):
+        if self._indexes is not None:       # kept: a later run() builds and uploads nothing again
+            return
         from ..filter_index import FilterIndex
         kg = self.kg_train
         device = next(self.model.parameters()).device if self.use_cuda == 'all' else torch.device('cpu')
@@ -440,54 +440,7 @@ class KvsAllTrainer:
                     batch = tuple(x.cuda() for x in batch)
                 yield side, batch
 
-    def _step(self, side, batch, acc=None):
-        """One training step; the loss as a device scalar, also added to the device float ``acc`` when given."""
-        e, r, seg_lo, seg_hi = batch
-        self.optimizer.zero_grad()
-        loss = self.model.k_vs_all_loss(e, r, (seg_lo, seg_hi, self._targets[side]), side,
+    def _loss(self, batch):
+        side, (e, r, seg_lo, seg_hi) = batch
+        return self.model.k_vs_all_loss(e, r, (seg_lo, seg_hi, self._targets[side]), side,
                                         label_smoothing=self.label_smoothing, reduction='mean')
-        if acc is not None:
-            acc.add_(loss.detach())
-        loss.backward()
-        self.optimizer.step()
-        return loss.detach()
-
-    def run(self):
-        self.model.cuda()
-        epochs = range(self.n_epochs)
-        bar = None
-        if self.verbose:
-            try:
-                from tqdm.autonotebook import tqdm
-                epochs = bar = tqdm(epochs, unit='epoch')
-            except ImportError:
-                pass
-        if self._indexes is None:       # kept: a later run() builds and uploads nothing again
-            self._build_indexes()
-        n_batches = max(self.n_batches(), 1)
-        self._epoch_losses, self._epoch_sums = [], None
-        if self.sync_free:
-            device = next(self.model.parameters()).device
-            self._epoch_sums = (torch.zeros(self.n_epochs, dtype=torch.float32, device=device), n_batches)
-        for epoch in epochs:
-            if self.sync_free:
-                acc = self._epoch_sums[0][epoch]        # a view: the steps add into the vector's own element
-                for side, batch in self._batches():
-                    self._step(side, batch, acc)
-            else:
-                sum_ = 0
-                for side, batch in self._batches():
-                    sum_ += self._step(side, batch).item()
-                self._epoch_losses.append(sum_ / n_batches)
-                if bar is not None:
-                    bar.set_description('Epoch {} | mean loss: {:.5f}'.format(epoch + 1, self._epoch_losses[-1]))
-            self.model.normalize_parameters()
-
-    @property
-    def epoch_losses(self):
-        """The mean step loss of every epoch of the last ``run()``, as Python floats.  After a ``sync_free`` run the
-        first access reads the epoch sums back (one copy)."""
-        if self._epoch_sums is not None:
-            sums, n_batches = self._epoch_sums
-            self._epoch_losses, self._epoch_sums = [s / n_batches for s in sums.cpu().tolist()], None
-        return self._epoch_losses
