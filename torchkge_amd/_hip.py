@@ -18,10 +18,12 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libkge_hip.so')
 TRANSE_L1, TRANSE_L2, TRANSH, TRANSD, DISTMULT, COMPLEX, RESCAL, HOLE = range(8)
 TORUSE_L1, TORUSE_TORUS_L1, TORUSE_TORUS_L2, TORUSE_TORUS_EL2 = range(8, 12)
 TRANSR = 12
+ROTATE = 13         # include/kge_hip_rotate.h
 SIDE_TAIL, SIDE_HEAD, SIDE_PROJ_H, SIDE_PROJ_T, SIDE_BOTH = range(5)
 EW_ADD, EW_SUB, EW_MUL, EW_MULSUB, EW_MULADD = range(5)
 LP_DOT, LP_L2_EXPAND, LP_L1_DIRECT, LP_L2_DIRECT, LP_L2_PROJH, LP_L2_PROJD = range(6)
 LP_TORUS_L1, LP_TORUS_L2, LP_TORUS_EL2 = range(6, 9)
+LP_CMOD = 9         # include/kge_hip_rotate.h: complex modulus of interleaved rows (RotatE), on the VALU
 # the modes whose all-candidates scores are a GEMM (KGE_LP_IS_MFMA of include/kge_hip.h); the rest run on the VALU
 LP_MFMA_MODES = (LP_DOT, LP_L2_EXPAND, LP_L2_PROJH, LP_L2_PROJD)
 
@@ -322,6 +324,7 @@ _BWD_STREAMS = {
     TORUSE_TORUS_L2: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')], TORUSE_TORUS_EL2: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],
     RESCAL: [(0, 0, 2, 'ht')],
     TRANSR: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],      # (rel_emb's rows are the U rows of proj_mat's reduction)
+    ROTATE: [(0, 0, 2, 'ht'), (1, 2, 1, 'r')],      # (rows of 2d floats; the phase rows use the first d of theirs)
 }
 # the kinds whose last table holds a matrix per relation: (table, entry point, its arguments between the row streams and
 # the ids).  The matrix gradient is reduced per relation from the rows U, V of streams 2 / 3 (sorted by relation: no
@@ -331,7 +334,7 @@ _BWD_REL_TAIL = {
     TRANSR: (2, 'kge_transr_rel_grad', lambda U, V, ld, d_ent, d_rel: (U, ld, V, ld, d_rel, d_ent)),
 }
 # the kinds whose backward kernel can add element by element into the tables (no rows): the small-batch mode.  Not
-# TorusE: no per-element float atomics there at any batch size
+# TorusE, nor RotatE: no per-element float atomics there at any batch size
 _BWD_ATOMIC = frozenset(k for k in range(TORUSE_L1) if k not in _BWD_REL_TAIL)
 BWD_SORTED_MIN_BATCH = 2048     # below this the plain atomic scatter is as fast
 

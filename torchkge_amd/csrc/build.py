@@ -19,7 +19,7 @@ SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfm
            'lp_split_recheck.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip', 'lp_l1_sad.hip', 'rank_filter.hip',
            'lp_pairs.hip', 'topk.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip', 'transr_xform.hip', 'analogy.hip', 'convkb.hip',
            'triplet.hip', 'segment_sum_rows.hip', 'segment_sum_ordered.hip', 'relation_corrupt.hip', 'row_optim.hip', 'pair_loss.hip',
-           'redundancy.hip', 'lp_xent.hip', 'lp_bce.hip', 'group_loss.hip', 'score_fact_groups.hip']
+           'redundancy.hip', 'lp_xent.hip', 'lp_bce.hip', 'group_loss.hip', 'score_fact_groups.hip', 'rotate.hip']
 HEADERS = ['kge_common.h', 'score_rows.h', 'lp_pair_exact.h', 'rel_operator.h', 'lp_split_common.h', 'lp_operand_cells.h', 'lp_hi_sweep.h', 'mask_scan.h', 'segment_levels.h', 'lp_tile64.h', 'loss_common.h', os.path.join('..', '..', 'include', 'kge_hip.h'),
            os.path.join('..', '..', 'include', 'kge_hip_analogy.h'), os.path.join('..', '..', 'include', 'kge_hip_convkb.h'),
            os.path.join('..', '..', 'include', 'kge_hip_triplet.h'), os.path.join('..', '..', 'include', 'kge_hip_det.h'),
@@ -27,7 +27,7 @@ HEADERS = ['kge_common.h', 'score_rows.h', 'lp_pair_exact.h', 'rel_operator.h', 
            os.path.join('..', '..', 'include', 'kge_hip_train.h'), os.path.join('..', '..', 'include', 'kge_hip_redundancy.h'),
            os.path.join('..', '..', 'include', 'kge_hip_xent.h'), os.path.join('..', '..', 'include', 'kge_hip_bce.h'),
            os.path.join('..', '..', 'include', 'kge_hip_plan.h'), os.path.join('..', '..', 'include', 'kge_hip_group.h'),
-           os.path.join('..', '..', 'include', 'kge_hip_factgroup.h')]
+           os.path.join('..', '..', 'include', 'kge_hip_factgroup.h'), os.path.join('..', '..', 'include', 'kge_hip_rotate.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
 # libkge_hip.so does not depend on librccl
@@ -73,6 +73,8 @@ EXTRA_FLAGS = {'lp_direct.hip': ['-fno-slp-vectorize'], 'lp_hi_stream.hip': _NO_
 # it has no MFMA and no kernel of it runs beside one, so the lane-crossing packed form above has nothing to misread
 # beside; a packed add / mul gives the bits of two scalar ones, and at two passes over B * K floats behind expf / log1pf
 # the file is bound by its launches and loads, not by the VALU issue rate the half-rate packed forms would cost.
+# rotate.hip (RotatE's query rows and triple kernels: sincosf, a correctly rounded sqrtf and a division per complex coordinate
+# behind gathered loads) takes NO extra flag for the same reason: no MFMA beside it, nowhere near the VALU issue rate.
 # score_fact_groups.hip (a fact with its K negatives) takes NO extra flag either, and must not: its scores are the bits of
 # score_triples.hip's because both inline score_rows.h under the same flags.
 

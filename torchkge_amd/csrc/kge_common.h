@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/kge_hip.h"
+#include "../../include/kge_hip_rotate.h"
 
 #define KGE_WAVE 64
 
@@ -31,6 +32,12 @@ int kge_transr_score_fwd(const float *E, const float *R, const float *M, int d_e
 int kge_transr_score_bwd(const float *E, const float *R, const float *M, int d_ent, int d_rel, const int64_t *h,
                          const int64_t *t, const int64_t *r, int64_t B, const float *go, float *rows, int64_t rows_ld,
                          hipStream_t s);
+
+// KGE_ROTATE behind kge_score_triples / kge_score_triples_bwd (rotate.hip; gradient rows only)
+int kge_rotate_score_fwd(const float *E, const float *P, int d_ent, int d_rel, const int64_t *h, const int64_t *t,
+                         const int64_t *r, int64_t B, float *out, hipStream_t s);
+int kge_rotate_score_bwd(const float *E, const float *P, int d_ent, int d_rel, const int64_t *h, const int64_t *t,
+                         const int64_t *r, int64_t B, const float *go, float *rows, int64_t rows_ld, hipStream_t s);
 
 // gM[rho] = sum over the triples of relation rho, in the order of perm, of U_i V_i^T (d_r x d_e): the reduction behind
 // kge_transr_rel_grad and, with d_r = d_e, kge_rescal_rel_grad, which validate their own arguments (transr_xform.hip)
@@ -153,13 +160,15 @@ __device__ __forceinline__ float lp_epilogue_any(const kge_lp_desc &d, float dot
     return lp_epilogue_proj(d.mode, v0, x, y, d.Wq[i * d.ldw], d.Wq[i * d.ldw + 1]);
 }
 
-// ---- per-element terms of the group-of-four direct chains: L1 and the torus modes (include/kge_hip.h) --------------
+// ---- per-element terms of the group-of-four direct chains: L1, the torus modes and -- per PAIR of elements -- the complex
+// modulus (include/kge_hip.h) ------------------------------------------------------------------------------------------
 // x = q - t; every term is 0 at x = 0 (zero-filled padding k counts as nothing).  The compiler must not contract x * x
 // into the following subtraction (-ffp-contract=off): 1 - v rounds the ROUNDED square, as torch's `1 - (a - b) ** 2`.
 constexpr float KGE_TWO_PI_F = 6.2831855f;      // fp32(2 pi): the reference's `2 * pi * tmp` on an fp32 tensor
 template <int MODE>
 __device__ __forceinline__ float lp_direct_term(float x)
 {
+    static_assert(MODE != KGE_LP_CMOD, "the complex modulus is a term of a pair: lp_cmod_pair");
     if (MODE == KGE_LP_TORUS_L1) {
         const float a = fabsf(x);
         return fminf(a, 1.0f - a);
@@ -171,6 +180,16 @@ __device__ __forceinline__ float lp_direct_term(float x)
         return 1.0f - cosf(KGE_TWO_PI_F * u);
     }
     return fabsf(x);    // KGE_LP_L1_DIRECT
+}
+// KGE_LP_CMOD: the modulus of one complex coordinate, x = (re, im) of q - t stored interleaved.  sqrtf is the correctly
+// rounded fp32 square root (hipcc's default); 0 at x = (0, 0), so an absent pair counts as nothing.
+__device__ __forceinline__ float lp_cmod_pair(float xr, float xi) { return sqrtf(fmaf(xi, xi, xr * xr)); }
+// what an aligned group of four k adds to the accumulator: the terms as a tree, or the two moduli of its two pairs
+template <int MODE>
+__device__ __forceinline__ float lp_direct_group(float x0, float x1, float x2, float x3)
+{
+    if constexpr (MODE == KGE_LP_CMOD) return lp_cmod_pair(x0, x1) + lp_cmod_pair(x2, x3);
+    else return (lp_direct_term<MODE>(x0) + lp_direct_term<MODE>(x1)) + (lp_direct_term<MODE>(x2) + lp_direct_term<MODE>(x3));
 }
 // score from the accumulated terms (power-of-two scalings: exact, the same bits as scaling every term)
 template <int MODE>
@@ -187,10 +206,10 @@ __device__ __forceinline__ float lp_group_chain(const float *q, const float *t, 
 {
     float acc = 0.0f;
     for (int k = 0; k < K; k += 4) {
-        float m[4];
+        float x[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = lp_direct_term<MODE>(k + e < K ? q[k + e] - t[k + e] : 0.0f);
-        acc = acc + ((m[0] + m[1]) + (m[2] + m[3]));
+        for (int e = 0; e < 4; ++e) x[e] = k + e < K ? q[k + e] - t[k + e] : 0.0f;
+        acc = acc + lp_direct_group<MODE>(x[0], x[1], x[2], x[3]);
     }
     return acc;
 }
@@ -206,10 +225,11 @@ __device__ __forceinline__ float lp_pair_score(const kge_lp_desc &d, int64_t i, 
     }
     const float *q = d.A0 + i * d.lda0;
     const float *t = d.T0 + c * d.ldt0;
-    switch (d.mode) {   // the torus modes: no rank-1 term (kge_lp_desc_check)
+    switch (d.mode) {   // the torus modes and the complex modulus: no rank-1 term (kge_lp_desc_check)
     case KGE_LP_TORUS_L1: return lp_direct_finish<KGE_LP_TORUS_L1>(lp_group_chain<KGE_LP_TORUS_L1>(q, t, d.K0));
     case KGE_LP_TORUS_L2: return lp_direct_finish<KGE_LP_TORUS_L2>(lp_group_chain<KGE_LP_TORUS_L2>(q, t, d.K0));
     case KGE_LP_TORUS_EL2: return lp_direct_finish<KGE_LP_TORUS_EL2>(lp_group_chain<KGE_LP_TORUS_EL2>(q, t, d.K0));
+    case KGE_LP_CMOD: return lp_direct_finish<KGE_LP_CMOD>(lp_group_chain<KGE_LP_CMOD>(q, t, d.K0));
     default: break;
     }
     float acc = 0.0f;
@@ -250,8 +270,9 @@ static inline int kge_env_int(const char *name, int dflt)
 static inline int kge_lp_desc_check(const kge_lp_desc *d)
 {
     if (!d) return KGE_EINVAL;
-    if (d->mode < KGE_LP_DOT || d->mode > KGE_LP_TORUS_EL2) return KGE_EINVAL;
+    if (d->mode < KGE_LP_DOT || d->mode > KGE_LP_CMOD) return KGE_EINVAL;
     if (d->B < 0 || d->N < 0 || d->K0 <= 0 || d->K1 < 0) return KGE_EINVAL;
+    if (d->mode == KGE_LP_CMOD && (d->K0 & 1)) return KGE_EINVAL;       // rows of interleaved (re, im) pairs
     if (d->B == 0 || d->N == 0) return 0; // empty problem: nothing is dereferenced
     if (!d->A0 || !d->T0) return KGE_EINVAL;
     if (d->K1 > 0 && (!d->A1 || !d->T1)) return KGE_EINVAL;

@@ -22,7 +22,9 @@
 // torus dissimilarities (utils/dissimilarities.py:28-54) of x = q - e have no
 // GEMM form; each term (kge_common.h: lp_direct_term) goes through the L1
 // group-of-four accumulation, and the reference's (b, N, d) broadcast is never
-// built.
+// built.  RotatE (KGE_LP_CMOD) is one more instantiation: its entity rows are stored
+// interleaved (re, im), so a complex coordinate is an aligned pair inside the group
+// of four and its modulus (lp_cmod_pair) takes the place of two terms.
 #include "kge_common.h"
 #include "../../include/kge_hip_plan.h"
 
@@ -112,8 +114,9 @@ __device__ __forceinline__ void lds_store8(float *dst, const float (&v)[8])
 }
 
 // TM = 8 (plain) or 4 (AXPY: the per-pair scalar a(i,c) also lives in registers).
-// OP: the per-element operation -- KGE_LP_L2_DIRECT (one fmaf per k), or KGE_LP_L1_DIRECT / a KGE_LP_TORUS_* mode (one
-// add per aligned 4-group of lp_direct_term, kge_common.h); the torus modes have no rank-1 term (AXPY = false).
+// OP: the per-element operation -- KGE_LP_L2_DIRECT (one fmaf per k), or KGE_LP_L1_DIRECT / a KGE_LP_TORUS_* mode /
+// KGE_LP_CMOD (one add per aligned 4-group: lp_direct_group, kge_common.h -- four terms or, for the complex modulus of
+// interleaved rows, the moduli of the group's two pairs); the torus modes and CMOD have no rank-1 term (AXPY = false).
 template <bool VEC4, int OP, bool AXPY, bool COUNT, int TM>
 __global__ __launch_bounds__(NTHREADS, 2) void lp_direct_kernel(const DirectParams p)
 {
@@ -270,9 +273,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void lp_direct_kernel(const DirectPara
                         dz = fmaf(a, wv.z, dz); dw = fmaf(a, wv.w, dw);
                     }
                     float v = acc[i][j];
-                    if (OP != KGE_LP_L2_DIRECT) {   // the L1 / torus contract: one add per aligned 4-group, the group summed as a tree
-                        v = v + ((lp_direct_term<OP>(dx) + lp_direct_term<OP>(dy)) +
-                                 (lp_direct_term<OP>(dz) + lp_direct_term<OP>(dw)));
+                    if (OP != KGE_LP_L2_DIRECT) {   // the L1 / torus / modulus contract: one add per aligned 4-group (lp_direct_group)
+                        v = v + lp_direct_group<OP>(dx, dy, dz, dw);
                     } else {
                         v = fmaf(dx, dx, v); v = fmaf(dy, dy, v);
                         v = fmaf(dz, dz, v); v = fmaf(dw, dw, v);
@@ -637,6 +639,7 @@ int dispatch_torus_mode(DirectParams &p, bool count, hipStream_t s)
     case KGE_LP_TORUS_L1: return dispatch_torus<VEC4, KGE_LP_TORUS_L1>(p, count, s);
     case KGE_LP_TORUS_L2: return dispatch_torus<VEC4, KGE_LP_TORUS_L2>(p, count, s);
     case KGE_LP_TORUS_EL2: return dispatch_torus<VEC4, KGE_LP_TORUS_EL2>(p, count, s);
+    case KGE_LP_CMOD: return dispatch_torus<VEC4, KGE_LP_CMOD>(p, count, s);    // (RotatE: the same plain chain)
     default: return KGE_EINVAL;
     }
 }

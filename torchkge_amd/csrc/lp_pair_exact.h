@@ -29,17 +29,19 @@ static inline bool kge_lp_vec4(const kge_lp_desc &d)
 }
 
 // the chain a pair runs: the scalar walk of lp_pair_score (any mode, any layout), or one of the staged chains
-enum PairChain { PAIR_SCALAR, PAIR_DOT, PAIR_L1, PAIR_L2, PAIR_TL1, PAIR_TL2, PAIR_TEL2 };
+enum PairChain { PAIR_SCALAR, PAIR_DOT, PAIR_L1, PAIR_L2, PAIR_TL1, PAIR_TL2, PAIR_TEL2, PAIR_CMOD };
 // the kge_lp_desc mode whose per-element term / finish (lp_direct_term, lp_direct_finish) a staged direct chain uses
 constexpr int pair_chain_mode(PairChain ch)
 {
     return ch == PAIR_TL1 ? (int)KGE_LP_TORUS_L1 : ch == PAIR_TL2 ? (int)KGE_LP_TORUS_L2
-         : ch == PAIR_TEL2 ? (int)KGE_LP_TORUS_EL2 : ch == PAIR_L2 ? (int)KGE_LP_L2_DIRECT : (int)KGE_LP_L1_DIRECT;
+         : ch == PAIR_TEL2 ? (int)KGE_LP_TORUS_EL2 : ch == PAIR_CMOD ? (int)KGE_LP_CMOD
+         : ch == PAIR_L2 ? (int)KGE_LP_L2_DIRECT : (int)KGE_LP_L1_DIRECT;
 }
 
 // the direct modes' chains (lp_pair_score without the rank-1 term), one accumulator: L2 one fmaf per k in
-// ascending order; L1 and the torus modes one add per aligned 4-group of k, the group as (m0+m1)+(m2+m3).  `a` / `t`
-// must be readable (zero-filled) up to the next multiple of 4 -- the staged chunks below are.
+// ascending order; L1, the torus modes and the complex modulus one add per aligned 4-group of k (lp_direct_group: the
+// group's terms as (m0+m1)+(m2+m3), or the moduli of its two pairs).  `a` / `t` must be readable (zero-filled) up to the
+// next multiple of 4 -- the staged chunks below are.
 template <PairChain CH>
 __device__ __forceinline__ float lp_chain_direct(const float *__restrict__ a, const float *__restrict__ t, int K, float acc)
 {
@@ -47,8 +49,7 @@ __device__ __forceinline__ float lp_chain_direct(const float *__restrict__ a, co
         constexpr int OP = pair_chain_mode(CH);
         for (int k = 0; k < K; k += 4) {
             const float4 av = *reinterpret_cast<const float4 *>(a + k), tv = *reinterpret_cast<const float4 *>(t + k);
-            acc = acc + ((lp_direct_term<OP>(av.x - tv.x) + lp_direct_term<OP>(av.y - tv.y)) +
-                         (lp_direct_term<OP>(av.z - tv.z) + lp_direct_term<OP>(av.w - tv.w)));
+            acc = acc + lp_direct_group<OP>(av.x - tv.x, av.y - tv.y, av.z - tv.z, av.w - tv.w);
         }
     } else {
         for (int k = 0; k < K; ++k) {
@@ -170,7 +171,7 @@ struct PairVariant {
     __shared__ __attribute__((aligned(16))) float es[V::lds_floats]
 
 // What an entry point wants from the selector -- the rows of the table it reproduces, not an extension point:
-//   PAIR_DEFAULT            MFMA modes: staged dot; plain direct / torus with float4 rows and no rank-1 term: the staged
+//   PAIR_DEFAULT            MFMA modes: staged dot; plain direct / torus / CMOD with float4 rows and no rank-1 term: the staged
 //                           chain of the mode; everything else, and B or N outside (0, INT32_MAX]: scalar
 //   PAIR_MFMA_ELSE_SCALAR   MFMA modes: staged dot (same B, N condition); everything else scalar
 //   PAIR_STAGED             staged or KGE_EINVAL: MFMA modes the dot chain, plain L1 / L2 without rank-1 term their chain,
@@ -192,11 +193,12 @@ int lp_pair_dispatch(const kge_lp_desc &d, F &&f)
     } else {
         if constexpr (POL == PAIR_DEFAULT) {
             if (!mfma && !d.Wq && vec4 && fits) {
-                switch (d.mode) {   // (the torus modes: the same staging, their per-element terms)
+                switch (d.mode) {   // (the torus modes and the complex modulus: the same staging, their terms)
                 case KGE_LP_L1_DIRECT: return f(PairVariant<PAIR_L1, true>{});
                 case KGE_LP_TORUS_L1: return f(PairVariant<PAIR_TL1, true>{});
                 case KGE_LP_TORUS_L2: return f(PairVariant<PAIR_TL2, true>{});
                 case KGE_LP_TORUS_EL2: return f(PairVariant<PAIR_TEL2, true>{});
+                case KGE_LP_CMOD: return f(PairVariant<PAIR_CMOD, true>{});
                 default: return f(PairVariant<PAIR_L2, true>{});
                 }
             }

@@ -258,6 +258,9 @@ __global__ __launch_bounds__(256) void lp_batched_kernel(int mode, const float *
         const float *qq = q + i * ldq;
         const float *cc = cand + i * stride_b + c * stride_n;
         float acc = 0.f;
+        if (mode == KGE_LP_CMOD) {      // lanes over the complex coordinates of the interleaved rows (K even)
+            for (int k = 2 * lane; k < K; k += 128) acc = acc + lp_cmod_pair(qq[k] - cc[k], qq[k + 1] - cc[k + 1]);
+        } else
         for (int k = lane; k < K; k += 64) {
             if (mode == KGE_LP_DOT) acc = fmaf(qq[k], cc[k], acc);
             else {
@@ -433,8 +436,9 @@ extern "C" int kge_lp_scores_batched(int mode, const float *q, int64_t ldq, cons
                                      float *out, int64_t ldo, kge_stream_t stream)
 {
     if (mode != KGE_LP_DOT && mode != KGE_LP_L1_DIRECT && mode != KGE_LP_L2_DIRECT && mode != KGE_LP_TORUS_L1 &&
-        mode != KGE_LP_TORUS_L2 && mode != KGE_LP_TORUS_EL2)
+        mode != KGE_LP_TORUS_L2 && mode != KGE_LP_TORUS_EL2 && mode != KGE_LP_CMOD)
         return KGE_EINVAL;
+    if (mode == KGE_LP_CMOD && (K & 1)) return KGE_EINVAL;
     if (B < 0 || N < 0 || K <= 0 || ldo < N) return KGE_EINVAL;
     if (B == 0 || N == 0) return 0;
     if (!q || !cand || !out) return KGE_EINVAL;

@@ -288,6 +288,7 @@ extern "C" int kge_score_triples(int kind, const float *t0, const float *t1, con
     if (kind == KGE_RESCAL || kind == KGE_HOLE)
         return kge_bilinear_score_fwd(kind, t0, t1, d_ent, d_rel, h, t, r, B, out, kge_s(stream));
     if (kind == KGE_TRANSR) return kge_transr_score_fwd(t0, t1, t2, d_ent, d_rel, h, t, r, B, out, kge_s(stream));
+    if (kind == KGE_ROTATE) return kge_rotate_score_fwd(t0, t1, d_ent, d_rel, h, t, r, B, out, kge_s(stream));
     int rc = check_common(kind, t0, t1, t2, t3, d_ent, d_rel, h, t, r, B);
     if (rc) return rc;
     if (B == 0) return 0;
@@ -319,6 +320,7 @@ extern "C" int kge_score_triples_bwd(int kind, const float *t0, const float *t1,
         return kge_bilinear_score_bwd(kind, t0, t1, d_ent, d_rel, h, t, r, B, go, g0, g1, rows, rows_ld, kge_s(stream));
     if (kind == KGE_TRANSR)
         return kge_transr_score_bwd(t0, t1, t2, d_ent, d_rel, h, t, r, B, go, rows, rows_ld, kge_s(stream));
+    if (kind == KGE_ROTATE) return kge_rotate_score_bwd(t0, t1, d_ent, d_rel, h, t, r, B, go, rows, rows_ld, kge_s(stream));
     int rc = check_common(kind, t0, t1, t2, t3, d_ent, d_rel, h, t, r, B);
     if (rc) return rc;
     if (B == 0) return 0;

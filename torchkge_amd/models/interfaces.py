@@ -291,7 +291,8 @@ class Model(Module):
             P = _hip.LpProblem(mode, A0, rep[0], qn=qn, en=en, K0=K0)
         elif mode == _hip.LP_DOT:
             P = _hip.LpProblem(mode, A0, rep[0], A1=A1, T1=rep[1] if A1 is not None else None, K0=K0)
-        elif mode in (_hip.LP_L1_DIRECT, _hip.LP_L2_DIRECT, _hip.LP_TORUS_L1, _hip.LP_TORUS_L2, _hip.LP_TORUS_EL2):
+        elif mode in (_hip.LP_L1_DIRECT, _hip.LP_L2_DIRECT, _hip.LP_TORUS_L1, _hip.LP_TORUS_L2, _hip.LP_TORUS_EL2,
+                      _hip.LP_CMOD):
             P = _hip.LpProblem(mode, A0, rep[0], K0=K0)
         else:
             return None

@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
 """TransE / TransH / TransR / TransD / TorusE with the reference's constructors, attributes and
-state_dict keys (torchkge/models/translation.py:18-767) on the HIP engine.
+state_dict keys (torchkge/models/translation.py:18-767) on the HIP engine, and RotatE, which the
+reference does not have.
 
 TransH / TransD never build the reference's (n_rel, n_ent, d) projection cache
 (`projected_entities`, filled by an n_ent-iteration Python loop,
@@ -9,14 +10,15 @@ a = E.W^T] or per entity [TransD: s = Ep.E] is enough, and the rank-1
 correction is applied inside the all-candidates kernel.  TransR (:432-458)
 likewise: Z[r, c] = ||M_r e_c||^2 is all its cache is needed for.
 """
+import math
 import os
 
 import torch
 
-from .. import _hip
+from .. import _hip, _hip_rotate
 from ..exceptions import NotYetImplementedError
 from ..utils.modeling import init_embedding
-from .interfaces import TranslationModel, EntityCandidates, RelationProjections, _table_of, _ScoreTriples
+from .interfaces import Model, TranslationModel, EntityCandidates, RelationProjections, _table_of, _ScoreTriples
 from .interfaces import guard_slot, G_QMAX, G_EMAX, G_XABS, G_YABS
 
 
@@ -803,3 +805,124 @@ class TransRModel(TranslationModel):
         _, U = _hip.transr_query(_hip.SIDE_TAIL, None, M, None, self.ent_emb_dim, self.rel_emb_dim, None, None,
                                  cand.r_idx, Q=q)
         return self._problem(q, U, cand.r_idx, self._cand_rows(E, ent_lo, ent_hi), ent_lo)
+
+
+class RotatEModel(Model):
+    """RotatE (Sun et al. 2019: "RotatE: Knowledge Graph Embedding by Relational Rotation in Complex Space"; not in the
+    reference).  ``RotatEModel(emb_dim, n_entities, n_relations)``: entities are ``emb_dim`` complex numbers, a relation
+    is a rotation by ``emb_dim`` phases, score = -sum_k |h_k r_k - t_k| with r_k = exp(i theta_k).
+
+    Parameters: ``ent_emb`` (n_ent, 2 * emb_dim), a row stored INTERLEAVED as (re_0, im_0, re_1, im_1, ...) --
+    ``torch.view_as_complex(weight.view(n_ent, emb_dim, 2))`` is its complex view -- and ``rel_emb`` (n_rel, emb_dim), the
+    phases in radians, uniform in (-pi, pi).  No margin inside the score: gamma belongs to the criterion
+    (``SelfAdversarialLoss(margin=...)``).
+
+    Every all-candidates problem is the broadcast-subtract mode KGE_LP_CMOD of a query row q = h o r (tail side) or
+    q = t o conj(r) (head side; |h r - t| = |h - t conj(r)| for a unit-modulus r) against the RAW entity table: the
+    interleaved layout puts a complex coordinate inside the aligned group of four floats that the L1 / torus modes
+    accumulate by, so nothing is repacked and no (b, N, 2d) tensor exists.  Relation prediction scores the b * n_rel
+    expanded triples through the fused triple kernel."""
+
+    _kind = _hip.ROTATE
+    _ENT_TABLES = ('ent_emb',)
+    MAX_EMB_DIM = 512       # kge_score_triples takes entity rows of at most 1024 floats, for every kind
+
+    def __init__(self, emb_dim, n_entities, n_relations):
+        if int(emb_dim) != emb_dim or not 1 <= emb_dim <= self.MAX_EMB_DIM:
+            raise ValueError('torchkge_amd: RotatEModel needs 1 <= emb_dim <= %d (entity rows are 2 * emb_dim floats and the '
+                             'fused triple kernels take rows of at most 1024), got %r' % (self.MAX_EMB_DIM, emb_dim))
+        super().__init__(n_entities, n_relations)
+        self.emb_dim = int(emb_dim)
+        self.ent_emb = init_embedding(self.n_ent, 2 * self.emb_dim)
+        self.rel_emb = init_embedding(self.n_rel, self.emb_dim)
+        with torch.no_grad():
+            self.rel_emb.weight.uniform_(-math.pi, math.pi)
+        self.split_filter = False       # a modulus per coordinate has no GEMM form: no f16 prefilter, the exact VALU count
+
+    def _tables(self):
+        return [self.ent_emb.weight, self.rel_emb.weight]
+
+    def _uses_guard(self):
+        return False
+
+    def normalize_parameters(self):
+        """Nothing to project: the phases are free and the entities unconstrained."""
+        return None
+
+    def get_embeddings(self):
+        """(complex (n_ent, emb_dim) view of the entity table, (n_rel, emb_dim) phases)."""
+        E = self.ent_emb.weight.data
+        return torch.view_as_complex(E.contiguous().view(E.shape[0], self.emb_dim, 2)), self.rel_emb.weight.data
+
+    # ---- all-candidates problems -----------------------------------------------------------------------------------
+    def lp_problem(self, h_idx, t_idx, r_idx, side, ent_lo=0, ent_hi=None, exchange=None, qtabs=None, cols=None):
+        """s[i, c] = -sum_k |q_ik - e_ck| (complex modulus) for the entities [ent_lo, ent_hi): ONE launch writes the query
+        rows (kge_rotate_query), the candidates are the table's own rows.  Row-sharded tables: ``exchange`` / ``qtabs``
+        as TransE."""
+        ent_lo, ent_hi = _ent_range(self, ent_lo, ent_hi)
+        E, P = (_hip.f32c(x.data) for x in self._tables())
+        sd = _hip.side_code(side)
+        if qtabs is not None:       # replicas of the query entities' rows: h_idx / t_idx index THEM
+            Q = _hip_rotate.rotate_query(sd, _hip.f32c(qtabs[0]), P, h_idx, t_idx, r_idx)
+        elif self._row_shard is not None:
+            if exchange is None:
+                raise RuntimeError('torchkge_amd: a row-sharded model needs the evaluator\'s query exchange')
+            Q = _hip_rotate.rotate_query(sd, E, P, h_idx, t_idx, r_idx, ent_lo=self._row_shard[0],
+                                  ent_n=self._row_shard[1] - self._row_shard[0])
+            exchange([Q])
+        else:
+            Q = _hip_rotate.rotate_query(sd, E, P, h_idx, t_idx, r_idx)
+        return _hip.LpProblem(_hip.LP_CMOD, Q, self._cand_rows(E, ent_lo, ent_hi), c_base=ent_lo)
+
+    # ---- reference inference API -----------------------------------------------------------------------------------
+    def inference_prepare_candidates(self, h_idx, t_idx, r_idx, entities=True):
+        """(h, t, r, candidates): the gathered interleaved rows and phases; candidates is a stride-0 (b, N, 2 * emb_dim)
+        view of the entity table, or with ``entities=False`` the (b, n_rel, emb_dim) one of the phase table."""
+        self._check_unsharded('inference_prepare_candidates')
+        b_size = max(h_idx.shape[0], t_idx.shape[0], r_idx.shape[0])   # inference passes one empty index
+        E, P = self.ent_emb.weight.data, self.rel_emb.weight.data
+        h, t, r = _hip.gather_rows(E, h_idx), _hip.gather_rows(E, t_idx), _hip.gather_rows(P, r_idx)
+        if entities:
+            candidates = E.view(1, self.n_ent, 2 * self.emb_dim).expand(b_size, self.n_ent, 2 * self.emb_dim)
+        else:
+            candidates = P.view(1, self.n_rel, self.emb_dim).expand(b_size, self.n_rel, self.emb_dim)
+        return h, t, r, candidates
+
+    RELATION_CHUNK = 1 << 20    # expanded triples per kge_score_triples launch of relation prediction
+
+    def inference_scoring_function(self, h, t, r):
+        """-sum_k |h_k r_k - t_k| against every candidate; the 3-D argument is the candidate set.  Entity candidates: the
+        query rows of the gathered embeddings, then KGE_LP_CMOD.  Relation candidates: the b * n_rel triples (h_i, r_c,
+        t_i), scored in chunks by the fused triple kernel on the gathered rows."""
+        if torch.is_tensor(r) and r.dim() == 3:
+            return self._relation_scores(h, t, r)
+        assert r.dim() == 2
+        tail = torch.is_tensor(t) and t.dim() == 3
+        x, cand = (h, t) if tail else (t, h)
+        assert torch.is_tensor(x) and x.dim() == 2 and torch.is_tensor(cand) and cand.dim() == 3
+        _hip.require_cuda(x, r, cand)
+        ids = torch.arange(x.shape[0], device=x.device)
+        q = _hip_rotate.rotate_query(_hip.SIDE_TAIL if tail else _hip.SIDE_HEAD, x, r, ids, ids, ids)
+        table = _table_of(cand)
+        if table is not None:
+            return _hip.LpProblem(_hip.LP_CMOD, q, _hip.f32c(table)).scores()
+        return _hip.lp_scores_batched(_hip.LP_CMOD, q, cand)
+
+    def _relation_scores(self, h, t, cand):
+        _hip.require_cuda(h, t, cand)
+        b, n_rel, d = cand.shape
+        dev = h.device
+        table = _table_of(cand)
+        out = torch.empty(b, n_rel, dtype=torch.float32, device=dev)
+        step = max(1, self.RELATION_CHUNK // max(n_rel, 1))
+        rel = torch.arange(n_rel, device=dev)
+        for b0 in range(0, b, step):
+            n = min(step, b - b0)
+            X = torch.cat([h[b0:b0 + n], t[b0:b0 + n]])             # entity rows of this chunk: heads, then tails
+            hh = torch.arange(n, device=dev).repeat_interleave(n_rel)
+            if table is not None:
+                P, rr = _hip.f32c(table), rel.repeat(n)
+            else:
+                P, rr = cand[b0:b0 + n].reshape(n * n_rel, d), torch.arange(n * n_rel, device=dev)
+            out[b0:b0 + n] = _hip.score_triples(_hip.ROTATE, [X, P], 2 * d, d, hh, hh + n, rr).view(n, n_rel)
+        return out
