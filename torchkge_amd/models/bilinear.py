@@ -135,6 +135,12 @@ class ComplExModel(BilinearModel):
         return [self.re_ent_emb.weight, self.im_ent_emb.weight, self.re_rel_emb.weight,
                 self.im_rel_emb.weight]
 
+    def _penalty_groups(self):
+        """The complex modulus per coordinate of the entity pair and of the relation pair (Lacroix et al. 2018)."""
+        from .._hip_penalty import SPLIT
+        return ([(SPLIT, (self.re_ent_emb.weight, self.im_ent_emb.weight))],
+                [(SPLIT, (self.re_rel_emb.weight, self.im_rel_emb.weight))])
+
     @property
     def _d_rel(self):
         return self.emb_dim
@@ -477,6 +483,12 @@ class AnalogyModel(BilinearModel):
     def _tables(self):
         return [self.sc_ent_emb.weight, self.re_ent_emb.weight, self.im_ent_emb.weight,
                 self.sc_rel_emb.weight, self.re_rel_emb.weight, self.im_rel_emb.weight]
+
+    def _penalty_groups(self):
+        """The scalar tables element by element, the complex part by the modulus of a coordinate, on both sides."""
+        from .._hip_penalty import REAL, SPLIT
+        return ([(REAL, self.sc_ent_emb.weight), (SPLIT, (self.re_ent_emb.weight, self.im_ent_emb.weight))],
+                [(REAL, self.sc_rel_emb.weight), (SPLIT, (self.re_rel_emb.weight, self.im_rel_emb.weight))])
 
     def _lp_width(self):
         return self.scalar_dim + 2 * self.complex_dim

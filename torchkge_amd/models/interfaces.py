@@ -221,6 +221,20 @@ class Model(Module):
             if n != rows:
                 raise RuntimeError('torchkge_amd: entity table %r has %d rows, expected %d' % (name, n, rows))
 
+    def _penalty_groups(self):
+        """What an embedding regularizer (torchkge_amd.utils.regularizers) penalises: ``(entity groups, relation
+        groups)``, each a list of ``(layout, table)`` or ``(layout, (re table, im table))`` with the layouts of
+        include/kge_hip_penalty.h.  The default: every ``nn.Embedding`` table of ``_tables()`` by itself, element by
+        element (REAL) -- an entity group where ``_ENT_TABLES`` names it, a relation group otherwise.  Parameters that
+        are no embedding table (ConvKB's layers) are the optimizer's ``weight_decay`` to shrink."""
+        from .._hip_penalty import REAL
+        names = {id(m.weight): n for n, m in self.named_children() if isinstance(m, torch.nn.Embedding)}
+        ent, rel = [], []
+        for x in self._tables():
+            if id(x) in names:
+                (ent if names[id(x)] in self._ENT_TABLES else rel).append((REAL, x))
+        return ent, rel
+
     def entity_table_bytes(self):
         return sum(getattr(self, n).weight.numel() * 4 for n in self._ENT_TABLES)
 

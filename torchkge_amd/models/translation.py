@@ -842,6 +842,12 @@ class RotatEModel(Model):
     def _tables(self):
         return [self.ent_emb.weight, self.rel_emb.weight]
 
+    def _penalty_groups(self):
+        """The complex modulus of every entity coordinate; no relation group: the phases parametrise unit-modulus
+        numbers, there is nothing to shrink."""
+        from .._hip_penalty import INTERLEAVED
+        return [(INTERLEAVED, self.ent_emb.weight)], []
+
     def _uses_guard(self):
         return False
 

@@ -20,6 +20,10 @@ What is the engine's own:
   * ``trainer.grouped_forward = True`` (an attribute, off by default): the scores come from
     ``Model.forward_grouped`` -- a fact's rows gathered once for its K negatives, K + 3 instead of 3 (K + 1) gradient rows
     per fact for TransE -- with the bits of ``Model.forward``;
+  * ``trainer.regularizer = N3Regularizer(...)`` (an attribute of all three trainers, None by default): an embedding
+    regularizer of ``utils/regularizers.py`` penalises the rows of the batch's facts (not the negatives; K-vs-all: the key's
+    entity and relation row); its gradient rows are sparse inside ``row_gradients()``, so the row optimizers keep working,
+    and the penalty is part of ``epoch_losses``;
   * ``get_counter_examples()`` is None before ``run()`` and the last epoch's negatives after it (the reference's
     ``run`` asks its loader for them before the first iteration and raises).
 
@@ -212,6 +216,7 @@ class Trainer(_EpochLoop):
     fact's tail)."""
 
     grouped_forward = False     # True: Model.forward_grouped scores the batches (set it on the instance)
+    regularizer = None          # an embedding regularizer of utils/regularizers.py (set it on the instance)
 
     def __init__(self, model, criterion, kg_train, n_epochs, batch_size, optimizer, sampling_type='bern', use_cuda=None,
                  *, fused=True, sync_free=False, sampler=None, verbose=True, n_neg=1):
@@ -266,6 +271,8 @@ class Trainer(_EpochLoop):
                 loss = self.criterion(p, n)
                 if acc is not None:
                     acc.add_(loss.detach())
+            if self.regularizer is not None:    # the batch's facts; the negatives are not penalised
+                loss = loss + self.regularizer(self.model, (batch['h'], batch['t']), (batch['r'],), acc)
             loss.backward()
             self.optimizer.step()
         return loss.detach()
@@ -330,7 +337,13 @@ class _DenseGradientTrainer(_EpochLoop):
         self.verbose = verbose
         self._epoch_losses = []
 
+    regularizer = None          # an embedding regularizer of utils/regularizers.py (set it on the instance)
+
     def _loss(self, batch):
+        raise NotImplementedError
+
+    def _penalised(self, batch):
+        """(entity id vectors, relation id vectors) of a batch that ``regularizer`` penalises."""
         raise NotImplementedError
 
     def _step(self, batch, acc=None):
@@ -339,6 +352,8 @@ class _DenseGradientTrainer(_EpochLoop):
         loss = self._loss(batch)
         if acc is not None:
             acc.add_(loss.detach())
+        if self.regularizer is not None:
+            loss = loss + self.regularizer(self.model, *self._penalised(batch), acc)
         loss.backward()
         self.optimizer.step()
         return loss.detach()
@@ -361,8 +376,11 @@ class OneVsAllTrainer(_DenseGradientTrainer):
         return self.model.one_vs_all_loss(batch[0], batch[1], batch[2], side=self.side, label_smoothing=self.label_smoothing,
                                           reduction='mean')
 
+    def _penalised(self, batch):
+        return (batch[0], batch[1]), (batch[2],)
+
     def _prepare(self):
-        if self._facts is None:         # kept: a later run() uploads nothing again
+        if self._facts is None:        # kept: a later run() uploads nothing again
             kg = self.kg_train
             self._facts = (kg.head_idx, kg.tail_idx, kg.relations)
             if self.use_cuda == 'all':
@@ -444,3 +462,7 @@ class KvsAllTrainer(_DenseGradientTrainer):
         side, (e, r, seg_lo, seg_hi) = batch
         return self.model.k_vs_all_loss(e, r, (seg_lo, seg_hi, self._targets[side]), side,
                                         label_smoothing=self.label_smoothing, reduction='mean')
+
+    def _penalised(self, batch):
+        """The key's entity row and relation row."""
+        return (batch[1][0],), (batch[1][1],)
