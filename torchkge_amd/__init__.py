@@ -30,12 +30,17 @@ _NOT_PROVIDED = {
 # stays the list of the reference's eleven model classes: code that enumerates the package's model classes to mirror the
 # reference (the relation-prediction and triplet-classification suites do) sees the reference's set.
 _OWN_MODELS = ('RotatEModel',)
+# Samplers the reference does not have: served the same way, for the same reason.
+_OWN_SAMPLERS = ('FilteredNegativeSampler',)
 
 
 def __getattr__(name):
     if name in _OWN_MODELS:
         from . import models
         return getattr(models, name)
+    if name in _OWN_SAMPLERS:
+        from . import sampling
+        return getattr(sampling, name)
     if name in _NOT_PROVIDED:
         raise NotProvidedError('torchkge_amd does not provide torchkge.%s: %s (see INTEGRATION.md)' % (name, _NOT_PROVIDED[name]))
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -19,7 +19,8 @@ SOURCES = ['score_triples.hip', 'lp_prep.hip', 'lp_gemm_mfma.hip', 'lp_split_mfm
            'lp_split_recheck.hip', 'lp_hi_stream.hip', 'lp_hi_chunk.hip', 'lp_direct.hip', 'lp_l1_sad.hip', 'rank_filter.hip',
            'lp_pairs.hip', 'topk.hip', 'corrupt.hip', 'key_sort.hip', 'index_build.hip', 'bilinear_xform.hip', 'transr_xform.hip', 'analogy.hip', 'convkb.hip',
            'triplet.hip', 'segment_sum_rows.hip', 'segment_sum_ordered.hip', 'relation_corrupt.hip', 'row_optim.hip', 'pair_loss.hip',
-           'redundancy.hip', 'lp_xent.hip', 'lp_bce.hip', 'group_loss.hip', 'score_fact_groups.hip', 'rotate.hip', 'row_penalty.hip']
+           'redundancy.hip', 'lp_xent.hip', 'lp_bce.hip', 'group_loss.hip', 'score_fact_groups.hip', 'rotate.hip', 'row_penalty.hip',
+           'filtered_corrupt.hip']
 HEADERS = ['kge_common.h', 'score_rows.h', 'lp_pair_exact.h', 'rel_operator.h', 'lp_split_common.h', 'lp_operand_cells.h', 'lp_hi_sweep.h', 'mask_scan.h', 'segment_levels.h', 'lp_tile64.h', 'loss_common.h', os.path.join('..', '..', 'include', 'kge_hip.h'),
            os.path.join('..', '..', 'include', 'kge_hip_analogy.h'), os.path.join('..', '..', 'include', 'kge_hip_convkb.h'),
            os.path.join('..', '..', 'include', 'kge_hip_triplet.h'), os.path.join('..', '..', 'include', 'kge_hip_det.h'),
@@ -28,7 +29,7 @@ HEADERS = ['kge_common.h', 'score_rows.h', 'lp_pair_exact.h', 'rel_operator.h', 
            os.path.join('..', '..', 'include', 'kge_hip_xent.h'), os.path.join('..', '..', 'include', 'kge_hip_bce.h'),
            os.path.join('..', '..', 'include', 'kge_hip_plan.h'), os.path.join('..', '..', 'include', 'kge_hip_group.h'),
            os.path.join('..', '..', 'include', 'kge_hip_factgroup.h'), os.path.join('..', '..', 'include', 'kge_hip_rotate.h'),
-           os.path.join('..', '..', 'include', 'kge_hip_penalty.h')]
+           os.path.join('..', '..', 'include', 'kge_hip_penalty.h'), os.path.join('..', '..', 'include', 'kge_hip_filtered.h')]
 LIB = os.path.join(HERE, 'libkge_hip.so')
 # the RCCL exchange step of the sharded path (include/kge_hip_coll.h): its own shared object, so that
 # libkge_hip.so does not depend on librccl
@@ -81,6 +82,8 @@ EXTRA_FLAGS = {'lp_direct.hip': ['-fno-slp-vectorize'], 'lp_hi_stream.hip': _NO_
 # row_penalty.hip (the Lp regularizers: a gathered row streamed once, a square, at most a sqrtf and two products per element)
 # takes NO extra flag, as pair_loss.hip: no MFMA in it or beside it, a packed mul gives the bits of two scalar ones, and the
 # file is bound by its gathered loads and its launches, not by the VALU issue rate.
+# filtered_corrupt.hip (filtered negative sampling: binary searches over int32 lists) has no float operation at all: the
+# common flags.
 
 
 def _hipcc():

@@ -22,13 +22,18 @@ no Python loop over the facts of the graph or the elements of a batch.
 The relation-corrupting sampler's three masked index-puts are one HIP entry
 point as well (kge_relation_corrupt, include/kge_hip_relation.h): two dependent
 prefix counts and one scatter.
+
+``FilteredNegativeSampler`` (the engine's own) draws every replacement exactly
+over the entities that are not known answers of the fact's key, from two
+device-resident FilterIndexes and one kernel (kge_filtered_corrupt,
+include/kge_hip_filtered.h): no rejection loop, no host read.
 """
 from collections import defaultdict
 
 import torch
 from torch import bernoulli, cat, ones, rand, randint, tensor
 
-from . import _hip, _hip_relation, _hip_triplet
+from . import _hip, _hip_filtered, _hip_relation, _hip_triplet
 from .exceptions import NotYetImplementedError
 from .filter_index import FilterIndex, KEY2_SPAN
 from .utils.data import DataLoader
@@ -160,6 +165,94 @@ class BernoulliNegativeSampler(NegativeSampler):
             n_neg = self.n_neg
         self.bern_probs = self.bern_probs.to(heads.device)
         return self._corrupt(heads, tails, self.bern_probs[relations].repeat(n_neg), n_neg)
+
+
+class FilteredNegativeSampler(NegativeSampler):
+    """Head or tail (Bernoulli choice of Wang et al. 2014, or 1/2 with ``bernoulli=False``) replaced by an entity drawn
+    EXACTLY and uniformly over the entities that are not known answers: a replaced tail of (h, r, t) is neither a known
+    tail of (h, r) nor t itself, a replaced head neither a known head of (t, r) nor h itself.  No negative is a known
+    fact and none equals its own fact -- also for a fact that is not among the known ones.  The engine's own: the
+    reference has no filtered sampler.
+
+    The known facts are those of ``filter_graphs`` (default ``(kg,)``), kept as two ``FilterIndex``es -- (h, r) -> tails
+    and (t, r) -> heads -- built from the graphs' OWN triples once per device on first use.  ``kg.filter_index`` is NOT
+    used: a child of ``split_kg`` shares its parent's lazy dictionaries, so that index holds the validation and test
+    facts as well, and a sampler that avoided them would leak the evaluation sets into training.
+
+    Random calls of ``corrupt_batch``, on the batch's device (n = B * n_neg): ``bernoulli(bern_probs[relations]
+    .repeat(n_neg))`` (``bernoulli=False``: of a vector of 1/2) and ``randint(0, 2**62, (n,))``; then two lookups of the
+    B keys and one kge_filtered_corrupt (include/kge_hip_filtered.h), which reduces a draw modulo the number c of free
+    entities of its position and picks the draw-th of them in ascending order.  Both sizes depend on (B, n_neg) alone:
+    nothing is ever read back, ``sync_free`` is accepted and changes nothing.  The modulo bias is below n_ent / 2**62.
+
+    ``exhaustible``: the number of keys whose list leaves fewer than two entities free (read once, when the index is
+    built).  Only a position of such a key can find no free entity; it then keeps its fact unchanged.  While
+    ``exhaustible`` is 0 the kernel writes no flags; otherwise ``last_exhausted`` holds the uint8 flags of the last batch
+    (tile order, 1 = the fact came back unchanged)."""
+
+    def __init__(self, kg, kg_val=None, kg_test=None, n_neg=1, *, bernoulli=True, filter_graphs=None):
+        super().__init__(kg, kg_val, kg_test, n_neg)
+        self.n_rel = kg.n_rel
+        self.bernoulli = bool(bernoulli)
+        self.bern_probs = self.evaluate_probabilities() if self.bernoulli else None
+        self.filter_graphs = (kg,) if filter_graphs is None else tuple(filter_graphs)
+        self._index = {}            # device -> ((h, r) -> tails, (t, r) -> heads)
+        self._exhaustible = None
+        self.last_exhausted = None
+
+    evaluate_probabilities = BernoulliNegativeSampler.evaluate_probabilities
+
+    def indexes(self, device=None):
+        """``(tail index, head index)`` of the known facts on ``device`` (default: where the graph's vectors are), built
+        on first use -- on the GPU by the library's own index builder."""
+        device = self.kg.head_idx.device if device is None else torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        hit = self._index.get(device)
+        if hit is None:
+            h, t, r = _graph_triples(*self.filter_graphs)
+            hit = self._index[device] = (FilterIndex.from_triples_torch(h, r, t, device, self.n_ent, self.n_rel, self.n_ent),
+                                         FilterIndex.from_triples_torch(t, r, h, device, self.n_ent, self.n_rel, self.n_ent))
+            if self._exhaustible is None:       # the one host read, at index build
+                self._exhaustible = sum(int(((ix.offsets[1:] - ix.offsets[:-1]) > self.n_ent - 2).sum().item()) for ix in hit)
+        return hit
+
+    @property
+    def exhaustible(self):
+        if self._exhaustible is None:
+            self.indexes()
+        return self._exhaustible
+
+    def corrupt_batch(self, heads, tails, relations, n_neg=None):
+        if n_neg is None:
+            n_neg = self.n_neg
+        device = heads.device
+        assert device == tails.device
+        _hip.require_cuda(heads, tails, relations)
+        n = heads.shape[0] * n_neg
+        tail_ix, head_ix = self.indexes(device)
+        tail_lo, tail_hi = tail_ix.lookup(heads, relations)
+        head_lo, head_hi = head_ix.lookup(tails, relations)
+        if self.bernoulli:
+            self.bern_probs = self.bern_probs.to(device)
+            probs = self.bern_probs[relations].repeat(n_neg)
+        else:
+            probs = ones(size=(n,), device=device) / 2
+        mask = bernoulli(probs)                                         # RNG draw #1
+        draws = randint(0, 2 ** 62, (n,), device=device)                # draw #2
+        neg_h, neg_t, self.last_exhausted = _hip_filtered.filtered_corrupt(
+            heads, tails, mask.to(torch.uint8), draws, tail_lo, tail_hi, tail_ix.targets, head_lo, head_hi,
+            head_ix.targets, self.n_ent, n_neg, want_exhausted=self._exhaustible > 0)
+        return neg_h, neg_t
+
+    def known(self, heads, tails, relations):
+        """bool mask: which of the triples ``(heads, relations, tails)`` are facts of ``filter_graphs`` (one
+        kge_triples_known against the tail index).  Works for the output of any sampler: with ``relations`` repeated
+        n_neg times it counts the false negatives of a batch."""
+        _hip.require_cuda(heads, tails, relations)
+        tail_ix, _ = self.indexes(heads.device)
+        return _hip_filtered.triples_known(tail_ix.keys, tail_ix.offsets, tail_ix.targets, KEY2_SPAN, heads, relations,
+                                           tails).bool()
 
 
 class _PossibilityIndex(object):
